@@ -1,7 +1,16 @@
 """bench.py -- the hot path on synthetic 640x576 frames against a 100k-triangle mesh.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config bench_100k] [--mode shard|replica]
-                    [--no-cpu-baseline] [--no-extras]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extras]]
+
+A plain run sets up, warms up, times the K steps of the headline region and prints the line.  `--full` adds every
+other region below (fresh_frame, frame_chain, tracking_frame, exhaustive, icp_batched, bench_1m, the replica and
+sharded variants; at N > 1 in shard mode frame_100k and the one-GPU comparison) and the CPU baseline;
+`--no-extras` / `--no-cpu-baseline` drop parts of that again.
+`--dump-outputs DIR` writes what the headline's last timed step returned as DIR/<name>.npy (float32 / float64, every
+value finite): t_hit (-1 where the ray hits nothing: the library's +inf), primitive_ids (u32 as float64, 4294967295
+on a miss) and, when the step registers, icp_transformation, icp_fitness, icp_inlier_rmse, icp_iterations.  The
+inputs are synthetic and seeded: the same arguments give the same inputs.
 
 `--gpus N` without a torchrun environment starts the N ranks itself (fresh child processes,
 spawned before anything touches the GPU; non-zero exit if a rank fails).  Under
@@ -18,9 +27,9 @@ N > 1, --mode shard (default; SURVEY s8e, north_star): ONE frame is split over t
 triangle records replicated, an all-gather of the 8-byte hit records (RCCL over xGMI, issued on the library's stream).
 Strong scaling.  The workload of the N > 1 headline is the one the split is built for, BASELINE config 4: the
 1280x720 dense frame (921,600 rays) against the 1M-triangle mesh, `value` = its rays / the slowest rank's time per
-sharded cast (`config.workload` says so; the same cast on ONE GPU is timed in the same run, `one_gpu_same_workload`,
+sharded cast (`config.workload` says so; with --full the same cast on ONE GPU is timed in the same run, `one_gpu_same_workload`,
 so the line carries its own strong-scaling ratio -- the N = 1 line of this file stays on the metric's own 100k
-configuration, as the contract asks).  The camera-size frame split the same way is timed beside it ("frame_100k":
+configuration, as the contract asks).  With --full the camera-size frame split the same way is timed beside it ("frame_100k":
 a 0.05-ms ray stage and a chain of 21 dependent 33-us passes -- neither pays for a collective, the registration is
 replicated on every rank below a million scene points and every rank gets the identical pose; the scene-sharded
 registration with one 29-double all-reduce per pass is timed under "icp_scene_sharded"), the pose batch of BASELINE
@@ -79,9 +88,48 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="bench_100k")
     ap.add_argument("--mode", choices=["shard", "replica"], default="shard")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the exhaustive / batched / 1M-triangle regions")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also time every region beside the headline and the CPU baseline (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the regions beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Every array as path/<name>.npy, float32 kept, anything else as float64 (exact for the u32 / i32 fields)."""
+    import numpy as np
+
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    bad = [k for k, v in arrays.items() if not np.isfinite(v).all()]
+    if bad:
+        raise RuntimeError(f"--dump-outputs: non-finite values in {bad}")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
+def hit_outputs(t_hit, prim_ids):
+    """A cast's hit records as dumped: t_hit with -1 for a miss (pedp.h: +inf there; the ray's id is 0xFFFFFFFF)."""
+    import numpy as np
+
+    t = np.asarray(t_hit, np.float32)
+    return {"t_hit": np.where(np.isposinf(t), np.float32(-1.0), t), "primitive_ids": prim_ids}
+
+
+def icp_outputs(res):
+    return {"icp_transformation": res["T"], "icp_fitness": [res["fitness"]], "icp_inlier_rmse": [res["inlier_rmse"]],
+            "icp_iterations": [res["iters"]]}
 
 
 def self_launch(args):
@@ -232,9 +280,14 @@ def run(args):
     tgt = _lib.Cloud(ctx, frame.model_points, frame.normals)
     icp_kw = dict(estimator=_lib.POINT_TO_PLANE, max_iteration=ICP_ITERS, relative_fitness=-1.0, relative_rmse=-1.0)
 
+    # N > 1, shard mode on the 100k configuration: the headline is BASELINE config 4's cast (below); the 100k frame in the
+    # same split is a region beside it, timed with --full only
+    big_mode = mode == "shard" and args.config == "bench_100k"
+    frame_100k_region = args.full or not big_mode
+
     # ---- the same frame sharded over the ranks (strong scaling)
     sharded = None
-    if world > 1:   # built in both modes: the headline of one, a timed region beside the headline of the other
+    if world > 1 and (args.full or (mode == "shard" and not big_mode)):   # the headline of one mode, a --full region of the other
         sharded = pdist.ShardedFrame(ray_be, frame.verts_posed, frame.tris, frame.rays6, scene, frame.model_points,
                                      frame.normals, icp_backend=icp_be)
 
@@ -303,17 +356,25 @@ def run(args):
 
     step = step_sharded if mode == "shard" else step_whole
     _lib.icp_configure(ctx, exhaustive=False, timed_pass=TIMED_PASS)
-    elapsed, res, rows = timed_region(step, args.steps, args.warmup)
-    passes, pairs_swept, fb_points = _lib.icp_last_stats(ctx)
-    ms_per_step = 1e3 * elapsed / args.steps
-    # which ray stage answered the timed casts
-    ray_variant, grid_status = rayset.last_variant() if (rayset is not None and mode != "shard") else _lib.raycast_last_variant(ray_ctx)
+    outputs = {}   # what the headline's last timed step returned (--dump-outputs, rank 0)
+    if frame_100k_region:
+        elapsed, res, rows = timed_region(step, args.steps, args.warmup)
+        if args.dump_outputs and rank == 0 and not big_mode:
+            if mode == "shard":
+                t_out, p_out = sharded.hits()
+            else:
+                t_out, p_out = t_hit.cpu().numpy(), prim.cpu().numpy().view(np.uint32)
+            outputs = {**hit_outputs(t_out, p_out), **icp_outputs(res)}
+        passes, pairs_swept, fb_points = _lib.icp_last_stats(ctx)
+        ms_per_step = 1e3 * elapsed / args.steps
+        # which ray stage answered the timed casts
+        ray_variant, grid_status = rayset.last_variant() if (rayset is not None and mode != "shard") else _lib.raycast_last_variant(ray_ctx)
 
     extras = {}
     # ---- N > 1, shard mode: the headline workload is BASELINE config 4 -- the 1280x720 dense frame against the 1M-triangle
     # mesh, rays in contiguous blocks per rank + all-gather of the hit records; K timed casts after W warm-ups
     big_headline = None
-    if mode == "shard" and args.config == "bench_100k":
+    if big_mode:
         big = synth.Frame("bench_1m")
         bf = pdist.ShardedFrame(ray_be, big.verts_posed, big.tris, big.rays6)
         for _ in range(max(args.warmup, 1)):
@@ -329,28 +390,32 @@ def run(args):
         barrier()
         big_elapsed = max_over_ranks(time.perf_counter() - tb)
         big_variant = _lib.raycast_last_variant(ray_ctx)
-        t_all, prim_all = bf.hits()                       # host arrays of the whole frame, from the gathered records
-        # the same cast whole on this rank's GPU (no split, no collective): the line's own one-GPU reference
-        whole = _lib.Mesh(ray_ctx, big.verts_posed, big.tris)
-        rays_w = ray_be.to_device(big.rays6)
-        t_w = torch.empty(big.n_rays, dtype=torch.float32, device=dev)
-        p_w = torch.empty(big.n_rays, dtype=torch.int32, device=dev)
-        for _ in range(2):
-            whole.cast_rays_device(rays_w.data_ptr(), big.n_rays, t_w.data_ptr(), p_w.data_ptr())
-        ray_ctx.synchronize()
-        barrier()
-        tw = time.perf_counter()
-        for _ in range(args.steps):
-            whole.cast_rays_device(rays_w.data_ptr(), big.n_rays, t_w.data_ptr(), p_w.data_ptr())
-            ray_ctx.synchronize()
-        one_gpu = max_over_ranks(time.perf_counter() - tw)
-        same = bool(np.array_equal(t_all.view(np.uint32), t_w.cpu().numpy().view(np.uint32))
-                    and np.array_equal(prim_all, p_w.cpu().numpy().view(np.uint32)))
         big_headline = {"rays": big.n_rays, "tris": big.n_tris, "elapsed": big_elapsed, "sweep_ms": float(np.mean(big_rows)),
-                        "variant": big_variant, "one_gpu_elapsed": one_gpu, "equals_one_gpu": same,
-                        "width": big.width, "height": big.height}
-        del bf, big, whole, rays_w, t_w, p_w, t_all, prim_all
-    if not args.no_extras:
+                        "variant": big_variant, "width": big.width, "height": big.height}
+        if args.full or (args.dump_outputs and rank == 0):
+            t_all, prim_all = bf.hits()                   # host arrays of the whole frame, from the gathered records
+            if args.dump_outputs and rank == 0:
+                outputs = hit_outputs(t_all, prim_all)
+        if args.full:
+            # the same cast whole on this rank's GPU (no split, no collective): the line's own one-GPU reference
+            whole = _lib.Mesh(ray_ctx, big.verts_posed, big.tris)
+            rays_w = ray_be.to_device(big.rays6)
+            t_w = torch.empty(big.n_rays, dtype=torch.float32, device=dev)
+            p_w = torch.empty(big.n_rays, dtype=torch.int32, device=dev)
+            for _ in range(2):
+                whole.cast_rays_device(rays_w.data_ptr(), big.n_rays, t_w.data_ptr(), p_w.data_ptr())
+            ray_ctx.synchronize()
+            barrier()
+            tw = time.perf_counter()
+            for _ in range(args.steps):
+                whole.cast_rays_device(rays_w.data_ptr(), big.n_rays, t_w.data_ptr(), p_w.data_ptr())
+                ray_ctx.synchronize()
+            big_headline["one_gpu_elapsed"] = max_over_ranks(time.perf_counter() - tw)
+            big_headline["equals_one_gpu"] = bool(np.array_equal(t_all.view(np.uint32), t_w.cpu().numpy().view(np.uint32))
+                                                  and np.array_equal(prim_all, p_w.cpu().numpy().view(np.uint32)))
+            del whole, rays_w, t_w, p_w, t_all, prim_all
+        del bf, big
+    if args.full and not args.no_extras:
         # ---- exhaustive region: the all-pairs path, same resident inputs, same sharding
         ex_steps = max(2, min(args.steps, 4))
         plain_cast[0] = True                      # (the exhaustive variants are pedp_raycast's)
@@ -550,10 +615,6 @@ def run(args):
                             trace_us = float(row["AverageNs"]) / 1e3
             except (OSError, KeyError, ValueError):
                 pass
-        icp_ms, ray_ms, sweep_ms = (float(v) for v in rows.mean(axis=0))
-        n_pass = max(passes, 1)
-        pairs_pass = pairs_swept / n_pass
-        sweep_tflops = FLOP_PER_PAIR * pairs_pass / (sweep_ms * 1e-3) / 1e12
         par = {"single": "one GPU; ray stage and ICP of a step overlap on two HIP streams",
                "shard": f"one frame sharded over {world} GPUs: contiguous ray blocks + all-gather of hit records "
                         f"({'library-issued RCCL' if native else 'torch.distributed'}); the frame's one registration "
@@ -564,46 +625,53 @@ def run(args):
         frames_per_step = world if mode == "replica" else 1
         out = {
             "metric": "Mrays/s ray-mesh + ICP iters/s, 640x576 vs 100k-tri mesh",
-            "value": frames_per_step * n_rays * args.steps / elapsed / 1e6,
+            "value": frames_per_step * n_rays * args.steps / elapsed / 1e6 if frame_100k_region else None,
             "unit": "Mrays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
+            "ms_per_step": ms_per_step if frame_100k_region else None,   # (both set below when the headline is config 4)
             "higher_is_better": True, "scaling": "weak" if mode == "replica" else "strong", "vs_baseline": None,
             "dtype": "f32 rays / f64 ICP (f32 MFMA filter)", "data": "synthetic" + (" (REHEARSAL: all ranks on one GPU over gloo, not a measurement)" if rehearsal else ""),
             "config": {"workload": f"{args.config}: {frame.width}x{frame.height} frame, {n_rays} rays x {n_tris} "
                                    f"triangles + {ICP_ITERS}-iteration point-to-plane ICP ({n_scene} scene x "
                                    f"{n_model} model points) per step",
                        "parallelism": par, "mode": mode},
-            "ray_stage_ms": ray_ms, "ray_stage_mrays_per_s": (n_rays / world if mode == "shard" else n_rays) / (ray_ms * 1e-3) / 1e6,
-            "icp_ms": icp_ms, "icp_iters_per_s": ICP_ITERS / (icp_ms * 1e-3),
-            "icp_passes": passes, "icp_pairs_swept_per_pass": pairs_pass,
-            "icp_fallback_points_per_pass": fb_points / n_pass,
-            "icp_fitness": res["fitness"], "icp_inlier_rmse": res["inlier_rmse"],
-            "pose_error_vs_gt": float(np.abs(np.linalg.inv(res["T"]) - frame.T_gt).max()),
-            # dominant kernel of the HEADLINE step as it runs there (rank 0's share in shard mode)
-            "ray_variant": ray_variant, "ray_grid_status": grid_status,
-            "ray_stage_form": "resident ray set (pedp_raycast_rayset: grid chains built once; 4 launches per cast)" if rayset is not None
-                              else "pedp_raycast per call (rays read twice, chains rebuilt; 6 launches)",
-            "ray_stage_ms_per_call_form": extras.get("plain_cast_ms"),
-            "roofline": {"kernel": "icp_pass_kernel (one launch per pass: per-chunk transform, culling, MFMA sweep, selection, partial "
-                                   "sums; the last workgroup sums, solves and updates the pose)", "region": "headline", "bound": "mfma",
-                         "achieved": sweep_tflops, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                         "frac": sweep_tflops / PEAK_FP32_TFLOPS,
-                         "traffic": traffic.get("icp_pass_kernel", {}).get("hbm_bytes_per_launch"),
-                         "traffic_source": traffic_source,
-                         "mfma_util_pmc_committed_profile": traffic.get("icp_pass_kernel", {}).get("mfma_util"),
-                         "kernel_ms": sweep_ms, "launches_per_step": passes,
-                         "kernel_ms_x_launches": sweep_ms * passes, "region_ms_per_step": ms_per_step,
-                         "kernel_us_committed_kernel_trace": trace_us,
-                         "note": f"{FLOP_PER_PAIR} flop x {pairs_pass:.4g} (scene slot, model point) pairs the kernel swept per "
-                                 "pass (16 x 16 per MFMA, mean over the passes) / mean launch-to-launch time of the kernel: ONE "
-                                 "HIP-event pair around the 21 launches of every registration of the timed loop, span / 21, "
-                                 "launch boundaries included (kernel_us_committed_kernel_trace is its mean dispatch-to-completion "
-                                 "span in the rocprofv3 kernel trace under profiles/).  The launch is "
-                                 "the WHOLE pass (the finish kernel of round 2 is inside it); it is one workgroup per live scene "
-                                 "chunk and is bound by its chain of dependent memory accesses and by the serial close of the "
-                                 "pass (DESIGN s4.2), not by the matrix pipe: the MFMA fraction says how little of it is arithmetic"},
         }
+        if frame_100k_region:   # the 100k frame's timed region: its stage split and roofline
+            icp_ms, ray_ms, sweep_ms = (float(v) for v in rows.mean(axis=0))
+            n_pass = max(passes, 1)
+            pairs_pass = pairs_swept / n_pass
+            sweep_tflops = FLOP_PER_PAIR * pairs_pass / (sweep_ms * 1e-3) / 1e12
+            out.update({
+                "ray_stage_ms": ray_ms, "ray_stage_mrays_per_s": (n_rays / world if mode == "shard" else n_rays) / (ray_ms * 1e-3) / 1e6,
+                "icp_ms": icp_ms, "icp_iters_per_s": ICP_ITERS / (icp_ms * 1e-3),
+                "icp_passes": passes, "icp_pairs_swept_per_pass": pairs_pass,
+                "icp_fallback_points_per_pass": fb_points / n_pass,
+                "icp_fitness": res["fitness"], "icp_inlier_rmse": res["inlier_rmse"],
+                "pose_error_vs_gt": float(np.abs(np.linalg.inv(res["T"]) - frame.T_gt).max()),
+                # dominant kernel of the HEADLINE step as it runs there (rank 0's share in shard mode)
+                "ray_variant": ray_variant, "ray_grid_status": grid_status,
+                "ray_stage_form": "resident ray set (pedp_raycast_rayset: grid chains built once; 4 launches per cast)" if rayset is not None
+                                  else "pedp_raycast per call (rays read twice, chains rebuilt; 6 launches)",
+                "ray_stage_ms_per_call_form": extras.get("plain_cast_ms"),
+                "roofline": {"kernel": "icp_pass_kernel (one launch per pass: per-chunk transform, culling, MFMA sweep, selection, partial "
+                                       "sums; the last workgroup sums, solves and updates the pose)", "region": "headline", "bound": "mfma",
+                             "achieved": sweep_tflops, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                             "frac": sweep_tflops / PEAK_FP32_TFLOPS,
+                             "traffic": traffic.get("icp_pass_kernel", {}).get("hbm_bytes_per_launch"),
+                             "traffic_source": traffic_source,
+                             "mfma_util_pmc_committed_profile": traffic.get("icp_pass_kernel", {}).get("mfma_util"),
+                             "kernel_ms": sweep_ms, "launches_per_step": passes,
+                             "kernel_ms_x_launches": sweep_ms * passes, "region_ms_per_step": ms_per_step,
+                             "kernel_us_committed_kernel_trace": trace_us,
+                             "note": f"{FLOP_PER_PAIR} flop x {pairs_pass:.4g} (scene slot, model point) pairs the kernel swept per "
+                                     "pass (16 x 16 per MFMA, mean over the passes) / mean launch-to-launch time of the kernel: ONE "
+                                     "HIP-event pair around the 21 launches of every registration of the timed loop, span / 21, "
+                                     "launch boundaries included (kernel_us_committed_kernel_trace is its mean dispatch-to-completion "
+                                     "span in the rocprofv3 kernel trace under profiles/).  The launch is "
+                                     "the WHOLE pass (the finish kernel of round 2 is inside it); it is one workgroup per live scene "
+                                     "chunk and is bound by its chain of dependent memory accesses and by the serial close of the "
+                                     "pass (DESIGN s4.2), not by the matrix pipe: the MFMA fraction says how little of it is arithmetic"},
+            })
         if "exhaustive" in extras:
             ex_steps, ex_elapsed, ex_res, ex_rows, ex_passes, ex_pairs = extras["exhaustive"]
             ex_ms = 1e3 * ex_elapsed / ex_steps
@@ -754,12 +822,13 @@ def run(args):
         if big_headline is not None:
             # the N > 1 headline: BASELINE config 4's cast, sharded; what the 100k frame did in the same split moves aside
             bh = big_headline
-            out["frame_100k"] = {k: out[k] for k in ("value", "ms_per_step", "ray_stage_ms", "ray_stage_mrays_per_s", "icp_ms",
-                                                      "icp_iters_per_s", "icp_passes", "icp_fitness", "pose_error_vs_gt", "ray_variant",
-                                                      "ray_grid_status", "roofline")}
-            out["frame_100k"]["workload"] = out["config"]["workload"]
-            out["frame_100k"]["note"] = ("the camera-size frame in the same split (rays in blocks + all-gather, the registration "
-                                         "replicated): a 0.05-ms ray stage does not pay for a collective")
+            if frame_100k_region:
+                out["frame_100k"] = {k: out[k] for k in ("value", "ms_per_step", "ray_stage_ms", "ray_stage_mrays_per_s", "icp_ms",
+                                                          "icp_iters_per_s", "icp_passes", "icp_fitness", "pose_error_vs_gt",
+                                                          "ray_variant", "ray_grid_status", "roofline")}
+                out["frame_100k"]["workload"] = out["config"]["workload"]
+                out["frame_100k"]["note"] = ("the camera-size frame in the same split (rays in blocks + all-gather, the registration "
+                                             "replicated): a 0.05-ms ray stage does not pay for a collective")
             for k in ("ray_stage_ms", "ray_stage_mrays_per_s", "icp_ms", "icp_iters_per_s", "icp_passes", "icp_pairs_swept_per_pass",
                       "icp_fallback_points_per_pass", "icp_fitness", "icp_inlier_rmse", "pose_error_vs_gt"):
                 out.pop(k, None)
@@ -771,11 +840,12 @@ def run(args):
             out["config"]["workload"] = (f"bench_1m (BASELINE config 4): {bh['width']}x{bh['height']} dense frame, {bh['rays']} rays x "
                                          f"{bh['tris']} triangles per step, ray stage (the split's workload; the 100k frame under frame_100k)")
             out["ray_variant"], out["ray_grid_status"] = bh["variant"]
-            out["hits_equal_one_gpu_cast"] = bh["equals_one_gpu"]
-            out["one_gpu_same_workload"] = {"ms_per_step": 1e3 * bh["one_gpu_elapsed"] / args.steps,
-                                            "value_mrays_per_s": bh["rays"] * args.steps / bh["one_gpu_elapsed"] / 1e6,
-                                            "note": "the whole cast on one of these GPUs, no split, no collective, same run"}
-            out["strong_scaling_speedup"] = bh["one_gpu_elapsed"] / bh["elapsed"]
+            if "one_gpu_elapsed" in bh:   # --full
+                out["hits_equal_one_gpu_cast"] = bh["equals_one_gpu"]
+                out["one_gpu_same_workload"] = {"ms_per_step": 1e3 * bh["one_gpu_elapsed"] / args.steps,
+                                                "value_mrays_per_s": bh["rays"] * args.steps / bh["one_gpu_elapsed"] / 1e6,
+                                                "note": "the whole cast on one of these GPUs, no split, no collective, same run"}
+                out["strong_scaling_speedup"] = bh["one_gpu_elapsed"] / bh["elapsed"]
             algo = 24.0 * bh["rays"] / world + 48.0 * bh["tris"] + 8.0 * bh["rays"] / world
             gbs = algo / (bh["sweep_ms"] * 1e-3) / 1e9
             out["roofline"] = {"kernel": "triangle-driven ray stage (rast_* kernels of one cast) on this rank's ray block", "region": "headline",
@@ -785,8 +855,10 @@ def run(args):
                                "note": "algorithmic bytes of rank 0's share of a cast (24 B per ray in, 48 B per triangle record, 8 B per "
                                        "ray out) / the HIP-event span of the cast's kernels on the ray stream; the rest of a step is the "
                                        "all-gather of the hit records"}
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(frame, depth)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

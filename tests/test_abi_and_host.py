@@ -22,6 +22,9 @@ def test_library_exports_every_declared_symbol():
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     declared = set(re.findall(r"\b(pedp_[a-z0-9_]+)\s*\(", header)) - {"pedp_allreduce_fn"}
     assert len(declared) >= 20
+    # the package's load order first (torch, then the library): a bare dlopen before torch is imported would bring the
+    # system HIP runtime in ahead of torch's copy, and with a GPU present the two runtimes in one process fight over it
+    _lib.load()
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/pedp.h but not exported"
