@@ -319,48 +319,53 @@ int pedp_ctx_synchronize(pedp_ctx_t c) {
 namespace {
 
 constexpr int CS_BLOCKS = 512, CS_THREADS = 256;
+constexpr int CS_PART = 10;  // per workgroup: sum xyz, lo xyz, hi xyz, number of finite rows
 
-// per-workgroup partial sums and bounds of a device-resident cloud (fixed tree: deterministic)
+// per-workgroup partial sums and bounds of a device-resident cloud (fixed tree: deterministic); rows with a
+// non-finite coordinate are left out (they are never a neighbour, and the box must stay finite for the spatial order)
 __global__ __launch_bounds__(CS_THREADS) void cloud_sum_kernel(const double *__restrict__ pts, int64_t N,
-                                                               double *__restrict__ part /* CS_BLOCKS x 9 */) {
-    __shared__ double sh[CS_THREADS / 64][9];
+                                                               double *__restrict__ part /* CS_BLOCKS x CS_PART */) {
+    __shared__ double sh[CS_THREADS / 64][CS_PART];
     const double big = 1.7976931348623157e308;
-    double v[9] = {0, 0, 0, big, big, big, -big, -big, -big};
-    for (int64_t i = (int64_t)blockIdx.x * CS_THREADS + threadIdx.x; i < N; i += (int64_t)CS_BLOCKS * CS_THREADS)
+    double v[CS_PART] = {0, 0, 0, big, big, big, -big, -big, -big, 0};
+    for (int64_t i = (int64_t)blockIdx.x * CS_THREADS + threadIdx.x; i < N; i += (int64_t)CS_BLOCKS * CS_THREADS) {
+        if (!pedp_row_finite(pts, i)) continue;
         for (int k = 0; k < 3; ++k) {
             const double x = pts[3 * i + k];
             v[k] += x;
             v[3 + k] = x < v[3 + k] ? x : v[3 + k];
             v[6 + k] = x > v[6 + k] ? x : v[6 + k];
         }
-    for (int k = 0; k < 9; ++k) {
+        v[9] += 1.0;
+    }
+    for (int k = 0; k < CS_PART; ++k) {
         double x = v[k];
         for (int off = 32; off >= 1; off >>= 1) {
             const double o = __shfl_xor(x, off, 64);
-            x = k < 3 ? x + o : (k < 6 ? (o < x ? o : x) : (o > x ? o : x));
+            x = (k < 3 || k == 9) ? x + o : (k < 6 ? (o < x ? o : x) : (o > x ? o : x));
         }
         if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = x;
     }
     __syncthreads();
-    if (threadIdx.x < 9) {
+    if (threadIdx.x < CS_PART) {
         const int k = threadIdx.x;
         double x = sh[0][k];
         for (int w = 1; w < CS_THREADS / 64; ++w) {
             const double o = sh[w][k];
-            x = k < 3 ? x + o : (k < 6 ? (o < x ? o : x) : (o > x ? o : x));
+            x = (k < 3 || k == 9) ? x + o : (k < 6 ? (o < x ? o : x) : (o > x ? o : x));
         }
-        part[blockIdx.x * 9 + k] = x;
+        part[blockIdx.x * CS_PART + k] = x;
     }
 }
 
 // the box alone, folded on the device into the cloud's own six doubles: nothing comes back to the host
-__global__ __launch_bounds__(64) void cloud_box_fold_kernel(const double *__restrict__ part /* CS_BLOCKS x 9 */, double *__restrict__ box) {
+__global__ __launch_bounds__(64) void cloud_box_fold_kernel(const double *__restrict__ part /* CS_BLOCKS x CS_PART */, double *__restrict__ box) {
     const int lane = threadIdx.x;
     double lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { lo[k] = part[lane * 9 + 3 + k]; hi[k] = part[lane * 9 + 6 + k]; }
+    for (int k = 0; k < 3; ++k) { lo[k] = part[lane * CS_PART + 3 + k]; hi[k] = part[lane * CS_PART + 6 + k]; }
     for (int b = lane + 64; b < CS_BLOCKS; b += 64)
         for (int k = 0; k < 3; ++k) {
-            const double l2 = part[b * 9 + 3 + k], h2 = part[b * 9 + 6 + k];
+            const double l2 = part[b * CS_PART + 3 + k], h2 = part[b * CS_PART + 6 + k];
             lo[k] = l2 < lo[k] ? l2 : lo[k];
             hi[k] = h2 > hi[k] ? h2 : hi[k];
         }
@@ -380,6 +385,7 @@ __global__ __launch_bounds__(CS_THREADS) void cloud_norm_kernel(const double *__
     __shared__ float sh[CS_THREADS / 64][2];
     float n1m = 0.f, n2m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * CS_THREADS + threadIdx.x; i < N; i += (int64_t)CS_BLOCKS * CS_THREADS) {
+        if (!pedp_row_finite(pts, i)) continue;
         const float x = (float)(pts[3 * i] - cx), y = (float)(pts[3 * i + 1] - cy), z = (float)(pts[3 * i + 2] - cz);
         n1m = fmaxf(n1m, fabsf(x) + fabsf(y) + fabsf(z));
         n2m = fmaxf(n2m, x * x + y * y + z * z);
@@ -414,24 +420,29 @@ pedp_cloud_s *new_cloud(pedp_ctx_t c, int64_t N) {
 int pedp_cloud_host_stats(pedp_ctx_t c, pedp_cloud_s *cl) {
     if (cl->host_stats || cl->N == 0) { cl->host_stats = true; return PEDP_OK; }
     const int64_t N = cl->N;
-    double part[CS_BLOCKS * 9];
+    double part[CS_BLOCKS * CS_PART];
     float fpart[CS_BLOCKS * 2];
-    int st = c->ops.reserve(sizeof(double) * CS_BLOCKS * 9 + sizeof(float) * CS_BLOCKS * 2 + 512);
+    int st = c->ops.reserve(sizeof(double) * CS_BLOCKS * CS_PART + sizeof(float) * CS_BLOCKS * 2 + 512);
     if (st) return st;
     double *d_part = (double *)c->ops.ptr;
-    float *d_fpart = (float *)(d_part + CS_BLOCKS * 9);
+    float *d_fpart = (float *)(d_part + CS_BLOCKS * CS_PART);
     hipLaunchKernelGGL(cloud_sum_kernel, dim3(CS_BLOCKS), dim3(CS_THREADS), 0, c->stream, (const double *)cl->pts, N, d_part);
     PEDP_HIP_CHECK(hipMemcpyAsync(part, d_part, sizeof(part), hipMemcpyDeviceToHost, c->stream));
     PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
-    double sum[3] = {0, 0, 0};
+    double sum[3] = {0, 0, 0}, n_fin = 0.0;
     for (int k = 0; k < 3; ++k) { cl->lo[k] = part[3 + k]; cl->hi[k] = part[6 + k]; }
-    for (int b = 0; b < CS_BLOCKS; ++b)
+    for (int b = 0; b < CS_BLOCKS; ++b) {
         for (int k = 0; k < 3; ++k) {
-            sum[k] += part[b * 9 + k];
-            if (part[b * 9 + 3 + k] < cl->lo[k]) cl->lo[k] = part[b * 9 + 3 + k];
-            if (part[b * 9 + 6 + k] > cl->hi[k]) cl->hi[k] = part[b * 9 + 6 + k];
+            sum[k] += part[b * CS_PART + k];
+            if (part[b * CS_PART + 3 + k] < cl->lo[k]) cl->lo[k] = part[b * CS_PART + 3 + k];
+            if (part[b * CS_PART + 6 + k] > cl->hi[k]) cl->hi[k] = part[b * CS_PART + 6 + k];
         }
-    for (int k = 0; k < 3; ++k) cl->centroid[k] = sum[k] / (double)N;
+        n_fin += part[b * CS_PART + 9];
+    }
+    cl->n_finite = (int64_t)n_fin;
+    if (cl->n_finite == 0)
+        for (int k = 0; k < 3; ++k) cl->lo[k] = cl->hi[k] = 0.0;
+    for (int k = 0; k < 3; ++k) cl->centroid[k] = cl->n_finite > 0 ? sum[k] / n_fin : 0.0;
     hipLaunchKernelGGL(cloud_norm_kernel, dim3(CS_BLOCKS), dim3(CS_THREADS), 0, c->stream, (const double *)cl->pts, N,
                        cl->centroid[0], cl->centroid[1], cl->centroid[2], d_fpart);
     PEDP_HIP_CHECK(hipMemcpyAsync(fpart, d_fpart, sizeof(fpart), hipMemcpyDeviceToHost, c->stream));
@@ -456,12 +467,22 @@ int pedp_cloud_create(pedp_ctx_t c, const double *pts, const double *normals, in
     pedp_cloud_s *cl = new_cloud(c, N);
     if (!cl) return PEDP_ERR_ALLOC;
     if (N > 0) {
+        // centroid, box and magnitudes over the finite rows (a row with a NaN or infinite coordinate is never a
+        // neighbour; the spatial order puts it behind all the others)
         double sum[3] = {0, 0, 0};
-        for (int64_t i = 0; i < N; ++i) { sum[0] += pts[3 * i]; sum[1] += pts[3 * i + 1]; sum[2] += pts[3 * i + 2]; }
-        for (int k = 0; k < 3; ++k) cl->centroid[k] = sum[k] / (double)N;
-        for (int k = 0; k < 3; ++k) { cl->lo[k] = pts[k]; cl->hi[k] = pts[k]; }
+        int64_t n_fin = 0, first = -1;
+        for (int64_t i = 0; i < N; ++i) {
+            if (!pedp_row_finite(pts, i)) continue;
+            sum[0] += pts[3 * i]; sum[1] += pts[3 * i + 1]; sum[2] += pts[3 * i + 2];
+            if (first < 0) first = i;
+            ++n_fin;
+        }
+        cl->n_finite = n_fin;
+        for (int k = 0; k < 3; ++k) cl->centroid[k] = n_fin > 0 ? sum[k] / (double)n_fin : 0.0;
+        for (int k = 0; k < 3; ++k) { cl->lo[k] = first >= 0 ? pts[3 * first + k] : 0.0; cl->hi[k] = cl->lo[k]; }
         float Tn = 0.f, T2 = 0.f;
         for (int64_t i = 0; i < N; ++i) {
+            if (!pedp_row_finite(pts, i)) continue;
             for (int k = 0; k < 3; ++k) {
                 if (pts[3 * i + k] < cl->lo[k]) cl->lo[k] = pts[3 * i + k];
                 if (pts[3 * i + k] > cl->hi[k]) cl->hi[k] = pts[3 * i + k];
@@ -527,7 +548,7 @@ int pedp_cloud_create_device(pedp_ctx_t c, const double *d_pts, const double *d_
     if (ok && e == hipSuccess && N > 0) e = hipEventRecord(c->ev_copy, c->stream);
     const bool wait_copies = ok && e == hipSuccess && N > 0;
     if (ok && e == hipSuccess && N > 0) {
-        const int st = c->sort_ws.reserve(sizeof(double) * CS_BLOCKS * 9 + 512);   // (the order's scratch: next in line on this stream)
+        const int st = c->sort_ws.reserve(sizeof(double) * CS_BLOCKS * CS_PART + 512);   // (the order's scratch: next in line on this stream)
         if (st) { pedp_cloud_destroy(cl); return st; }
         double *d_part = (double *)c->sort_ws.ptr;
         hipLaunchKernelGGL(cloud_sum_kernel, dim3(CS_BLOCKS), dim3(CS_THREADS), 0, c->stream, (const double *)cl->pts, N, d_part);

@@ -198,6 +198,7 @@ __device__ __forceinline__ unsigned long long point_cell(const double *__restric
                                                          double loz, double sx, double sy, double sz) {
     const double fx = (pts[3 * i] - lox) * sx, fy = (pts[3 * i + 1] - loy) * sy, fz = (pts[3 * i + 2] - loz) * sz;
     const double top = (double)(1 << SORT_BITS);
+    if (!pedp_row_finite(pts, i)) return 1ull << (3 * SORT_BITS);  // (bit test: this file is built with -fno-honor-nans)
     if (!(fx >= 0.0 && fx < top && fy >= 0.0 && fy < top && fz >= 0.0 && fz < top)) return 1ull << (3 * SORT_BITS);
     return hilbert3((unsigned)(int)fx, (unsigned)(int)fy, (unsigned)(int)fz);
 }
@@ -258,6 +259,10 @@ __global__ __launch_bounds__(64) void chunk_sphere_kernel(const double *__restri
 }
 
 // ------------------------------------------------------------------ target preparation
+// Rows of a target that take part in the search: the finite ones (host statistics count them; they come first in
+// the spatial order, the non-finite ones last).  A non-finite row is never a neighbour.
+inline int64_t target_rows(pedp_cloud_t t) { return t->n_finite >= 0 ? t->n_finite : t->N; }
+
 // Sorted target operand: row k holds point perm[k] as float4 (x', y', z', |t'|^2), centred on
 // c; pad rows can never win.  One bounding sphere per 64-row unit (centred coordinates);
 // radius < 0 marks a unit without real points.
@@ -2981,7 +2986,7 @@ inline bool nn_bf16_sweep() {  // PEDP_NN_F32=1: the dense sweep on the f32-inpu
 }
 int enqueue_nn_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_cloud_t tgt, int mode,
                     const TargetPrep &tp, double r, hipEvent_t ev0, hipEvent_t ev1, bool exhaustive = false) {
-    const int64_t Ns = src->N, Nt = tgt->N;
+    const int64_t Ns = src->N, Nt = target_rows(tgt);
     // r1: distance scale of the candidates the bound must hold for (anything farther is
     // not an inlier anyway); huge radii fall back to the cloud scale inside the kernel.
     const float r1 = (float)(r * 1.01);
@@ -3069,7 +3074,7 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pe
     pa.chunk_sph = (const double *)src->chunk_sph;
     pa.pp_stride = 3 * (size_t)w.Ns_pad;
     pa.tgtf = (const float *)w.tgt4; pa.n_tiles = (int)(w.Nt_pad / 16); pa.n_words = w.n_words;
-    pa.tile_sph = w.tile_sph; pa.word_sph = w.word_sph; pa.tgt_s = w.tgt_s; pa.tperm = w.tgt_perm; pa.Nt = tgt->N;
+    pa.tile_sph = w.tile_sph; pa.word_sph = w.word_sph; pa.tgt_s = w.tgt_s; pa.tperm = w.tgt_perm; pa.Nt = target_rows(tgt);
     pa.tgt = tgt->pts; pa.nrm = tgt->normals;
     pa.Tn = tp.Tn; pa.T2 = tp.T2;
     for (int k = 0; k < 3; ++k) { pa.lo[k] = tp.lo[k]; pa.hi[k] = tp.hi[k]; pa.bc[k] = 0.5 * (tp.lo[k] + tp.hi[k]); }
@@ -3135,6 +3140,7 @@ int ensure_target_pack(pedp_ctx_t c, pedp_cloud_t tgt, TargetPrep &tp) {
     if (tgt->tgt4) return PEDP_OK;
     int rc = ensure_spatial_perm(c, tgt);
     if (rc) return rc;
+    const int64_t nt = target_rows(tgt);  // the finite rows: first in the spatial order, the only ones in the operand
     // real tiles rounded to NN_TU, plus readable pad tiles the pipelined sweep may prefetch
     int64_t pad = (int64_t)align_up((size_t)(tgt->N > 0 ? tgt->N : 1), 16 * NN_TU) + 16 * NN_TILE_PAD;
     // all three or none: a half-built pack must not look finished to the next call
@@ -3162,15 +3168,15 @@ int ensure_target_pack(pedp_ctx_t c, pedp_cloud_t tgt, TargetPrep &tp) {
     tgt->tgt4_pad = pad;
     int64_t grid = (pad + 255) / 256;
     hipLaunchKernelGGL(pack_target_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, tgt->pts,
-                       (const int32_t *)tgt->perm, tgt->N, pad, tp.c[0], tp.c[1], tp.c[2], (float4 *)tgt->tgt4);
+                       (const int32_t *)tgt->perm, nt, pad, tp.c[0], tp.c[1], tp.c[2], (float4 *)tgt->tgt4);
     hipLaunchKernelGGL(tile_sphere_kernel, dim3((unsigned)((pad / 16 + 255) / 256)), dim3(256), 0, c->stream,
-                       (const float4 *)tgt->tgt4, tgt->N, pad / 16, 16, (float4 *)tgt->tile_sph);
+                       (const float4 *)tgt->tgt4, nt, pad / 16, 16, (float4 *)tgt->tile_sph);
     hipLaunchKernelGGL(tile_sphere_kernel, dim3((unsigned)((pad / 64 + 255) / 256)), dim3(256), 0, c->stream,
-                       (const float4 *)tgt->tgt4, tgt->N, pad / 64, 64, (float4 *)tgt->tile_sph4);
+                       (const float4 *)tgt->tgt4, nt, pad / 64, 64, (float4 *)tgt->tile_sph4);
     hipLaunchKernelGGL(tile_sphere_kernel, dim3((unsigned)((n_wsph + 63) / 64)), dim3(64), 0, c->stream,
-                       (const float4 *)tgt->tgt4, tgt->N, n_wsph, 1024, (float4 *)tgt->tile_sphw);
+                       (const float4 *)tgt->tgt4, nt, n_wsph, 1024, (float4 *)tgt->tile_sphw);
     hipLaunchKernelGGL(sort_rows_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, tgt->pts, tgt->normals,
-                       (const int32_t *)tgt->perm, tgt->N, pad, (double *)tgt->tgt_s);
+                       (const int32_t *)tgt->perm, nt, pad, (double *)tgt->tgt_s);
     PEDP_HIP_CHECK(hipGetLastError());
     return PEDP_OK;
 }
@@ -3248,7 +3254,7 @@ int icp_job_setup(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const 
     PEDP_HIP_CHECK(hipSetDevice(x->device));
     job.max_iter = prm->max_iteration;
     job.Ns = source->N;
-    job.Nt = target->N;
+    job.Nt = target_rows(target);
     job.qt = x->icp_exhaustive ? 4 : icp_unit_size(target, prm->max_correspondence_distance);
     job.exhaustive = x->icp_exhaustive;
     job.timed_pass = x->icp_timed_pass;
@@ -3301,7 +3307,7 @@ void icp_fill_state(IcpState *dst, const TargetPrep &tp, const double init[16], 
 // early_stop is set, so the sequence can be captured into a graph
 int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp,
                 const pedp_icp_params *prm, bool want_trace, bool early_stop, const IcpJob &job) {
-    const int64_t Ns = source->N, Nt = target->N;
+    const int64_t Ns = source->N, Nt = target_rows(target);
     const int max_iter = prm->max_iteration;
     const double r = prm->max_correspondence_distance;
     const double n_global = prm->n_source_global > 0 ? (double)prm->n_source_global : (double)Ns;
@@ -3496,7 +3502,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
     IcpJob job;
     job.max_iter = prms[0].max_iteration;
     job.Ns = source->N;
-    job.Nt = target->N;
+    job.Nt = target_rows(target);
     job.qt = 1;
     IcpWorkspace &w = job.w;
     int rc = carve_workspace(c, job.Ns, job.Nt, job.max_iter, 1, w, true, G);
@@ -3700,8 +3706,8 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
     bool all_fused = !c->icp_exhaustive;
     for (int b = 0; b < B && all_fused; ++b) {
         const double r = prms[b].max_correspondence_distance;
-        all_fused = icp_unit_size(target, r) == 1 && r > 0.0 && source->N > 0 && target->N > 0 &&
-                    (target->N + 1023) / 1024 <= BK_WCAP;
+        all_fused = icp_unit_size(target, r) == 1 && r > 0.0 && source->N > 0 && target_rows(target) > 0 &&
+                    (target_rows(target) + 1023) / 1024 <= BK_WCAP;
     }
     if (all_fused) return icp_batch_fused(c, source, target, tp, prms, inits, B, T_out, fitness, inlier_rmse, n_iter_done);
     if (!uniform) {
@@ -3778,14 +3784,19 @@ int pedp_nn(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const double
     PEDP_REQUIRE(c && source && target && T && idx && d2, "pedp_nn: null argument");
     PEDP_REQUIRE(source->ctx == c && target->ctx == c, "pedp_nn: cloud belongs to another context");
     PEDP_REQUIRE(target->N > 0, "pedp_nn: empty target");
+    PEDP_REQUIRE(!c->icp_pending, "pedp_nn: a registration is pending on this context (pedp_icp_end first)");
     if (source->N == 0) return PEDP_OK;
     PEDP_HIP_CHECK(hipSetDevice(c->device));
-    IcpWorkspace w;
-    int rc = carve_workspace(c, source->N, target->N, 0, 4, w);  // no radius: dense sweep, 64-row units
-    if (rc) return rc;
     TargetPrep tp;
-    rc = ensure_target_pack(c, target, tp);
+    int rc = ensure_target_pack(c, target, tp);
     if (!rc) rc = ensure_target_bf16(c, target);
+    if (rc) return rc;
+    if (target_rows(target) == 0) {  // no finite target row: no neighbour anywhere
+        for (int64_t i = 0; i < source->N; ++i) { idx[i] = -1; d2[i] = HUGE_VAL; }
+        return PEDP_OK;
+    }
+    IcpWorkspace w;
+    rc = carve_workspace(c, source->N, target_rows(target), 0, 4, w);  // no radius: dense sweep, 64-row units
     if (rc) return rc;
     w.tgt4 = (const float4 *)target->tgt4;
     w.tile_sph = (const float4 *)target->tile_sph4;
@@ -3814,6 +3825,7 @@ int pedp_ransac_hypotheses(pedp_ctx_t c, pedp_cloud_t src, pedp_cloud_t tgt, con
                            double *T) {
     PEDP_REQUIRE(c && src && tgt, "pedp_ransac_hypotheses: null context / cloud");
     PEDP_REQUIRE(src->ctx == c && tgt->ctx == c, "pedp_ransac_hypotheses: clouds belong to another context");
+    PEDP_REQUIRE(!c->icp_pending, "pedp_ransac_hypotheses: a registration is pending on this context (pedp_icp_end first)");
     PEDP_REQUIRE(count >= 0 && count <= (1 << 22) && itr0 >= 0, "pedp_ransac_hypotheses: count must be in 0..2^22");
     if (count == 0) return PEDP_OK;
     PEDP_REQUIRE(corr && accepted && T, "pedp_ransac_hypotheses: null arrays");
@@ -3843,6 +3855,7 @@ int pedp_ransac_hypotheses(pedp_ctx_t c, pedp_cloud_t src, pedp_cloud_t tgt, con
 
 int pedp_icp_configure(pedp_ctx_t c, int exhaustive, int timed_pass) {
     PEDP_REQUIRE(c, "pedp_icp_configure: null context");
+    PEDP_REQUIRE(!c->icp_pending, "pedp_icp_configure: a registration is pending on this context (pedp_icp_end first)");
     c->icp_exhaustive = exhaustive != 0;
     c->icp_timed_pass = timed_pass;
     for (int k = 0; k < PEDP_MAX_SUB; ++k)  // captured graphs bake the mode in

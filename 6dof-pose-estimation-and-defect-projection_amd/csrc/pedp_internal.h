@@ -28,6 +28,15 @@ struct pedp_ctx_s;
 int pedp_sort_keys64_begin(pedp_ctx_s *c, int64_t N, int bits, unsigned long long **d_keys);
 int pedp_sort_keys64_run(pedp_ctx_s *c, int64_t N, int bits, int32_t *d_perm);
 
+// Row i of an N x 3 float64 array has no NaN / infinite coordinate.  Tested on the exponent bits, so that no
+// compiler assumption about NaNs (-fno-honor-nans) can fold it away.
+__host__ __device__ inline bool pedp_row_finite(const double *pts, int64_t i) {
+    uint64_t b[3];
+    memcpy(b, pts + 3 * i, sizeof(b));
+    const uint64_t e = 0x7FF0000000000000ull;
+    return (b[0] & e) != e && (b[1] & e) != e && (b[2] & e) != e;
+}
+
 #define PEDP_HIP_CHECK(expr)                                                              \
     do {                                                                                  \
         hipError_t e_ = (expr);                                                           \
@@ -188,7 +197,8 @@ struct pedp_cloud_s {
     double centroid[3] = {0, 0, 0};
     float Tn = 0.f;  // max |t'|_1
     float T2 = 0.f;  // max |t'|_2^2
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // axis-aligned bounding box of the points
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // axis-aligned bounding box of the points (finite rows)
+    int64_t n_finite = -1;  // rows without a NaN / infinite coordinate, valid with host_stats (-1: not counted, all N)
     // Built on first use in ICP: spatial order of the points (device int32[N]); as a target
     // additionally the sorted float4 operand (x', y', z', |t'|^2), padded, and one bounding
     // sphere per 16-row tile.

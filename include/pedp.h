@@ -398,8 +398,8 @@ int pedp_icp(pedp_ctx_t ctx, pedp_cloud_t source, pedp_cloud_t target,
  * pedp_icp_end waits for them and hands the result over -- the same bits as pedp_icp's.  What the host does in between
  * (enqueueing a frame's ray stage on ANOTHER context, bench.py's step) overlaps with the registration instead of waiting in
  * front of it.  Between the two calls this context must not be used for anything else (its workspace and its page-locked
- * state block belong to the pending registration): a second pedp_icp_begin, pedp_icp or pedp_icp_batched returns
- * PEDP_ERR_BAD_ARG; destroying the context or either cloud with a registration pending is an error of the caller.  want_trace:
+ * state block belong to the pending registration): a second pedp_icp_begin, pedp_icp, pedp_icp_batched(_ex), pedp_nn,
+ * pedp_icp_configure or pedp_ransac_hypotheses returns PEDP_ERR_BAD_ARG; destroying the context or either cloud with a registration pending is an error of the caller.  want_trace:
  * pedp_icp_end's `trace` may be non-null.  The reference has no counterpart (registration_icp is one blocking call,
  * src/pose_estimation.py:447-453). */
 int pedp_icp_begin(pedp_ctx_t ctx, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *params,
@@ -431,7 +431,11 @@ int pedp_icp_batched_ex(pedp_ctx_t ctx, pedp_cloud_t source, pedp_cloud_t target
 
 /* One exact nearest-neighbour pass (the correspondence step alone): for every source
  * point transformed by T, the index of the closest target point and the squared
- * distance, float64-exact (ties: lowest index).  idx/d2: host arrays, length N. */
+ * distance, float64-exact (ties: lowest index).  idx/d2: host arrays, length N.
+ * Non-finite rows (here and in every registration): a target row with a NaN or infinite
+ * coordinate is never a neighbour (the target's centroid, box and operand are made of its finite
+ * rows), and a source row with one has none (idx -1, d2 +inf; no correspondence).
+ * PEDP_ERR_BAD_ARG while a registration is pending on ctx (pedp_icp_begin). */
 int pedp_nn(pedp_ctx_t ctx, pedp_cloud_t source, pedp_cloud_t target, const double T[16],
             int32_t *idx, double *d2);
 /* Milliseconds of the last TIMED MFMA sweep kernel on this context (HIP events on the stream,

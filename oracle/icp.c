@@ -332,7 +332,7 @@ static void kd_search(const kd_t *t, int32_t ni, const double *q, double mind, d
         for (int32_t i = nd->first; i < nd->first + nd->count; ++i) {
             int32_t j = t->perm[i];
             double d = dist2(q, t->pts + 3 * (int64_t)j);
-            if (d < *best || (d == *best && j < *bi)) { *best = d; *bi = j; }
+            if (d < *best || (d == *best && d < INFINITY && j < *bi)) { *best = d; *bi = j; }
         }
         return;
     }
@@ -352,20 +352,25 @@ static void kd_search(const kd_t *t, int32_t ni, const double *q, double mind, d
     }
 }
 
+/* Only finite target rows enter the tree: a row with a NaN or infinite coordinate is never a
+ * neighbour (brute force never takes it either: its distance is NaN or inf), and inside the tree it
+ * would poison the median sort and the split values.  No finite row: an empty tree (n_nodes = 0). */
 static void kd_create(kd_t *t, const double *tgt, int64_t Nt) {
     t->nodes = (kd_node *)malloc(sizeof(kd_node) * (size_t)(2 * Nt + 2));
     t->perm = (int32_t *)malloc(sizeof(int32_t) * (size_t)(Nt > 0 ? Nt : 1));
     t->n_nodes = 0;
     t->pts = tgt;
     for (int k = 0; k < 3; ++k) { t->lo[k] = INFINITY; t->hi[k] = -INFINITY; }
+    int32_t n = 0;
     for (int64_t i = 0; i < Nt; ++i) {
-        t->perm[i] = (int32_t)i;
+        if (!(isfinite(tgt[3 * i]) && isfinite(tgt[3 * i + 1]) && isfinite(tgt[3 * i + 2]))) continue;
+        t->perm[n++] = (int32_t)i;
         for (int k = 0; k < 3; ++k) {
             if (tgt[3 * i + k] < t->lo[k]) t->lo[k] = tgt[3 * i + k];
             if (tgt[3 * i + k] > t->hi[k]) t->hi[k] = tgt[3 * i + k];
         }
     }
-    kd_build_rec(t, 0, (int32_t)Nt);
+    if (n > 0) kd_build_rec(t, 0, n);
 }
 
 static void kd_destroy(kd_t *t) {
@@ -390,7 +395,7 @@ static void kd_query_all(const kd_t *t, const double *src, int64_t Ns, int32_t *
         }
         double best = bound;
         int32_t bi = 0x7FFFFFFF;
-        if (!(mind * (1.0 - 1e-12) > best)) kd_search(t, 0, q, mind, dists, &best, &bi);
+        if (t->n_nodes > 0 && !(mind * (1.0 - 1e-12) > best)) kd_search(t, 0, q, mind, dists, &best, &bi);
         if (bi == 0x7FFFFFFF) { idx[i] = -1; d2[i] = INFINITY; }
         else { idx[i] = bi; d2[i] = best; }
     }

@@ -59,10 +59,13 @@ int pedp_oracle_raycast_bvh(const float *tri9, int64_t F, const float *rays6, in
 #define PEDP_ORACLE_P2POINT 1
 
 /* Exact nearest neighbour of every source point among tgt (brute force, f64).
- * idx[i] in [0,Nt), d2[i] = squared distance.  Ties: lowest index. */
+ * idx[i] in [0,Nt), d2[i] = squared distance.  Ties: lowest index.
+ * Non-finite rows: a target row with a NaN or infinite coordinate is never a neighbour, and a
+ * source row with one has none (idx -1, d2 +inf); in registration it has no correspondence. */
 void pedp_oracle_nn(const double *src, int64_t Ns, const double *tgt, int64_t Nt,
                     int32_t *idx, double *d2, int nthreads);
-/* Same through a KD-tree (CPU baseline in Open3D's algorithmic class). */
+/* Same through a KD-tree (CPU baseline in Open3D's algorithmic class); the same results, non-finite
+ * rows included (they are left out of the tree when it is built). */
 void pedp_oracle_nn_kdtree(const double *src, int64_t Ns, const double *tgt, int64_t Nt,
                            int32_t *idx, double *d2, int nthreads);
 

@@ -459,6 +459,31 @@ def test_begin_end_equals_the_blocking_call(ctx, oracle):
         _lib.icp_end(ctx)
 
 
+def test_pending_registration_refuses_the_calls_that_share_its_state(ctx, oracle):
+    """Between pedp_icp_begin and pedp_icp_end the context's page-locked state block and ICP workspace belong to the
+    pending registration: pedp_nn, pedp_icp_configure, pedp_ransac_hypotheses and pedp_icp_batched_ex are refused
+    (BAD_ARG) and the registration then ends with the blocking call's bits."""
+    from pedp_hip import _lib
+
+    f, scene = _frame_scene(oracle, "parity")
+    src, tgt = _lib.Cloud(ctx, scene), _lib.Cloud(ctx, f.model_points, f.normals)
+    kw = dict(max_iteration=12, relative_fitness=-1, relative_rmse=-1)
+    one = _lib.icp(ctx, src, tgt, 10.0, f.icp_init(), want_corr=True, want_trace=True, **kw)
+    _lib.icp_begin(ctx, src, tgt, 10.0, f.icp_init(), want_trace=True, **kw)
+    corr = np.zeros(src.N, np.int32)
+    for call in (lambda: _lib.nn(ctx, src, tgt, f.icp_init()),
+                 lambda: _lib.icp_configure(ctx, exhaustive=True),
+                 lambda: _lib.ransac_hypotheses(ctx, src, tgt, corr, 1, 0, 16, 0.9, 4.0, 0.6),
+                 lambda: _lib.icp_batched_ex(ctx, src, tgt, [10.0], f.icp_init()[None], max_iteration=2)):
+        with pytest.raises(_lib.PedpError, match="pending"):
+            call()
+    two = _lib.icp_end(ctx, want_corr=True)
+    assert np.array_equal(one["T"], two["T"]) and one["fitness"] == two["fitness"] and one["inlier_rmse"] == two["inlier_rmse"]
+    assert one["iters"] == two["iters"] and np.array_equal(one["corr"], two["corr"]) and np.array_equal(one["trace"], two["trace"])
+    idx, _ = _lib.nn(ctx, src, tgt, f.icp_init())   # free again
+    assert len(idx) == src.N
+
+
 _DENSE_PROBE = r"""
 import sys, numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/oracle")

@@ -89,6 +89,45 @@ def test_nn_brute_kdtree_scipy_agree(oracle):
     assert np.allclose(np.sqrt(d1), dd, rtol=1e-13)
 
 
+@pytest.mark.parametrize("geometry", ["blob", "far", "small", "clusters", "planar", "collinear", "duplicated",
+                                      "one_point", "lattice", "boundary", "nonfinite_source", "nonfinite_target"])
+def test_nn_kdtree_equals_brute_and_scipy_on_the_matrix_geometries(oracle, geometry):
+    """The KD-tree the registration oracle uses by default agrees with brute force on every geometry of the
+    device case matrix, non-finite rows included: a non-finite target row is never a neighbour, a non-finite
+    source row has none (idx -1, d2 inf).  scipy's cKDTree (built on the finite target rows) gives the same
+    distances, and the same index wherever the nearest neighbour is unique."""
+    import _nn_cases
+
+    src, tgt, _ = _nn_cases.GEOMETRIES[geometry](700, 2500, 11)
+    rng = np.random.default_rng(5)
+    tgt = tgt.copy()
+    tgt[rng.choice(len(tgt), 4, replace=False)] = [[np.nan, 0, 0], [0, np.inf, 0], [0, 0, -np.inf], [np.nan] * 3]
+    src = np.vstack([src, [[np.nan, 0, 0], [np.inf, 0, 0], [0, -np.inf, 0], [np.inf] * 3]])
+    i1, d1 = oracle.nn(src, tgt)
+    i2, d2 = oracle.nn(src, tgt, kdtree=True)
+    assert np.array_equal(i1, i2)
+    assert np.array_equal(d1.view(np.uint64), d2.view(np.uint64))
+    fin_t = np.isfinite(tgt).all(1)
+    fin_s = np.isfinite(src).all(1)
+    assert (i1[~fin_s] == -1).all() and np.isinf(d1[~fin_s]).all()
+    assert fin_t[i1[fin_s]].all()
+    keep = np.nonzero(fin_t)[0]
+    dd, ii = cKDTree(tgt[keep]).query(src[fin_s])
+    assert np.allclose(d1[fin_s], dd * dd, rtol=1e-12, atol=0)
+    ii = keep[ii]
+    other = ii != i1[fin_s]   # cKDTree breaks exact ties its own way: the brute index is then the lowest of equals
+    q = src[fin_s][other]
+    assert np.array_equal(((q - tgt[ii[other]]) ** 2).sum(1), ((q - tgt[i1[fin_s][other]]) ** 2).sum(1))
+    assert (i1[fin_s][other] < ii[other]).all()
+    # the registration oracle (KD-tree by default) takes the same correspondences as brute force
+    nrm = np.tile([0.0, 0.0, 1.0], (len(tgt), 1))
+    for est in (0, 1):
+        a = oracle.icp(src, tgt, nrm, 1.5, np.eye(4), estimator=est, max_iter=3, rel_fitness=-1, rel_rmse=-1)
+        b = oracle.icp(src, tgt, nrm, 1.5, np.eye(4), estimator=est, max_iter=3, rel_fitness=-1, rel_rmse=-1,
+                       kdtree=False)
+        assert np.array_equal(a["corr"], b["corr"]) and np.array_equal(a["trace"], b["trace"], equal_nan=True)
+
+
 def test_nn_exact_ties_pick_lowest_index(oracle):
     tgt = np.array([[1.0, 0, 0], [-1.0, 0, 0], [0, 1.0, 0], [1.0, 0, 0]])
     src = np.zeros((1, 3))
