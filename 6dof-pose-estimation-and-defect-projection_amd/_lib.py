@@ -125,6 +125,16 @@ PROTOTYPES = {
     "pedp_comm_size": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
     "pedp_comm_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "pedp_comm_allreduce_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "pedp_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_rasterize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p]),
+    "pedp_interpolate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "pedp_texture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                               C.c_int, C.c_void_p]),
+    "pedp_render_configure": (C.c_int, [C.c_void_p, C.c_int]),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
 }
@@ -279,6 +289,13 @@ class DepthEntryParams(C.Structure):
     _fields_ = [("erode_radius", C.c_int32), ("erode_diff", C.c_float), ("erode_ratio", C.c_float), ("erode_zfar", C.c_float),
                 ("bilateral_radius", C.c_int32), ("bilateral_zfar", C.c_float), ("sigmaD", C.c_float), ("sigmaR", C.c_float),
                 ("K", C.c_float * 9), ("xyz_zfar", C.c_float), ("z_min", C.c_float), ("scale", C.c_double)]
+
+
+class RenderParams(C.Structure):
+    """pedp_render_params (include/pedp.h)."""
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("proj", C.c_float * 16),
+                ("use_light", C.c_int32), ("light_mode", C.c_int32), ("light_dir", C.c_float * 3), ("light_pos", C.c_float * 3),
+                ("has_light_color", C.c_int32), ("light_color", C.c_float * 3), ("w_ambient", C.c_float), ("w_diffuse", C.c_float)]
 
 
 class ProjectOpts(C.Structure):

@@ -26,6 +26,7 @@ SOURCES = {
     "pedp_depth.hip": [],
     "pedp_cloudops.hip": [],
     "pedp_comm.hip": [],
+    "pedp_render.hip": [],
     "pedp_cluster.cpp": [],
 }
 HEADERS = ["pedp_internal.h", os.path.join("..", "..", "include", "pedp.h")]

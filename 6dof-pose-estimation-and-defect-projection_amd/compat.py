@@ -2,7 +2,9 @@
 (run.py:3, src/__init__.py:1-4), plus the `mycpp` slot (Utils.py:45-48, estimater.py:118).
 
 The hot-path names, the global registration that precedes them under
-`determine_pose(icp=True)`, and the message format to the viewer thread (`update_dash_data`); the Dash app, sensor and learned-model code stay the reference's own.
+`determine_pose(icp=True)`, the message format to the viewer thread (`update_dash_data`), and FoundationPose's
+renderer (`nvdiffrast_render`, `make_mesh_tensors` and the `dr` stand-in for `nvdiffrast.torch`); the Dash app, sensor
+and learned-model code stay the reference's own.
 """
 import numpy as np
 
@@ -38,6 +40,8 @@ def cluster_poses(angle_diff, dist_diff, poses_in, symmetry_tfs):
 
 from .depth_filters import bilateral_filter_depth, depth2xyzmap, depth2xyzmap_batch, erode_depth  # noqa: E402
 from .viewer_wire import update_dash_data  # noqa: E402  (web_vis.py:203-217: the message to the viewer thread)
+from .render import (dr, glcam_in_cvcam, make_mesh_tensors, nvdiffrast_render,  # noqa: E402  (Utils.py:18, :68-220, :752-804)
+                     projection_matrix_from_intrinsics)
 
 
 class _MyCpp:
@@ -63,4 +67,5 @@ __all__ = [
     "CorrespondenceCheckerBasedOnEdgeLength", "CorrespondenceCheckerBasedOnDistance", "CorrespondenceCheckerBasedOnNormal",
     "PointCloud", "TriangleMesh", "LineSet", "PinholeCameraIntrinsic", "RegistrationResult",
     "cluster_poses", "mycpp", "update_dash_data",
+    "nvdiffrast_render", "make_mesh_tensors", "projection_matrix_from_intrinsics", "glcam_in_cvcam", "dr",
 ]

@@ -278,6 +278,8 @@ void pedp_ctx_destroy(pedp_ctx_t c) {
     c->proj.release();
     c->ops.release();
     c->proj_out.release();
+    c->render_ws.release();
+    c->render_io.release();
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->avg_host) (void)hipHostFree(c->avg_host);
     for (int k = 0; k < 2; ++k)

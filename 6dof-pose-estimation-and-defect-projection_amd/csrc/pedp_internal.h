@@ -138,6 +138,9 @@ struct pedp_ctx_s {
     size_t avg_host_cap = 0;
     pedp_scratch ops_in;     // a large cloud's points, uploaded ahead of the workspace sizing (its box comes from the device copy)
     pedp_scratch proj, proj_out;  // fused heat-map projection: selection, rays, hit records / compacted outputs
+    pedp_scratch render_ws;  // renderer: pose records, per-pixel depth keys of one pose chunk, big-triangle list
+    pedp_scratch render_io;  // renderer: inputs and outputs of host-memory calls
+    int render_chunk = 0;    // pedp_render_configure: poses per chunk (0 = by a key budget)
     bool icp_exhaustive = false;  // pedp_icp_configure: no culling (all-pairs sweep every pass)
     int icp_timed_pass = -1;      // pedp_icp_configure: HIP events around the sweep kernel of this pass
     long long icp_last_cand = 0, icp_last_fb = 0, icp_last_passes = 0, icp_last_nt = 0, icp_last_planned = 0;

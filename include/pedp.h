@@ -505,6 +505,44 @@ int pedp_comm_size(pedp_ctx_t ctx, int *nranks, int *rank);
 int pedp_comm_allgather(pedp_ctx_t ctx, const void *send, void *recv, int64_t bytes_per_rank);
 int pedp_comm_allreduce_f64(pedp_ctx_t ctx, double *buf, int64_t n);
 
+/* ---------------------------------------------------------------- mesh renderer
+ * Replaces nvdiffrast on FoundationPose's render path (Utils.py nvdiffrast_render :133-220, callers
+ * predict_pose_refine.py:49, predict_score.py:79; the dr.rasterize / interpolate / texture calls of run.py:34 and
+ * estimater.py:100, :166).  Forward only, no antialiasing; the contract (clip space, pixel centres, coverage,
+ * visibility, rast_out, lighting) is DESIGN.md s"Renderer".  All arrays float32 / int32, row-major; every pointer is
+ * host or device memory by `mem`. */
+typedef struct pedp_render_params {
+    int H, W;              /* image size of the intrinsics (bbox2d lives in it) */
+    int out_h, out_w;      /* rendered size (output_size) */
+    float proj[16];        /* OpenGL projection, row-major (host value) */
+    int use_light;         /* colour = colour * w_ambient + diffuse * light_color * w_diffuse */
+    int light_mode;        /* 0: light_dir, 1: light_pos (per-vertex direction light_pos - xyz) */
+    float light_dir[3], light_pos[3];
+    int has_light_color;   /* 0: light_color is the colour itself */
+    float light_color[3];
+    float w_ambient, w_diffuse;
+} pedp_render_params;
+
+/* N poses (ob_in_cam, N x 16) of one mesh (verts / vnormals V x 3, faces F x 3, vcolor V x 3 in [0,1] or per-vertex
+ * uv V x 2 + texture tex_h x tex_w x 3), bbox2d N x 4 (umin, vmin, umax, vmax) or null.  Writes color N x out_h x
+ * out_w x 3, depth N x out_h x out_w, and where not null normal and xyz (N x out_h x out_w x 3), rows already flipped
+ * (output row 0 = image row 0).  F = 0 or V = 0 gives zeros. */
+int pedp_render(pedp_ctx_t ctx, const float *verts, int64_t V, const int32_t *faces, int64_t F, const float *vnormals,
+                const float *vcolor, const float *uv, const float *tex, int tex_h, int tex_w, const float *poses,
+                const float *bbox2d, int N, const pedp_render_params *prm, int mem, float *color, float *depth,
+                float *normal, float *xyz);
+/* dr.rasterize, instanced mode: pos N x V x 4 clip space -> rast N x H x W x 4 (u, v, z/w, triangle id + 1), GL row order. */
+int pedp_rasterize(pedp_ctx_t ctx, const float *pos, int N, int64_t V, const int32_t *tri, int64_t F, int H, int W, int mem,
+                   float *rast);
+/* dr.interpolate: attr V x A (attr_batched = 0) or N x V x A -> out N x H x W x A; zero where rast has no triangle. */
+int pedp_interpolate(pedp_ctx_t ctx, const float *attr, int attr_batched, int64_t V, int A, const float *rast, int N, int H,
+                     int W, const int32_t *tri, int64_t F, int mem, float *out);
+/* dr.texture, filter 'linear', boundary 'wrap': tex tex_n x th x tw x C (tex_n 1 or N), uv N x H x W x 2 -> out N x H x W x C. */
+int pedp_texture(pedp_ctx_t ctx, const float *tex, int tex_n, int th, int tw, int C, const float *uv, int N, int H, int W,
+                 int mem, float *out);
+/* Poses per chunk of the renderer's workspace (0: as many as 128 MB of per-pixel keys hold). */
+int pedp_render_configure(pedp_ctx_t ctx, int pose_chunk);
+
 /* ---------------------------------------------------------------- cluster_poses
  * Replaces mycpp.cluster_poses (mycpp/src/app/pybind_api.cpp:24-68; caller
  * estimater.py:118).  Host only.  poses: n x 16 float32 row-major, syms: s x 16.
