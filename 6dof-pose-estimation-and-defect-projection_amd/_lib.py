@@ -135,6 +135,13 @@ PROTOTYPES = {
     "pedp_texture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_void_p]),
     "pedp_render_configure": (C.c_int, [C.c_void_p, C.c_int]),
+    "pedp_warp_perspective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p]),
+    "pedp_crop_window": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_float,
+                                   C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "pedp_crop_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
 }
@@ -296,6 +303,22 @@ class RenderParams(C.Structure):
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("proj", C.c_float * 16),
                 ("use_light", C.c_int32), ("light_mode", C.c_int32), ("light_dir", C.c_float * 3), ("light_pos", C.c_float * 3),
                 ("has_light_color", C.c_int32), ("light_color", C.c_float * 3), ("w_ambient", C.c_float), ("w_diffuse", C.c_float)]
+
+
+class Image(C.Structure):
+    """pedp_image (include/pedp.h): a strided N x C x H x W uint8 / float32 image, strides in elements."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("sn", C.c_int64), ("sc", C.c_int64), ("sy", C.c_int64), ("sx", C.c_int64)]
+
+
+U8, F32 = 0, 1
+
+
+class CropParams(C.Structure):
+    """pedp_crop_params (include/pedp.h)."""
+    _fields_ = [("variant", C.c_int32), ("normalize_xyz", C.c_int32), ("use_normal", C.c_int32), ("B", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("K", C.c_float * 9),
+                ("mesh_diameter", C.c_float)]
 
 
 class ProjectOpts(C.Structure):

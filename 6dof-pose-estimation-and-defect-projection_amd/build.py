@@ -27,6 +27,7 @@ SOURCES = {
     "pedp_cloudops.hip": [],
     "pedp_comm.hip": [],
     "pedp_render.hip": [],
+    "pedp_crop.hip": [],
     "pedp_cluster.cpp": [],
 }
 HEADERS = ["pedp_internal.h", os.path.join("..", "..", "include", "pedp.h")]

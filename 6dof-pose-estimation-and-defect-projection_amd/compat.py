@@ -3,7 +3,8 @@
 
 The hot-path names, the global registration that precedes them under
 `determine_pose(icp=True)`, the message format to the viewer thread (`update_dash_data`), and FoundationPose's
-renderer (`nvdiffrast_render`, `make_mesh_tensors` and the `dr` stand-in for `nvdiffrast.torch`); the Dash app, sensor
+renderer (`nvdiffrast_render`, `make_mesh_tensors` and the `dr` stand-in for `nvdiffrast.torch`), and its crop batches
+(`make_crop_data_batch`, `make_score_crop_data_batch` and the `kornia` stand-in with `warp_perspective`); the Dash app, sensor
 and learned-model code stay the reference's own.
 """
 import numpy as np
@@ -42,6 +43,8 @@ from .depth_filters import bilateral_filter_depth, depth2xyzmap, depth2xyzmap_ba
 from .viewer_wire import update_dash_data  # noqa: E402  (web_vis.py:203-217: the message to the viewer thread)
 from .render import (dr, glcam_in_cvcam, make_mesh_tensors, nvdiffrast_render,  # noqa: E402  (Utils.py:18, :68-220, :752-804)
                      projection_matrix_from_intrinsics)
+from .crop import (BatchPoseData, compute_crop_window_tf_batch, kornia, make_crop_data_batch,  # noqa: E402,F401  (Utils.py:577-621)
+                   make_score_crop_data_batch, warp_perspective)
 
 
 class _MyCpp:
@@ -68,4 +71,6 @@ __all__ = [
     "PointCloud", "TriangleMesh", "LineSet", "PinholeCameraIntrinsic", "RegistrationResult",
     "cluster_poses", "mycpp", "update_dash_data",
     "nvdiffrast_render", "make_mesh_tensors", "projection_matrix_from_intrinsics", "glcam_in_cvcam", "dr",
+    "warp_perspective", "kornia", "compute_crop_window_tf_batch", "make_crop_data_batch", "make_score_crop_data_batch",
+    "BatchPoseData",
 ]

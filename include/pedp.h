@@ -543,6 +543,61 @@ int pedp_texture(pedp_ctx_t ctx, const float *tex, int tex_n, int th, int tw, in
 /* Poses per chunk of the renderer's workspace (0: as many as 128 MB of per-pixel keys hold). */
 int pedp_render_configure(pedp_ctx_t ctx, int pose_chunk);
 
+/* ---------------------------------------------------------------- crop batches (kornia warp_perspective)
+ * Replaces kornia.geometry.transform.warp_perspective (kornia 0.7.2) and FoundationPose's make_crop_data_batch
+ * (predict_pose_refine.py:26-88, predict_score.py:57-112, with compute_crop_window_tf_batch of Utils.py:577-621 and
+ * the datasets' transform_batch, h5_dataset.py:79-180).  The contract is DESIGN.md s4.9: per pose one float64 map from
+ * output pixel to grid_sample pixel coordinate, evaluated in float64 per pixel, cast to float32, then grid_sample's
+ * float32 bilinear (zeros padding, corners nw, ne, sw, se, no FMA) or nearest (round half to even).  A singular or
+ * non-finite M gives zeros.  Every pointer is host or device memory by `mem`. */
+enum { PEDP_U8 = 0, PEDP_F32 = 1 };
+
+/* A strided N x C x H x W image: element (n, c, y, x) at data + n*sn + c*sc + y*sy + x*sx elements of `dtype`
+ * (PEDP_U8 or PEDP_F32).  Strides are >= 0; sn = 0 is a batch expanded from one image, and H x W x C storage behind a
+ * permuted view is sc = 1, sy = W*C, sx = C. */
+typedef struct pedp_image {
+    const void *data;
+    int dtype;
+    int N, C, H, W;
+    int64_t sn, sc, sy, sx;
+} pedp_image;
+
+/* warp_perspective(src, M, (out_h, out_w), mode, 'zeros', align_corners): M B x 9 float32 (source pixel -> output
+ * pixel), src N = B or 1, mode 0 bilinear / 1 nearest.  out: B x C x out_h x out_w float32, contiguous. */
+int pedp_warp_perspective(pedp_ctx_t ctx, const pedp_image *src, const float *M, int B, int out_h, int out_w, int mode,
+                          int align_corners, int mem, float *out);
+
+/* compute_crop_window_tf_batch(method='box_3d'): poses B x 16 float32 (by `mem`), K 9 float32 host values (read during
+ * the call, whatever `mem` says), radius = float32(mesh_diameter * crop_ratio / 2), out_w x out_h the crop size.
+ * tf_to_crops B x 9 float32; bbox2d B x 4 (the crop corners (0, 0) and (corner_u, corner_v) through the float64 inverse
+ * of tf_to_crops, cast to float32) or null.  The scales are out_w * float32(1 / (right - left)), as torch computes a
+ * number divided by a tensor. */
+int pedp_crop_window(pedp_ctx_t ctx, const float *poses, int B, const float *K, float radius, int out_w, int out_h,
+                     float corner_u, float corner_v, int mem, float *tf_to_crops, float *bbox2d);
+
+typedef struct pedp_crop_params {
+    int variant;        /* 0: refiner (predict_pose_refine.py), 1: scorer (predict_score.py) */
+    int normalize_xyz;  /* cfg['normalize_xyz'] */
+    int use_normal;     /* refiner: write normalB from the normal source */
+    int B;              /* poses */
+    int H, W;           /* full frame */
+    int out_h, out_w;   /* crop (input_resize) */
+    float K[9];         /* float32 intrinsics (scorer: the back-projection of the depth round trip) */
+    float mesh_diameter;
+} pedp_crop_params;
+
+/* One fused pass over every pose: the B side (rgbB bilinear / 255; refiner xyzB nearest from `xyz` and, under
+ * use_normal, normalB nearest from `normal`; scorer depthB nearest from `depth` and xyzB through the crop -> frame ->
+ * crop round trip) and the A side (rgbA = (rgb_r * 255) / 255, xyzA from xyz_r; "/ 255" is torch's product with
+ * float32(1 / 255)), with transform_batch's xyz
+ * normalisation on both xyz maps.  Sources are one H x W frame each (their sn is ignored); rgb_r and xyz_r are the
+ * renderer's B x out_h x out_w x 3 outputs.  tf_to_crops B x 9, poses B x 16 float32.  Outputs B x C x out_h x out_w
+ * float32 (C = 3, depthB C = 1); null where the variant has none. */
+int pedp_crop_batch(pedp_ctx_t ctx, const pedp_crop_params *prm, const float *tf_to_crops, const float *poses,
+                    const pedp_image *rgb, const pedp_image *xyz, const pedp_image *normal, const pedp_image *depth,
+                    const float *rgb_r, const float *xyz_r, int mem, float *rgbA, float *rgbB, float *xyzA, float *xyzB,
+                    float *normalB, float *depthB);
+
 /* ---------------------------------------------------------------- cluster_poses
  * Replaces mycpp.cluster_poses (mycpp/src/app/pybind_api.cpp:24-68; caller
  * estimater.py:118).  Host only.  poses: n x 16 float32 row-major, syms: s x 16.
