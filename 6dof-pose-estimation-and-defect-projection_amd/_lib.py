@@ -142,6 +142,12 @@ PROTOTYPES = {
     "pedp_crop_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "pedp_crop_batch_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "pedp_pose_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "pedp_max_pair_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_double)]),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
 }
@@ -319,6 +325,16 @@ class CropParams(C.Structure):
     _fields_ = [("variant", C.c_int32), ("normalize_xyz", C.c_int32), ("use_normal", C.c_int32), ("B", C.c_int32),
                 ("H", C.c_int32), ("W", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("K", C.c_float * 9),
                 ("mesh_diameter", C.c_float)]
+
+
+class PoseUpdateParams(C.Structure):
+    """pedp_pose_update_params (include/pedp.h)."""
+    _fields_ = [("trans_rep", C.c_int32), ("rot_rep", C.c_int32), ("normalize_xyz", C.c_int32),
+                ("trans_normalizer", C.c_float * 3), ("rot_normalizer", C.c_float), ("mesh_diameter", C.c_double)]
+
+
+TRANS_TRACKNET, TRANS_RAW = 0, 1
+ROT_AXIS_ANGLE, ROT_6D = 0, 1
 
 
 class ProjectOpts(C.Structure):

@@ -28,6 +28,7 @@ SOURCES = {
     "pedp_comm.hip": [],
     "pedp_render.hip": [],
     "pedp_crop.hip": [],
+    "pedp_pose.hip": [],
     "pedp_cluster.cpp": [],
 }
 HEADERS = ["pedp_internal.h", os.path.join("..", "..", "include", "pedp.h")]

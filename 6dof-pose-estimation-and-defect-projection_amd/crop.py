@@ -236,10 +236,12 @@ def _cfg(cfg, key, default=None):
 
 
 def crop_pass(variant, tf_to_crops, poseA, K, mesh_diameter, rgb, rgb_r, xyz_r, xyz_map=None, normal_map=None, depth=None,
-              normalize_xyz=False, use_normal=False):
+              normalize_xyz=False, use_normal=False, packed=False):
     """The fused pass alone (pedp_crop_batch): every B-side map and the A-side normalisation, given the windows and the
     renderer's crop-sized maps (rgb_r, xyz_r: B x h x w x 3 CUDA tensors).  Returns a dict of B x C x h x w tensors
-    (rgbA, rgbB, xyzA, xyzB, normalB, depthB; None where the variant has none)."""
+    (rgbA, rgbB, xyzA, xyzB, normalB, depthB; None where the variant has none).  With `packed` (pedp_crop_batch_packed)
+    the dict also holds the networks' inputs A = cat([rgbA, xyzA], 1) and B = cat([rgbB, xyzB], 1), B x 6 x h x w, and
+    rgbA ... xyzB are views of them."""
     import torch
 
     scorer = variant == 1
@@ -282,13 +284,23 @@ def crop_pass(variant, tf_to_crops, poseA, K, mesh_diameter, rgb, rgb_r, xyz_r, 
     prm.H, prm.W, prm.out_h, prm.out_w = H, W, oh, ow
     prm.K[:] = Kf.tolist()
     prm.mesh_diameter = float(np.float32(mesh_diameter))
-    out = {k: torch.empty((B, 3, oh, ow), dtype=torch.float32, device=dev) for k in ("rgbA", "rgbB", "xyzA", "xyzB")}
+    if packed:
+        out = {k: torch.empty((B, 6, oh, ow), dtype=torch.float32, device=dev) for k in ("A", "B")}
+        for side in "AB":
+            out["rgb" + side], out["xyz" + side] = out[side][:, :3], out[side][:, 3:]
+    else:
+        out = {k: torch.empty((B, 3, oh, ow), dtype=torch.float32, device=dev) for k in ("rgbA", "rgbB", "xyzA", "xyzB")}
     out["normalB"] = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=dev) if use_normal else None
     out["depthB"] = torch.empty((B, 1, oh, ow), dtype=torch.float32, device=dev) if scorer else None
 
     def img(k):
         return C.byref(srcs[k]) if k in srcs else None
 
+    if packed:
+        _launch(dev, "pedp_crop_batch_packed", lambda lib, hd, mem: lib.pedp_crop_batch_packed(
+            hd, C.byref(prm), _ptr(tf), _ptr(poseA), img("rgb"), img("xyz"), img("normal"), img("depth"), _ptr(rgb_r),
+            _ptr(xyz_r), mem, _ptr(out["A"]), _ptr(out["B"]), _ptr(out["normalB"]), _ptr(out["depthB"])))
+        return out
     _launch(dev, "pedp_crop_batch", lambda lib, hd, mem: lib.pedp_crop_batch(
         hd, C.byref(prm), _ptr(tf), _ptr(poseA), img("rgb"), img("xyz"), img("normal"), img("depth"), _ptr(rgb_r),
         _ptr(xyz_r), mem, _ptr(out["rgbA"]), _ptr(out["rgbB"]), _ptr(out["xyzA"]), _ptr(out["xyzB"]), _ptr(out["normalB"]),
@@ -297,7 +309,9 @@ def crop_pass(variant, tf_to_crops, poseA, K, mesh_diameter, rgb, rgb_r, xyz_r, 
 
 
 def _crop_batch(variant, render_size, ob_in_cams, mesh, rgb, depth, K, crop_ratio, xyz_map, normal_map, mesh_diameter, cfg,
-                glctx, mesh_tensors, dataset, batch_cls):
+                glctx, mesh_tensors, dataset, batch_cls, packed=False):
+    """The crop batch of either predictor; with `packed` the returned batch also carries the networks' inputs as `A` and
+    `B` (B x 6 x h x w), of which rgbAs ... xyz_mapBs are views."""
     import torch
 
     if cfg is None or mesh_diameter is None:
@@ -327,7 +341,7 @@ def _crop_batch(variant, render_size, ob_in_cams, mesh, rgb, depth, K, crop_rati
 
     scorer = variant == 1
     outs = crop_pass(variant, tf_to_crops, poseA, Kf, mesh_diameter, rgb, rgb_r, xyz_r, xyz_map=xyz_map, normal_map=normal_map,
-                     depth=depth if scorer else None, normalize_xyz=normalize, use_normal=use_normal)
+                     depth=depth if scorer else None, normalize_xyz=normalize, use_normal=use_normal, packed=packed)
     rgbA, rgbB, xyzA, xyzB, normalB, depthB = (outs[k] for k in ("rgbA", "rgbB", "xyzA", "xyzB", "normalB", "depthB"))
     normalA = None
     if use_normal and not scorer:  # the reference warps the crop-sized render like a full frame (predict_pose_refine.py:74)
@@ -337,9 +351,12 @@ def _crop_batch(variant, render_size, ob_in_cams, mesh, rgb, depth, K, crop_rati
     if scorer:
         Ks = Ks.expand(B, 3, 3)
     cls = batch_cls or BatchPoseData
-    return cls(rgbAs=rgbA, rgbBs=rgbB, depthAs=depth_r.reshape(B, 1, oh, ow) if scorer else None, depthBs=depthB,
-               normalAs=normalA, normalBs=normalB, poseA=poseA, xyz_mapAs=xyzA, xyz_mapBs=xyzB, tf_to_crops=tf_to_crops,
-               Ks=Ks, mesh_diameters=mesh_diameters)
+    batch = cls(rgbAs=rgbA, rgbBs=rgbB, depthAs=depth_r.reshape(B, 1, oh, ow) if scorer else None, depthBs=depthB,
+                normalAs=normalA, normalBs=normalB, poseA=poseA, xyz_mapAs=xyzA, xyz_mapBs=xyzB, tf_to_crops=tf_to_crops,
+                Ks=Ks, mesh_diameters=mesh_diameters)
+    if packed:
+        batch.A, batch.B = outs["A"], outs["B"]
+    return batch
 
 
 def make_crop_data_batch(render_size, ob_in_cams, mesh, rgb, depth, K, crop_ratio, xyz_map, normal_map=None,

@@ -266,6 +266,7 @@ struct CropArgs {
     Img rgb, xyz, normal, depth;
     const float *rgb_r, *xyz_r;
     float *rgbA, *rgbB, *xyzA, *xyzB, *normalB, *depthB;
+    size_t pstride;    // floats from one pose's rgbA / rgbB / xyzA / xyzB plane to the next: 3 h w, packed 6 h w
     float K[9];
     float inv_r;       // 1 / (float32(diameter) / 2)
     float z_invalid;   // refiner 0.001, scorer 0.1
@@ -299,7 +300,8 @@ __global__ __launch_bounds__(CB) void crop_kernel(CropArgs a, const CropPose *__
     const int b = b0 + blockIdx.y;
     const CropPose &cp = poses[b];
     const int y = q / a.ow, x = q - y * a.ow;
-    const size_t p3 = (size_t)b * 3 * hw + q;
+    const size_t p3 = (size_t)b * a.pstride + q;   // rgbA / rgbB / xyzA / xyzB
+    const size_t n3 = (size_t)b * 3 * hw + q;       // normalB
 
     // B side: one coordinate for every map
     float ix = 0.f, iy = 0.f;
@@ -320,7 +322,7 @@ __global__ __launch_bounds__(CB) void crop_kernel(CropArgs a, const CropPose *__
         }
         if (a.use_normal) {
             const int64_t off = (int64_t)yo * a.normal.sy + (int64_t)xo * a.normal.sx;
-            for (int c = 0; c < 3; ++c) a.normalB[p3 + (size_t)c * hw] = in ? load(a.normal, off + c * a.normal.sc) : 0.f;
+            for (int c = 0; c < 3; ++c) a.normalB[n3 + (size_t)c * hw] = in ? load(a.normal, off + c * a.normal.sc) : 0.f;
         }
     } else {
         a.depthB[(size_t)b * hw + q] = in ? load(a.depth, (int64_t)yo * a.depth.sy + (int64_t)xo * a.depth.sx) : 0.f;
@@ -472,11 +474,16 @@ int pedp_crop_window(pedp_ctx_t c, const float *poses, int B, const float *K, fl
     return PEDP_OK;
 }
 
-int pedp_crop_batch(pedp_ctx_t c, const pedp_crop_params *prm, const float *tf_to_crops, const float *poses, const pedp_image *rgb,
-                    const pedp_image *xyz, const pedp_image *normal, const pedp_image *depth, const float *rgb_r,
-                    const float *xyz_r, int mem, float *rgbA, float *rgbB, float *xyzA, float *xyzB, float *normalB,
-                    float *depthB) {
-    const char *who = "pedp_crop_batch";
+}  // extern "C"
+
+namespace {
+
+// pedp_crop_batch and, with `packed`, pedp_crop_batch_packed: rgbA / rgbB are then the A / B buffers (B x 6 x h x w) and
+// xyzA / xyzB are ignored (the planes at channel 3 of each).
+int crop_batch(pedp_ctx_t c, const char *who, bool packed, const pedp_crop_params *prm, const float *tf_to_crops,
+               const float *poses, const pedp_image *rgb, const pedp_image *xyz, const pedp_image *normal,
+               const pedp_image *depth, const float *rgb_r, const float *xyz_r, int mem, float *rgbA, float *rgbB, float *xyzA,
+               float *xyzB, float *normalB, float *depthB) {
     PEDP_REQUIRE(c && prm, "%s: null context or parameters", who);
     PEDP_REQUIRE(mem == PEDP_HOST || mem == PEDP_DEVICE, "%s: bad mem flag %d", who, mem);
     PEDP_REQUIRE(prm->variant == 0 || prm->variant == 1, "%s: variant %d (0 refiner, 1 scorer)", who, prm->variant);
@@ -499,7 +506,7 @@ int pedp_crop_batch(pedp_ctx_t c, const pedp_crop_params *prm, const float *tf_t
         PEDP_REQUIRE(!use_normal || (normal->C == 3 && normal->H == H && normal->W == W), "%s: normal map must be %d x %d x 3",
                      who, H, W);
     }
-    PEDP_REQUIRE(tf_to_crops && poses && rgb_r && xyz_r && rgbA && rgbB && xyzA && xyzB, "%s: null array", who);
+    PEDP_REQUIRE(tf_to_crops && poses && rgb_r && xyz_r && rgbA && rgbB && (packed || (xyzA && xyzB)), "%s: null array", who);
     PEDP_REQUIRE(scorer ? depthB != nullptr : (!use_normal || normalB != nullptr), "%s: null output", who);
     PEDP_HIP_CHECK(hipSetDevice(c->device));
     const pedp_image *srcs[4] = {rgb, scorer ? nullptr : xyz, use_normal ? normal : nullptr, scorer ? depth : nullptr};
@@ -526,10 +533,19 @@ int pedp_crop_batch(pedp_ctx_t c, const pedp_crop_params *prm, const float *tf_t
     const float *d_poses = (const float *)sg.in(poses, 64 * (size_t)B);
     a.rgb_r = (const float *)sg.in(rgb_r, 4 * n3);
     a.xyz_r = (const float *)sg.in(xyz_r, 4 * n3);
-    a.rgbA = sg.out(rgbA, n3);
-    a.rgbB = sg.out(rgbB, n3);
-    a.xyzA = sg.out(xyzA, n3);
-    a.xyzB = sg.out(xyzB, n3);
+    if (packed) {
+        a.rgbA = sg.out(rgbA, 2 * n3);
+        a.rgbB = sg.out(rgbB, 2 * n3);
+        a.xyzA = a.rgbA + 3 * hw;
+        a.xyzB = a.rgbB + 3 * hw;
+        a.pstride = 6 * hw;
+    } else {
+        a.rgbA = sg.out(rgbA, n3);
+        a.rgbB = sg.out(rgbB, n3);
+        a.xyzA = sg.out(xyzA, n3);
+        a.xyzB = sg.out(xyzB, n3);
+        a.pstride = 3 * hw;
+    }
     a.normalB = use_normal ? sg.out(normalB, n3) : nullptr;
     a.depthB = scorer ? sg.out(depthB, (size_t)B * hw) : nullptr;
     if (sg.rc) return sg.rc;
@@ -552,13 +568,34 @@ int pedp_crop_batch(pedp_ctx_t c, const pedp_crop_params *prm, const float *tf_t
         PEDP_HIP_CHECK(hipGetLastError());
     }
     if (mem == PEDP_HOST) {
-        float *outs[6] = {rgbA, rgbB, xyzA, xyzB, a.normalB ? normalB : nullptr, a.depthB ? depthB : nullptr};
+        const size_t nab = packed ? 2 * n3 : n3;
+        float *outs[6] = {rgbA, rgbB, packed ? nullptr : xyzA, packed ? nullptr : xyzB, a.normalB ? normalB : nullptr,
+                          a.depthB ? depthB : nullptr};
         const float *devs[6] = {a.rgbA, a.rgbB, a.xyzA, a.xyzB, a.normalB, a.depthB};
-        const size_t cnt[6] = {n3, n3, n3, n3, n3, (size_t)B * hw};
+        const size_t cnt[6] = {nab, nab, n3, n3, n3, (size_t)B * hw};
         for (int k = 0; k < 6 && !rc; ++k)
             if (outs[k]) rc = pedp_download(c, outs[k], devs[k], sizeof(float) * cnt[k]);
     }
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pedp_crop_batch(pedp_ctx_t c, const pedp_crop_params *prm, const float *tf_to_crops, const float *poses, const pedp_image *rgb,
+                    const pedp_image *xyz, const pedp_image *normal, const pedp_image *depth, const float *rgb_r,
+                    const float *xyz_r, int mem, float *rgbA, float *rgbB, float *xyzA, float *xyzB, float *normalB,
+                    float *depthB) {
+    return crop_batch(c, "pedp_crop_batch", false, prm, tf_to_crops, poses, rgb, xyz, normal, depth, rgb_r, xyz_r, mem, rgbA,
+                      rgbB, xyzA, xyzB, normalB, depthB);
+}
+
+int pedp_crop_batch_packed(pedp_ctx_t c, const pedp_crop_params *prm, const float *tf_to_crops, const float *poses,
+                           const pedp_image *rgb, const pedp_image *xyz, const pedp_image *normal, const pedp_image *depth,
+                           const float *rgb_r, const float *xyz_r, int mem, float *A, float *B, float *normalB, float *depthB) {
+    return crop_batch(c, "pedp_crop_batch_packed", true, prm, tf_to_crops, poses, rgb, xyz, normal, depth, rgb_r, xyz_r, mem, A,
+                      B, nullptr, nullptr, normalB, depthB);
 }
 
 }  // extern "C"

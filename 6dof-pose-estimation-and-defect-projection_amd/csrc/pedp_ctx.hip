@@ -282,6 +282,8 @@ void pedp_ctx_destroy(pedp_ctx_t c) {
     c->render_io.release();
     c->crop_ws.release();
     c->crop_io.release();
+    c->pose_ws.release();
+    c->pose_io.release();
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->avg_host) (void)hipHostFree(c->avg_host);
     for (int k = 0; k < 2; ++k)

@@ -598,6 +598,44 @@ int pedp_crop_batch(pedp_ctx_t ctx, const pedp_crop_params *prm, const float *tf
                     const float *rgb_r, const float *xyz_r, int mem, float *rgbA, float *rgbB, float *xyzA, float *xyzB,
                     float *normalB, float *depthB);
 
+/* The crop batch with the network's inputs packed: predict_pose_refine.py:187-188 and predict_score.py:188-189 build
+ * A = torch.cat([rgbAs, xyz_mapAs], 1) and B = torch.cat([rgbBs, xyz_mapBs], 1) from pedp_crop_batch's outputs.  Same
+ * arguments and values as pedp_crop_batch, but the A side goes into one B x 6 x out_h x out_w float32 buffer (channels
+ * rgbA 0-2, xyzA 3-5) and the B side into another (rgbB, xyzB); normalB and depthB as pedp_crop_batch. */
+int pedp_crop_batch_packed(pedp_ctx_t ctx, const pedp_crop_params *prm, const float *tf_to_crops, const float *poses,
+                           const pedp_image *rgb, const pedp_image *xyz, const pedp_image *normal, const pedp_image *depth,
+                           const float *rgb_r, const float *xyz_r, int mem, float *A, float *B, float *normalB, float *depthB);
+
+/* ---------------------------------------------------------------- pose arithmetic (pytorch3d, compute_mesh_diameter)
+ * The contract is DESIGN.md s4.10: float32 with no contraction, every sum in the order written, tanh / sin / cos in
+ * float64 rounded once to float32.  The rotations restate pytorch3d 0.7's so3_exp_map and rotation_6d_to_matrix (parity
+ * with pytorch3d unpinned: it is not installed where this library runs). */
+enum { PEDP_TRANS_TRACKNET = 0, PEDP_TRANS_RAW = 1 };
+enum { PEDP_ROT_AXIS_ANGLE = 0, PEDP_ROT_6D = 1 };
+
+typedef struct pedp_pose_update_params {
+    int trans_rep;              /* cfg['trans_rep']: PEDP_TRANS_TRACKNET or PEDP_TRANS_RAW (deepim is not supported) */
+    int rot_rep;                /* cfg['rot_rep']: PEDP_ROT_AXIS_ANGLE or PEDP_ROT_6D */
+    int normalize_xyz;          /* cfg['normalize_xyz'] */
+    float trans_normalizer[3];  /* float32(cfg['trans_normalizer']), one value repeated or three */
+    float rot_normalizer;       /* float32(cfg['rot_normalizer']) */
+    double mesh_diameter;       /* under normalize_xyz the translation is multiplied by float32(mesh_diameter / 2) */
+} pedp_pose_update_params;
+
+/* Replaces predict_pose_refine.py:195-231 (the tanh scaling, pytorch3d's so3_exp_map(...).permute(0, 2, 1) or
+ * rotation_6d_to_matrix(...).permute(0, 2, 1), the diameter scale) and egocentric_delta_pose_to_pose (Utils.py:848-855),
+ * one lane per pose.  trans B x 3, rot B x 3 (axis-angle) or B x 6 (6d), poseA B x 16 float32 -> poses B x 16 (may be
+ * poseA itself); trans_delta B x 3 and rot_mat_delta B x 9 (the predictor's last_trans_update / last_rot_update) or null.
+ * Every pointer is host or device memory by `mem`. */
+int pedp_pose_update(pedp_ctx_t ctx, const pedp_pose_update_params *prm, int B, const float *trans, const float *rot,
+                     const float *poseA, int mem, float *poses, float *trans_delta, float *rot_mat_delta);
+
+/* Replaces compute_mesh_diameter's `np.linalg.norm(pts[None] - pts[:, None], axis=-1).max()` (Utils.py:559-574): pts
+ * n x 3 float64 (host or device by `mem`) -> *out = sqrt(max over i, j of (dx^2 + dy^2) + dz^2), bit for bit numpy's
+ * value; NaN if any coordinate is not finite (numpy's diagonal inf - inf), 0 for n = 1; n = 0 is an error.  *out is host
+ * memory; the call returns once it is written. */
+int pedp_max_pair_distance(pedp_ctx_t ctx, const double *pts, int64_t n, int mem, double *out);
+
 /* ---------------------------------------------------------------- cluster_poses
  * Replaces mycpp.cluster_poses (mycpp/src/app/pybind_api.cpp:24-68; caller
  * estimater.py:118).  Host only.  poses: n x 16 float32 row-major, syms: s x 16.
