@@ -368,8 +368,9 @@ __global__ void __launch_bounds__(RB) interpolate_kernel(const float *attr, int 
     float *o = out + p * A;
     int32_t idx[3] = {-1, -1, -1};
     if (r.w >= 1.0f && r.w <= (float)F) {
-        const int64_t t = (int64_t)r.w - 1;
-        for (int k = 0; k < 3; ++k) idx[k] = tri[3 * t + k];
+        const int64_t t = (int64_t)r.w - 1;  // (float)F rounds above F for some F > 2^24: t == F must not be read
+        if (t < F)
+            for (int k = 0; k < 3; ++k) idx[k] = tri[3 * t + k];
     }
     if (idx[0] < 0 || idx[1] < 0 || idx[2] < 0 || idx[0] >= V || idx[1] >= V || idx[2] >= V) {
         for (int a = 0; a < A; ++a) o[a] = 0.f;

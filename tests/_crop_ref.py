@@ -127,7 +127,7 @@ def crop_window(poses, K, radius, out_w, out_h, corner=None):
     z0 = f32(0)
     offs = [(z0, z0), (r, z0), (-r, z0), (z0, r), (z0, -r)]
     uv = []
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         for ox, oy in offs:
             X, Y, Z = t[:, 0] + ox, t[:, 1] + oy, t[:, 2] + z0
             u = (K[0] * X + K[1] * Y) + K[2] * Z

@@ -131,19 +131,21 @@ def _lerp(u, v, t, a0, a1, a2):
 
 
 def interpolate(attr, rast, faces):
-    """attr V x A or N x V x A -> N x H x W x A."""
+    """attr V x A or N x V x A -> N x H x W x A.  Zero where the id is not in [1, F] (NaN included; a fractional id
+    truncates) and where the triangle names a vertex outside [0, V)."""
     rast = np.asarray(rast, f32)
     N, H, W, _ = rast.shape
     attr = np.asarray(attr, f32)
-    A = attr.shape[-1]
+    V, A = attr.shape[-2], attr.shape[-1]
     out = np.zeros((N, H, W, A), f32)
-    faces = np.asarray(faces, np.int64)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
     for n in range(N):
         a = attr[n] if attr.ndim == 3 else attr
         r = rast[n].reshape(-1, 4)
-        hit = (r[:, 3] >= 1) & (r[:, 3] <= len(faces))
-        t = r[hit, 3].astype(np.int64) - 1
-        i = faces[t]
+        hit = np.nonzero((r[:, 3] >= 1) & (r[:, 3] <= len(faces)))[0]
+        i = faces[r[hit, 3].astype(np.int64) - 1]
+        good = np.all((i >= 0) & (i < V), axis=1)
+        hit, i = hit[good], i[good]
         u, v = r[hit, 0][:, None], r[hit, 1][:, None]
         out[n].reshape(-1, A)[hit] = _lerp(u, v, (ONE - u) - v, a[i[:, 0]], a[i[:, 1]], a[i[:, 2]])
     return out

@@ -389,3 +389,123 @@ def test_bad_shapes_raise(scene):
     with pytest.raises(_lib.PedpError):
         make_crop_data_batch((CROP, CROP), P, None, rgb, depth, K_, 1.4, xyz[:100], mesh_diameter=diameter, cfg=cfg,
                              mesh_tensors=mt)
+
+
+# ---------------------------------------------------------------- degenerate hypotheses
+
+def _assert_bits_nan(got, want, what):
+    """Bit equality where both are numbers; a NaN where the other is a NaN (of any payload)."""
+    g, w = _bits(got), _bits(want)
+    assert g.shape == w.shape, f"{what}: shape {g.shape} != {w.shape}"
+    gn, wn = np.isnan(g.view(np.float32)), np.isnan(w.view(np.float32))
+    assert np.array_equal(gn, wn), f"{what}: NaN at {int((gn != wn).sum())} differing places"
+    bad = (g != w) & ~gn
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} values differ"
+
+
+# kind -> the translation it gets (the rotation stays the hypothesis')
+DEGENERATE = {
+    "z_zero": [0.01, -0.01, 0.0],
+    "z_negative": [0.01, -0.01, -0.3],
+    "z_tiny": [0.01, -0.01, 1e-30],
+    "x_nan": [np.nan, -0.01, 0.5],
+    "x_inf": [np.inf, -0.01, 0.5],
+    "x_minus_inf": [-np.inf, -0.01, 0.5],
+    "z_nan": [0.01, -0.01, np.nan],
+    "x_overflow": [1e37, -0.01, 0.5],                         # u overflows to inf, v stays finite: the radius is NaN
+    "off_frame": [50 * W_ * 0.5 / K_[0, 0], -0.01, 0.5],      # the centre 50 frame widths right of the image
+    "sub_pixel": [0.3, 0.3, 1e4],                              # radius << 0.5 px: right == left after rounding
+}
+# the crop window is not finite: tf_to_crops holds NaN, the maps are "singular" and the render's bbox2d is NaN
+NONFINITE = ("z_zero", "x_nan", "x_inf", "x_minus_inf", "z_nan", "x_overflow", "sub_pixel")
+
+
+def _mixed_batch(T):
+    poses = _hypotheses(64, T, seed=21)
+    slots = {k: 3 + 6 * i for i, k in enumerate(DEGENERATE)}
+    for k, s in slots.items():
+        poses[s, :3, 3] = DEGENERATE[k]
+    return poses, slots
+
+
+def test_degenerate_crop_windows(scene):
+    from pedp_hip.compat import compute_crop_window_tf_batch
+    from pedp_hip.crop import _crop_window
+
+    mt, diameter, rgb, depth, xyz, normal, T = scene
+    poses, slots = _mixed_batch(T)
+    r = diameter * 1.4 / 2
+    tf_r, bb_r = ref.crop_window(poses, K_, np.float32(r), CROP, CROP, (CROP - 1, CROP - 1))
+    for k in NONFINITE:
+        assert np.isnan(tf_r[slots[k]]).any() and np.isnan(bb_r[slots[k]]).all(), k
+    # torch.max's NaN: without it the finite v extent would give x_overflow a finite second row
+    assert np.isnan(tf_r[slots["x_overflow"], 1]).all()
+    for k in ("z_negative", "z_tiny", "off_frame"):
+        assert np.isfinite(tf_r[slots[k]]).all(), k
+    pt = torch.as_tensor(poses, device="cuda")
+    tf, bb = _crop_window(pt, K_, r, CROP, CROP, (CROP - 1, CROP - 1), True)
+    _assert_bits_nan(tf, tf_r, "tf_to_crops")
+    _assert_bits_nan(bb, bb_r, "bbox2d")
+    tf2 = compute_crop_window_tf_batch(poses=pt, K=K_, crop_ratio=1.4, out_size=(CROP, CROP), method="box_3d", mesh_diameter=diameter)
+    _assert_bits_nan(tf2, tf_r, "compute_crop_window_tf_batch")
+    tfh, bbh = _crop_window(poses, K_, r, CROP, CROP, (CROP - 1, CROP - 1), True)
+    _assert_bits_nan(tfh, tf_r, "tf_to_crops (host)")
+    _assert_bits_nan(bbh, bb_r, "bbox2d (host)")
+    # every window under half a pixel: mesh_diameter is one number per batch, so a call of its own
+    healthy = np.delete(poses, list(slots.values()), 0)
+    tiny = 1e-4
+    tf_r, bb_r = ref.crop_window(healthy, K_, np.float32(tiny * 1.4 / 2), CROP, CROP, (CROP - 1, CROP - 1))
+    assert np.isnan(tf_r).any((1, 2)).mean() > 0.5, "too few windows collapsed to right == left"
+    tf, bb = _crop_window(torch.as_tensor(healthy, device="cuda"), K_, tiny * 1.4 / 2, CROP, CROP, (CROP - 1, CROP - 1), True)
+    _assert_bits_nan(tf, tf_r, "sub-pixel tf_to_crops")
+    _assert_bits_nan(bb, bb_r, "sub-pixel bbox2d")
+    tf2 = compute_crop_window_tf_batch(poses=torch.as_tensor(healthy, device="cuda"), K=K_, crop_ratio=1.4, out_size=(CROP, CROP),
+                                       method="box_3d", mesh_diameter=tiny)
+    _assert_bits_nan(tf2, tf_r, "sub-pixel compute_crop_window_tf_batch")
+
+
+def _field(batch, k):
+    v = getattr(batch, k) if not isinstance(batch, dict) else batch.get(k)
+    return None if v is None else v.detach().cpu().numpy()
+
+
+def _contract_of_degenerate(got, slots, poses, variant, normalize, use_normal):
+    """What the contract gives each kind.  transform_batch of an empty pixel (xyz 0) fails the z test: 0 under
+    normalize_xyz, else 0 - t per channel."""
+    empty_xyz = {k: (np.zeros((3, CROP, CROP), np.float32) if normalize else
+                     np.broadcast_to((np.float32(0) - poses[s, :3, 3])[:, None, None], (3, CROP, CROP)))
+                 for k, s in slots.items()}
+    a_side = ["rgbAs"] + (["normalAs"] if use_normal else []) + (["depthAs"] if variant == 1 else [])
+    b_side = ["rgbBs"] + (["normalBs"] if use_normal else []) + (["depthBs"] if variant == 1 else [])
+    for k, s in slots.items():
+        empty_a = k in NONFINITE or k == "z_negative"   # no window, or the mesh behind the camera: nothing rendered
+        empty_b = k in NONFINITE or k in ("z_tiny", "off_frame")  # no window, or a window that samples off the frame
+        for f in (a_side if empty_a else []) + (b_side if empty_b else []):
+            assert not _field(got, f)[s].any(), f"{k}: {f} not all zero"
+        if empty_a:
+            _assert_bits_nan(_field(got, "xyz_mapAs")[s], empty_xyz[k], f"{k}: xyz_mapAs")
+        if empty_b:
+            _assert_bits_nan(_field(got, "xyz_mapBs")[s], empty_xyz[k], f"{k}: xyz_mapBs")
+    s = slots["off_frame"]
+    assert _field(got, "rgbAs")[s].any(), "off_frame: the render inside its own window is empty"
+    s = slots["z_negative"]
+    assert _field(got, "rgbBs")[s].any(), "z_negative: the mirrored window samples nothing"
+
+
+@pytest.mark.parametrize("variant,normalize,use_normal", [(0, True, True), (0, False, True), (1, True, False), (1, False, False)])
+def test_degenerate_hypotheses_through_the_crop_batch(scene, variant, normalize, use_normal):
+    poses, slots = _mixed_batch(scene[-1])
+    got = _fused(variant, poses, scene, normalize, use_normal)
+    want = _unfused(variant, poses, scene, normalize, use_normal)
+    for k, v in want.items():
+        _assert_bits_nan(getattr(got, k), v, k)
+    _contract_of_degenerate(got, slots, poses, variant, normalize, use_normal)
+    # no cross-talk: the healthy hypotheses equal a batch of only them
+    healthy = np.setdiff1d(np.arange(len(poses)), list(slots.values()))
+    alone = _fused(variant, poses[healthy], scene, normalize, use_normal)
+    for k in ("rgbAs", "rgbBs", "xyz_mapAs", "xyz_mapBs", "normalAs", "normalBs", "depthAs", "depthBs", "tf_to_crops"):
+        a, b = _field(got, k), _field(alone, k)
+        assert (a is None) == (b is None), k
+        if a is not None:
+            _assert_bits(a[healthy], b, f"{k}, healthy hypotheses alone")
+            assert np.isfinite(b).all(), f"{k}: a healthy hypothesis has a non-finite value"

@@ -206,3 +206,87 @@ def test_dr_shim_refuses_what_it_does_not_support():
 
     for name in ("nvdiffrast_render", "make_mesh_tensors", "projection_matrix_from_intrinsics", "glcam_in_cvcam", "dr"):
         assert name in compat.__all__
+
+
+# ---------------------------------------------------------------- float64 geometry (CPU twin of test_render_geometry_gpu.py)
+
+def _geometry_render(verts, faces, poses, K, H, W, out_h, out_w, bbox=None, textured=False, seed=0):
+    """ref.render of an analytic scene: colours (or uv into a ramp texture) and normals affine in the model position."""
+    import _render_geometry as geo
+    from pedp_hip.render import projection_matrix_from_intrinsics
+
+    cf, nf = geo.affine_field(verts, 0.05, 0.95, seed), geo.normal_field(verts, seed + 1)
+    kw, uvf = {"vcolor": geo.vertex_values(verts, cf)}, None
+    if textured:
+        th, tw = 48, 64
+        uvf = geo.affine_field(verts, [1.0 / tw, 1.0 / th], [1 - 1.0 / tw, 1 - 1.0 / th], seed + 2, dims=2)
+        kw = {"tex": geo.ramp_texture(th, tw), "uv": geo.vertex_values(verts, uvf)}
+    proj = projection_matrix_from_intrinsics(K, H, W, 0.001, 100).astype(np.float32)
+    out = ref.render(verts, faces, geo.vertex_values(verts, nf), poses, proj, H, W, out_h, out_w, bbox=bbox, get_normal=True, **kw)
+    return out, cf, nf, uvf
+
+
+@pytest.mark.parametrize("textured,crop", [(False, False), (True, False), (False, True)])
+def test_restatement_meets_the_geometry_of_a_grazing_quad(textured, crop):
+    """The checks of test_render_geometry_gpu.py against the restatement: perspective-correct attributes on the rays
+    through the pixel centres, the covered set of the float64 ray test, and a scene in which the wrong conventions
+    miss by far."""
+    import _render_geometry as geo
+
+    H, W = 480, 640
+    v, f = geo.grazing_quad()
+    poses = geo.quad_poses(3, seed=1)
+    bbox, oh, ow = None, H, W
+    if crop:  # windows around the middle of the quad, wider than tall, at a smaller output size
+        bbox = np.array([[200.0, 230.0, 440.0, 400.0], [150.5, 180.25, 500.0, 470.0], [300.0, 160.0, 340.0, 200.0]], np.float32)
+        oh, ow = 60, 72
+    (color, depth, normal, xyz), cf, nf, uvf = _geometry_render(v, f, poses, geo.K_FRAME, H, W, oh, ow, bbox, textured)
+    stats = [geo.check_pose((color[n], depth[n], normal[n], xyz[n]), poses[n], geo.K_FRAME, v, f, cf, nf, uvf, 0.3 if textured else None,
+                            None if bbox is None else bbox[n], quad=True) for n in range(len(poses))]
+    s = geo.summarize(stats)
+    print(s)
+    assert s["covered"] > (2000 if crop else 50000)
+
+
+def test_restatement_meets_the_geometry_of_a_torus():
+    import _render_geometry as geo
+    from pedp_hip import synth
+
+    v, t, _ = synth.bumpy_torus(40, 30)
+    v = (v * 0.001).astype(np.float32)
+    H, W = 48, 64
+    K = np.array([[70.0, 0, 31.2], [0, 66.0, 24.4], [0, 0, 1]])
+    rng = np.random.default_rng(4)
+    poses = np.empty((3, 4, 4), np.float32)
+    for i in range(3):
+        T = np.eye(4)
+        T[:3, :3] = synth.axis_angle(rng.normal(size=3), rng.uniform(0, np.pi))
+        T[:3, 3] = [rng.uniform(-0.02, 0.02), rng.uniform(-0.02, 0.02), 0.35]
+        poses[i] = T
+    bbox = np.array([[10.0, 8.0, 50.0, 44.0], [5.5, 2.25, 60.0, 40.0], [20.0, 10.0, 44.0, 34.0]], np.float32)
+    for bb, (oh, ow) in ((None, (H, W)), (bbox, (32, 32))):
+        (color, depth, normal, xyz), cf, nf, _ = _geometry_render(v, t, poses, K, H, W, oh, ow, bb)
+        stats = [geo.check_pose((color[n], depth[n], normal[n], xyz[n]), poses[n], K, v, t, cf, nf, bbox=None if bb is None else bb[n])
+                 for n in range(3)]
+        s = geo.summarize(stats)
+        assert s["covered"] > 100, s
+
+
+def test_interpolate_restatement_zero_rule():
+    """The kernel's rule: a pixel is zero where its id is not in [1, F] (NaN included) or its triangle names a vertex
+    outside [0, V); a fractional id truncates; NaN barycentrics with a valid id propagate."""
+    attr = np.array([[1.0, 10.0], [2.0, 20.0], [4.0, 40.0], [8.0, 80.0]], f32)
+    tri = np.array([[0, 1, 2], [1, 2, 3], [-1, 1, 2], [0, 4, 2], [3, 2, -4]], np.int32)
+    ids = [1.0, 2.0, 2.9, 3.0, 4.0, 5.0, 0.0, 6.0, -1.0, np.nan, 5.5]
+    rast = np.zeros((1, 1, len(ids) + 1, 4), f32)
+    rast[0, 0, :-1, 0], rast[0, 0, :-1, 1], rast[0, 0, :-1, 3] = 0.25, 0.5, ids
+    rast[0, 0, -1] = [np.nan, 0.5, 0.0, 1.0]
+    out = ref.interpolate(attr, rast, tri)[0, 0]
+    a0 = 0.25 * 1.0 + 0.5 * 2.0 + 0.25 * 4.0
+    a1 = 0.25 * 2.0 + 0.5 * 4.0 + 0.25 * 8.0
+    np.testing.assert_array_equal(out[:3, 0], [a0, a1, a1])          # 2.9 truncates to triangle 1
+    np.testing.assert_array_equal(out[:3, 1], [10 * a0, 10 * a1, 10 * a1])
+    assert not out[3:len(ids)].any()                                 # bad vertex indices, bad ids
+    assert np.isnan(out[-1]).all()
+    batched = ref.interpolate(np.stack([attr, 2 * attr]), np.concatenate([rast, rast]), tri)
+    np.testing.assert_array_equal(batched[1], 2 * batched[0])

@@ -412,3 +412,233 @@ def test_host_arrays_work_too():
     assert isinstance(rast, torch.Tensor) and not rast.is_cuda
     _assert_bits(rast, ref.rasterize(clip, t, H, W), "rast (host)")
     _assert_bits(dr.interpolate(vc, rast.numpy(), t)[0], ref.interpolate(vc, rast.numpy(), t), "interpolate (host)")
+
+
+# ---------------------------------------------------------------- the big-triangle list's overflow
+
+BIG_CAP = 1 << 20          # big-list entries per chunk (csrc/pedp_render.hip)
+KEY_BUDGET = 128 << 20     # key bytes per automatic chunk
+
+
+def _big_triangles(N, F, S, rng, min_px=10):
+    """N x 3F x 4 clip positions (w = 1) of F triangles per pose, each inside the viewport with a projected bounding box
+    at least min_px wide and tall and an area of at least 20 px^2: none is culled, every rectangle exceeds 64 px."""
+    px = 2.0 / S
+    xy = np.empty((N, F, 3, 2))
+    todo = np.ones((N, F), bool)
+    while todo.any():
+        k = int(todo.sum())
+        c = rng.uniform(-0.7, 0.7, (k, 1, 2))
+        xy[todo] = c + rng.uniform(-0.28, 0.28, (k, 3, 2))
+        ext = xy.max(2) - xy.min(2)
+        e1, e2 = xy[:, :, 1] - xy[:, :, 0], xy[:, :, 2] - xy[:, :, 0]
+        area = 0.5 * np.abs(e1[..., 0] * e2[..., 1] - e1[..., 1] * e2[..., 0]) / (px * px)
+        todo = (ext < min_px * px).any(-1) | (area < 20)
+    pos = np.ones((N, F * 3, 4), np.float32)
+    pos[..., :2] = xy.reshape(N, F * 3, 2)
+    pos[..., 2] = rng.uniform(-0.9, 0.9, (N, F * 3))
+    assert (np.abs(pos[..., :2]) <= 0.98).all()
+    return pos
+
+
+def test_big_list_overflow_rasterize():
+    """655 poses x 2048 triangles at 160 x 160, one automatic chunk: 1,341,440 big rectangles for a list of 2^20, so
+    292,864 lanes cover their own rectangles.  Which lanes overflow depends on the order of the atomics; the result
+    must not."""
+    from pedp_hip import render
+    from pedp_hip.compat import dr
+
+    N, F, S = 655, 2048, 160
+    assert KEY_BUDGET // (8 * S * S) == N                      # one chunk
+    assert N * F == 1_341_440 and N * F - BIG_CAP == 292_864   # entries past the list's end
+    assert 8 * F < BIG_CAP                                      # chunks of 8 poses: 16,384 entries, no overflow
+    pos = _big_triangles(N, F, S, np.random.default_rng(31))
+    tri = np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+    pos_t, tri_t = torch.as_tensor(pos, device="cuda"), torch.as_tensor(tri, device="cuda")
+    a, _ = dr.rasterize(None, pos_t, tri_t, (S, S))
+    b, _ = dr.rasterize(None, pos_t, tri_t, (S, S))
+    _assert_bits(b, a, "second run")
+    del b
+    try:
+        render.set_pose_chunk(8)
+        c, _ = dr.rasterize(None, pos_t, tri_t, (S, S))
+    finally:
+        render.set_pose_chunk(0)
+    _assert_bits(c, a, "chunks of 8 poses")
+    del c
+    for k in (0, 1, 327, 653, 654):
+        _assert_bits(a[k], ref.rasterize(pos[k:k + 1], tri, S, S)[0], f"pose {k} against the restatement")
+    assert (a[..., 3] > 0).float().mean().item() > 0.7
+
+
+def test_big_list_overflow_fused_render():
+    """The fused path's overflow: 2048 large triangles at 655 perturbed poses, 160 x 160."""
+    from pedp_hip import render, synth
+    from pedp_hip.compat import nvdiffrast_render, projection_matrix_from_intrinsics
+
+    N, F, S = 655, 2048, 160
+    rng = np.random.default_rng(32)
+    K = np.array([[200.0, 0, 79.5], [0, 200.0, 79.5], [0, 0, 1]])
+    c = np.concatenate([rng.uniform(-0.12, 0.12, (F, 1, 2)), rng.uniform(0.45, 0.55, (F, 1, 1))], 2)
+    off = rng.uniform(0.035, 0.06, (F, 3, 2)) * np.array([[[-1, -1], [1, -0.2], [-0.3, 1]]])
+    v = (c + np.concatenate([off, rng.uniform(-0.02, 0.02, (F, 3, 1))], 2)).reshape(-1, 3).astype(np.float32)
+    t = np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+    n = np.tile(np.array([0, 0, -1], np.float32), (3 * F, 1))
+    poses = np.empty((N, 4, 4), np.float32)
+    for i in range(N):
+        T = np.eye(4)
+        T[:3, :3] = synth.axis_angle(rng.normal(size=3), rng.uniform(0, np.deg2rad(2)))
+        T[:3, 3] = rng.uniform(-0.005, 0.005, 3)
+        poses[i] = T
+    # the overflow is reached: more than 2^20 (pose, triangle) rectangles of at least 10 x 10 px, inside the image
+    cam = np.einsum("nij,vj->nvi", poses[:, :3, :3].astype(np.float64), v.astype(np.float64)) + poses[:, None, :3, 3]
+    uv = (cam[..., :2] / cam[..., 2:]) * 200.0 + 79.5
+    uv = uv.reshape(N, F, 3, 2)
+    ext = uv.max(2) - uv.min(2)
+    big = ((ext >= 10).all(-1) & (uv.min((2, 3)) >= 0) & (uv.max((2, 3)) <= S)).sum()
+    assert big > BIG_CAP + 100_000, f"only {big} big rectangles"
+    mt = _mesh_tensors(v, t, n)
+    pt = torch.as_tensor(poses, device="cuda")
+
+    def run():
+        extra = {}
+        out = nvdiffrast_render(K=K, H=S, W=S, ob_in_cams=pt, mesh_tensors=mt, use_light=True, get_normal=True, extra=extra)
+        return list(out) + [extra["xyz_map"]]
+
+    a = run()
+    for x, y, what in zip(a, run(), ("color", "depth", "normal", "xyz")):
+        _assert_bits(y, x, f"{what}, second run")
+    try:
+        render.set_pose_chunk(8)
+        c8 = run()
+    finally:
+        render.set_pose_chunk(0)
+    for x, y, what in zip(a, c8, ("color", "depth", "normal", "xyz")):
+        _assert_bits(y, x, f"{what}, chunks of 8 poses")
+    del c8
+    proj = projection_matrix_from_intrinsics(K, S, S, 0.001, 100).astype(np.float32)
+    for k in (0, 654):
+        want = ref.render(v, t, n, poses[k:k + 1], proj, S, S, S, S, vcolor=mt["vertex_color"].cpu().numpy(), get_normal=True,
+                          use_light=True)
+        for x, w, what in zip(a, want, ("color", "depth", "normal", "xyz")):
+            _assert_bits(x[k:k + 1], w, f"{what}, pose {k} against the restatement")
+    assert (a[1] > 0).float().mean().item() > 0.5
+
+
+# ---------------------------------------------------------------- dr.texture and dr.interpolate, bit for bit
+
+f32 = np.float32
+
+
+def _guard_u(n):
+    """float32 u at which the sampler's x = u n - 0.5 is exactly 1e8 (sampled as zeros) and the one just below it."""
+    n32 = f32(n)
+
+    def x(u):
+        return f32(f32(u) * n32) - f32(0.5)
+
+    u = f32(f32(1e8) / n32)
+    while x(u) >= f32(1e8):
+        u = np.nextafter(u, f32(0))
+    while x(u) < f32(1e8):
+        u = np.nextafter(u, f32(np.inf))
+    return u, np.nextafter(u, f32(0))
+
+
+def _texture_case(N, th, tw, C, per_image, rng):
+    tex = rng.random((N if per_image else 1, th, tw, C), dtype=np.float32) + f32(0.5)   # no zero texel
+    H, W = 6, 40
+    uv = rng.uniform(-2.5, 3.5, (N, H, W, 2)).astype(np.float32)
+    j = np.arange(tw + 1)
+    i = np.arange(th + 1)
+    row_u = np.concatenate([(j[:tw] + 0.5) / tw, j / tw, [0.0, 1.0, -1.0 / tw, -0.25, 1.25, 2.0, -3.0]]).astype(np.float32)
+    row_v = np.concatenate([(i[:th] + 0.5) / th, i / th, [0.0, 1.0, -1.0 / th, -0.25, 1.25, 2.0, -3.0]]).astype(np.float32)
+    k = min(W, len(row_u))
+    uv[:, 0, :k, 0] = row_u[:k]                        # texel centres and edges, 0 and 1, wrap in u
+    k = min(W, len(row_v))
+    uv[:, 1, :k, 1] = row_v[:k]                        # ... and in v
+    at_u, below_u = _guard_u(tw)
+    at_v, below_v = _guard_u(th)
+    special = [(np.nan, 0.3), (0.3, np.nan), (np.inf, 0.3), (0.3, -np.inf), (-np.inf, np.inf), (at_u, 0.3), (-at_u, 0.3),
+               (0.3, at_v), (below_u, 0.3), (0.3, below_v), (-below_u, -below_v)]
+    uv[:, 2, :len(special)] = np.array(special, np.float32)
+    zero = np.zeros((H, W), bool)
+    zero[2, :8] = True                                  # NaN, inf and |x| >= 1e8: zeros
+    return tex, uv, zero
+
+
+@pytest.mark.parametrize("C", [1, 2, 3, 4, 16])
+@pytest.mark.parametrize("per_image", [False, True])
+def test_texture_bit_equal_to_restatement(C, per_image):
+    from pedp_hip.compat import dr
+
+    rng = np.random.default_rng(C * 2 + per_image)
+    N = 3
+    for th, tw in ((1, 1), (1, 7), (5, 1), (13, 21)):
+        tex, uv, zero = _texture_case(N, th, tw, C, per_image, rng)
+        want = ref.texture(tex, uv)
+        assert not want[:, zero].any() and want[:, ~zero].all(), "the case does not separate zeros from samples"
+        got = dr.texture(torch.as_tensor(tex, device="cuda"), torch.as_tensor(uv, device="cuda"), filter_mode="linear")
+        assert got.is_cuda and tuple(got.shape) == (N, 6, 40, C)
+        _assert_bits(got, want, f"{th} x {tw}, device")
+        _assert_bits(dr.texture(tex, uv), want, f"{th} x {tw}, host")
+        for dt in (np.float64, np.float16):  # other dtypes: the result of their float32 conversion
+            tx, u = tex.astype(dt), uv.astype(dt)
+            w2 = ref.texture(tx.astype(np.float32), u.astype(np.float32))
+            _assert_bits(dr.texture(torch.as_tensor(tx, device="cuda"), torch.as_tensor(u, device="cuda")), w2, f"{dt.__name__} device")
+            _assert_bits(dr.texture(tx, u), w2, f"{dt.__name__} host")
+
+
+def test_texture_refuses_bad_channel_and_texture_counts():
+    from pedp_hip import _lib
+    from pedp_hip.compat import dr
+
+    uv = torch.zeros((3, 4, 4, 2), device="cuda")
+    with pytest.raises(_lib.PedpError):
+        dr.texture(torch.zeros((1, 2, 2, 17), device="cuda"), uv)
+    with pytest.raises(_lib.PedpError):
+        dr.texture(torch.zeros((2, 2, 2, 3), device="cuda"), uv)
+    assert tuple(dr.texture(torch.zeros((3, 2, 2, 16), device="cuda"), uv).shape) == (3, 4, 4, 16)
+
+
+@pytest.mark.parametrize("A", [1, 2, 3, 7])
+@pytest.mark.parametrize("per_image", [False, True])
+def test_interpolate_bit_equal_to_restatement(A, per_image):
+    """rast from dr.rasterize, then edited: ids 0, F + 1, 2.5 (triangle 1), negative and NaN, NaN barycentrics with a
+    valid id, and triangles that name a vertex outside [0, V)."""
+    from pedp_hip.compat import dr, projection_matrix_from_intrinsics
+
+    v, t, _ = _torus("tiny")
+    N, H, W = 3, 24, 32
+    F, V = len(t), len(v)
+    K = _K(W, H)
+    M, win = ref.pose_records(projection_matrix_from_intrinsics(K, H, W, 0.001, 100).astype(np.float32), _poses(N, seed=40), None,
+                              H, W)
+    clip = np.stack([ref.clip_vertices(v, M[i], win[i]) for i in range(N)])
+    rast, _ = dr.rasterize(None, torch.as_tensor(clip, device="cuda"), torch.as_tensor(t, device="cuda"), (H, W))
+    rast = rast.cpu().numpy()
+    assert (rast[..., 3] > 0).sum() > 200
+    tri = t.copy()
+    tri[5] = [-1, 1, 2]              # a negative vertex index
+    tri[6] = [0, V, 2]               # one past the last vertex
+    tri[7] = [3, 4, 2 ** 31 - 1]
+    # (id, barycentrics, expected): 0 zeros, 1 a value, nan NaN
+    edits = [(0.0, "", 0), (F + 1.0, "", 0), (2.5, "", 1), (-1.0, "", 0), (-0.5, "", 0), (np.nan, "", 0), (2.0, "u", np.nan),
+             (4.0, "v", np.nan), (6.0, "", 0), (7.0, "", 0), (8.0, "", 0), (float(F), "", 1), (F + 0.5, "", 0), (3.999, "", 1)]
+    where = []
+    for k, (rid, bad, _) in enumerate(edits):
+        at = (k % N, 2 + k // 4, 3 + 5 * (k % 4))
+        where.append(at)
+        rast[at][:2] = [np.nan if bad == "u" else 0.25, np.nan if bad == "v" else 0.5]
+        rast[at][3] = rid
+    rng = np.random.default_rng(A)
+    attr = rng.normal(size=((N, V, A) if per_image else (V, A))).astype(np.float32)
+    want = ref.interpolate(attr, rast, tri)
+    for at, (rid, _, exp) in zip(where, edits):
+        val = want[at]
+        ok = np.isnan(val).all() if exp is np.nan else (not val.any() if exp == 0 else np.isfinite(val).all() and val.any())
+        assert ok, f"the restatement at id {rid}: {val}"
+    got = dr.interpolate(torch.as_tensor(attr, device="cuda"), torch.as_tensor(rast, device="cuda"), torch.as_tensor(tri, device="cuda"))[0]
+    assert got.is_cuda and tuple(got.shape) == (N, H, W, A)
+    _assert_bits(got, want, "device")
+    _assert_bits(dr.interpolate(attr, rast, tri)[0], want, "host")
