@@ -148,6 +148,7 @@ PROTOTYPES = {
     "pedp_pose_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     "pedp_max_pair_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_double)]),
+    "pedp_mask_depth_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
 }
@@ -335,6 +336,12 @@ class PoseUpdateParams(C.Structure):
 
 TRANS_TRACKNET, TRANS_RAW = 0, 1
 ROT_AXIS_ANGLE, ROT_6D = 0, 1
+
+
+class MaskDepthStats(C.Structure):
+    """pedp_mask_depth_record (include/pedp.h)."""
+    _fields_ = [("n_pos", C.c_int32), ("n_valid", C.c_int32), ("n_med", C.c_int32), ("umin", C.c_int32), ("umax", C.c_int32),
+                ("vmin", C.c_int32), ("vmax", C.c_int32), ("median", C.c_float)]
 
 
 class ProjectOpts(C.Structure):

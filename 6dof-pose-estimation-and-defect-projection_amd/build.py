@@ -29,6 +29,7 @@ SOURCES = {
     "pedp_render.hip": [],
     "pedp_crop.hip": [],
     "pedp_pose.hip": [],
+    "pedp_estimator.hip": [],
     "pedp_cluster.cpp": [],
 }
 HEADERS = ["pedp_internal.h", os.path.join("..", "..", "include", "pedp.h")]

@@ -5,8 +5,9 @@ The hot-path names, the global registration that precedes them u
 `determine_pose(icp=True)`, the message format to the viewer thread (`update_dash_data`), and FoundationPose's
 renderer (`nvdiffrast_render`, `make_mesh_tensors` and the `dr` stand-in for `nvdiffrast.torch`), and its crop batches
 (`make_crop_data_batch`, `make_score_crop_data_batch` and the `kornia` stand-in with `warp_perspective`), and the pose
-arithmetic of its refinement loop (`pose_update`, `max_pair_distance`); the Dash app, sensor
-and learned-model code stay the reference's own.
+arithmetic of its refinement loop (`pose_update`, `max_pair_distance`), and the estimator with the two predictors'
+loops (`FoundationPose`, `PoseRefinePredictor`, `ScorePredictor`, estimator.py); the Dash app, sensor code and the
+networks with their weights stay the reference's own.
 """
 import numpy as np
 
@@ -47,6 +48,8 @@ from .render import (dr, glcam_in_cvcam, make_mesh_tensors, nvdiffrast_render,  
 from .crop import (BatchPoseData, compute_crop_window_tf_batch, kornia, make_crop_data_batch,  # noqa: E402,F401  (Utils.py:577-621)
                    make_score_crop_data_batch, warp_perspective)
 from .pose import max_pair_distance, pose_update  # noqa: E402,F401  (predict_pose_refine.py:195-231, Utils.py:559-574)
+from .estimator import (FoundationPose, PoseRefinePredictor, ScorePredictor, compute_mesh_diameter,  # noqa: E402,F401
+                        euler_matrix, guess_translation, mask_depth_stats, sample_views_icosphere, set_seed)
 
 
 class _MyCpp:
@@ -75,4 +78,6 @@ __all__ = [
     "nvdiffrast_render", "make_mesh_tensors", "projection_matrix_from_intrinsics", "glcam_in_cvcam", "dr",
     "warp_perspective", "kornia", "compute_crop_window_tf_batch", "make_crop_data_batch", "make_score_crop_data_batch",
     "BatchPoseData", "pose_update", "max_pair_distance",
+    "FoundationPose", "PoseRefinePredictor", "ScorePredictor", "guess_translation", "mask_depth_stats", "set_seed",
+    "sample_views_icosphere", "euler_matrix", "compute_mesh_diameter",
 ]

@@ -144,6 +144,8 @@ struct pedp_ctx_s {
     pedp_scratch crop_io;    // crop batches: inputs and outputs of host-memory calls
     pedp_scratch pose_ws;    // pose arithmetic: the pair maximum's key and flag (and its host-memory points)
     pedp_scratch pose_io;    // pose update: inputs and outputs of host-memory calls
+    pedp_scratch stats_ws;   // mask/depth statistics: counters, the three passes' histograms, the record
+    pedp_scratch stats_io;   // mask/depth statistics: the frame and the mask of host-memory calls
     int render_chunk = 0;    // pedp_render_configure: poses per chunk (0 = by a key budget)
     bool icp_exhaustive = false;  // pedp_icp_configure: no culling (all-pairs sweep every pass)
     int icp_timed_pass = -1;      // pedp_icp_configure: HIP events around the sweep kernel of this pass

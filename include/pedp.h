@@ -636,6 +636,26 @@ int pedp_pose_update(pedp_ctx_t ctx, const pedp_pose_update_params *prm, int B, 
  * memory; the call returns once it is written. */
 int pedp_max_pair_distance(pedp_ctx_t ctx, const double *pts, int64_t n, int mem, double *out);
 
+/* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
+ * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
+ * The contract is DESIGN.md s4.11.  With pos = mask > 0, truthy = mask.astype(bool) (for a float32 mask they differ on
+ * negative and NaN entries) and near = depth >= float32(0.001) (false for NaN):
+ *   n_pos, umin, umax, vmin, vmax   count and box of pos (u = column, v = row); the box is -1 when n_pos = 0
+ *   n_valid                         count of near & pos
+ *   n_med, median                   count of truthy & near and numpy's median of those depths bit for bit: the middle
+ *                                   element, or (a + b) / 2 in float32 of the two middle ones; NaN when n_med = 0 */
+typedef struct pedp_mask_depth_record {
+    int32_t n_pos, n_valid, n_med;
+    int32_t umin, umax, vmin, vmax;
+    float median;
+} pedp_mask_depth_record;
+
+/* depth H x W float32 and mask H x W of mask_dtype (PEDP_U8: uint8 or bool bytes; PEDP_F32), both contiguous, host or
+ * device memory by `mem`; H * W <= 4096 * 4096.  *out is host memory; the call returns once it is written.  Integer
+ * atomics only: the record does not depend on scheduling. */
+int pedp_mask_depth_stats(pedp_ctx_t ctx, const float *depth, const void *mask, int mask_dtype, int H, int W, int mem,
+                          pedp_mask_depth_record *out);
+
 /* ---------------------------------------------------------------- cluster_poses
  * Replaces mycpp.cluster_poses (mycpp/src/app/pybind_api.cpp:24-68; caller
  * estimater.py:118).  Host only.  poses: n x 16 float32 row-major, syms: s x 16.
