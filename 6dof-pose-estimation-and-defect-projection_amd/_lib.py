@@ -115,6 +115,7 @@ PROTOTYPES = {
     "pedp_nn_last_sweep_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
     "pedp_icp_last_stats": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_planned_passes": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
+    "pedp_icp_last_serial_path": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
     "pedp_icp_end": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int32), C.c_void_p, C.c_void_p]),
@@ -664,6 +665,14 @@ def icp_last_stats(ctx):
     a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     check(load().pedp_icp_last_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c)), "pedp_icp_last_stats")
     return a.value, b.value, c.value
+
+
+def icp_last_serial_path(ctx):
+    """(passes of the last single icp() closed by the wide close, its bracket: bit 0 the start kernel, bit 1 the final
+    state written by the closing workgroup).  PEDP_ICP_SERIAL_CLOSE=1 / PEDP_ICP_COPY_BRACKET=1 give (0, 0)."""
+    a, b = C.c_int64(0), C.c_int64(0)
+    check(load().pedp_icp_last_serial_path(ctx._h, C.byref(a), C.byref(b)), "pedp_icp_last_serial_path")
+    return a.value, b.value
 
 
 def icp_last_planned_passes(ctx):

@@ -39,9 +39,17 @@
 #include "pedp_internal.h"
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 #include <new>
+
+// The in-launch close of a pass hands data from workgroup to workgroup without fences: relaxed agent-scope
+// atomics, sc1 loads and stores past the CU's L1, s_waitcnt for "my stores have left".  That is sound on
+// gfx950's cache hierarchy and has been checked on nothing else.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "pedp_icp.hip: the fence-free close of a pass rests on gfx950's caches; build with --offload-arch=gfx950 only"
+#endif
 
 #ifndef PEDP_NN_EXPERIMENT
 #define PEDP_NN_EXPERIMENT 0
@@ -142,6 +150,8 @@ struct IcpState {
     unsigned ticket_base, idle_base;
     int n_planned;             // passes of this registration that ran under a visit plan (statistics)
     int nonce;                 // of this registration (<< 16 in the tags of the visit plan: entries of an earlier registration never match)
+    int n_wide;                // passes of this registration closed by the wide close (statistics: tests check it was in force)
+    int reserved_;
     double T_init[16];         // the start transformation: slot 0 of the update history (arrives with the state, no copy of its own)
 };
 
@@ -1192,16 +1202,21 @@ __device__ bool solve6_ldlt(const double *Ain, const double *b, double *x) {
     return ok;
 }
 
-__device__ void vec6_to_T(const double *x, double *T) {
-    double ca, sa, cb, sb, cc, sc;  // one argument reduction per angle
-    sincos(x[0], &sa, &ca);
-    sincos(x[1], &sb, &cb);
-    sincos(x[2], &sc, &cc);
+// the update from the angles' sines and cosines (the wide close computes the three sincos on three lanes at once
+// and calls this with the values it has gathered: the same expressions either way)
+__device__ __forceinline__ void sincos_to_T(double sa, double ca, double sb, double cb, double sc, double cc, const double *x, double *T) {
     ident4(T);
     T[0] = cc * cb;  T[1] = cc * sb * sa - sc * ca;  T[2] = cc * sb * ca + sc * sa;
     T[4] = sc * cb;  T[5] = sc * sb * sa + cc * ca;  T[6] = sc * sb * ca - cc * sa;
     T[8] = -sb;      T[9] = cb * sa;                 T[10] = cb * ca;
     T[3] = x[3]; T[7] = x[4]; T[11] = x[5];
+}
+__device__ void vec6_to_T(const double *x, double *T) {
+    double ca, sa, cb, sb, cc, sc;  // one argument reduction per angle
+    sincos(x[0], &sa, &ca);
+    sincos(x[1], &sb, &cb);
+    sincos(x[2], &sc, &cc);
+    sincos_to_T(sa, ca, sb, cb, sc, cc, x, T);
 }
 
 __device__ double det3_dev(const double *M) {
@@ -1672,6 +1687,10 @@ struct PassArgs {
     int4 *visit;                // [2][visit_cap]: (live rank, chunk, pass + 1 it is meant for, n_live) for workgroup b of pass p at [p & 1][b]
     int2 *dur;                  // [2][visit_cap]: (cycles, pass + 1 that measured them) by live rank, at [p & 1][rank]
     int visit_cap, n_cu;
+    // the closing workgroup that ends the registration (it sets `done`) also writes the final state here, into the
+    // executor's page-locked block: no copy follows the last pass (single registration; null: the host copies)
+    unsigned long long *down;
+    int serial_close;           // PEDP_ICP_SERIAL_CLOSE=1: the close as it was, everything after the sums on one lane
 };
 
 template <typename T>
@@ -1704,13 +1723,24 @@ struct FinishArgs {
     // in-launch finish: what the closing workgroup read of the state when the launch began (pass, rebuild flag, live
     // count do not change inside a pass) -- no second, dependent read in front of the partial sums' loads
     int known = 0, k_pass = 0, k_rebuild = 0, k_n_live = 0;
+    // in-launch finish: where the final state goes once `done` is set (page-locked host memory; null: nowhere)
+    unsigned long long *down = nullptr;
+    // 0: the wide close -- the first look at the sign-off counters travels with the partial sums' loads, and behind the
+    // solve the three sincos run on three lanes, the sixteen entries of the new pose on sixteen; 1: all of it on lane 0,
+    // one step after the other, as it was.  Every output is computed by the same sequence of float64 operations.
+    int serial = 0;
 };
 template <int NT, int LCAP>
 struct FinishLds {
     double slice[32][32], pk[32];
     int scan[NT], lst[LCAP];
-    int do_rebuild, n_live_s;
+    int do_rebuild, n_live_s, stopped;
+    double t0[16];  // the pose the pass started from
 };
+// lane 0's value in every lane of a wave whose lanes are all active
+__device__ __forceinline__ double bcast0(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
 // COHERENT: the partial sums and the live mask were written earlier in THIS launch by other
 // workgroups (sc1 stores / atomics): read them past this CU's L1 -- global_load ... sc1, never a
 // flat_ load (the pointers come out of the LDS-parked argument block, so the address space is
@@ -1744,15 +1774,29 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                  margin = st->margin;
     constexpr int PARTS = 32, TPARTS = NT / 32, PPT = PARTS / TPARTS;  // ranges; ranges in flight; ranges per thread
     static_assert(NT % 32 == 0 && PARTS % TPARTS == 0, "thread count");
-    if (tid == 0) L.do_rebuild = 0;
+    const bool wide = f.serial == 0;
+    if (tid == 0) { L.do_rebuild = 0; L.stopped = 0; }
     if (tid == 0) PEDP_STAMP(2, 0, 0);
     if (tid == 0 && pass == 5) PEDP_STAMP(2, 3, 0);
-    // what the solving thread needs of the state is requested now, ahead of the sums
-    double T0[16], fit0 = 0.0, rmse0 = 0.0, mu_th0 = 0.0, mu_ta0 = 0.0;
+    // The first look at the sign-off counters is requested here, with the partial sums' loads, and evaluated where
+    // the poll stands: the counters only grow, so a look that is complete now is complete then, and only a look that
+    // comes back short enters the spin.  (With fewer live chunks than workgroups there are idle workgroups in every
+    // pass, so the look -- a device-scope round trip -- used to be paid behind the sum's two barriers, every pass.)
+    const bool early_look = wide && COHERENT && f.n_idle > 0;
+    unsigned look0 = 0u, idle_base0 = 0u;
+    if (early_look && tid < 64) {
+        if (tid < 16) look0 = __hip_atomic_load((g_u32 *)(uintptr_t)(f.idle + 32 * tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        idle_base0 = st->idle_base;  // (rewritten only by this workgroup, further down)
+    }
+    // what the solving thread needs of the state is requested now, ahead of the sums; the pose is parked in LDS, an
+    // entry per lane (the barriers of the sums lie between this store and its readers): held in lane 0's registers
+    // through the sums and the solve it was thirty-two registers of a kernel at its cap, spilled and fetched back
+    double fit0 = 0.0, rmse0 = 0.0, mu_th0 = 0.0, mu_ta0 = 0.0;
+    int n_wide0 = 0;
+    if (tid < 16) L.t0[tid] = st->T[tid];
     if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) T0[k] = st->T[k];
         fit0 = st->fitness; rmse0 = st->rmse; mu_th0 = st->mu_theta; mu_ta0 = st->mu_tau;
+        if (wide) n_wide0 = st->n_wide;
     }
 #if PEDP_ICP_STAMPS
     if (tid == 0) { g_icp_stamps[2][1][0] = (long long)__builtin_amdgcn_s_memtime(); g_icp_stamps[2][1][1] = (long long)__builtin_amdgcn_s_memrealtime(); }
@@ -1886,10 +1930,12 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
     }
     if (COHERENT && f.n_idle > 0 && tid < 64) {  // normally true at the first look
         for (unsigned spins = 0;; ++spins) {
-            unsigned c = tid < 16 ? __hip_atomic_load((g_u32 *)(uintptr_t)(f.idle + 32 * tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+            unsigned c = look0;  // (the wide close's first look is back already)
+            if (!early_look || spins > 0)
+                c = tid < 16 ? __hip_atomic_load((g_u32 *)(uintptr_t)(f.idle + 32 * tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
 #pragma unroll
             for (int off = 8; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-            if (__shfl(c, 0, 64) - st->idle_base >= (unsigned)f.n_idle) break;
+            if (__shfl(c, 0, 64) - (early_look ? idle_base0 : st->idle_base) >= (unsigned)f.n_idle) break;
             if (spins > (1u << 22)) {  // bounded: a lost workgroup must not hang the device -- but the pass is NOT closed over
                 if (tid == 0) L.do_rebuild = -1;   // workgroups that may still read the old state: the registration fails loudly
                 break;
@@ -1900,124 +1946,188 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
     if (COHERENT && f.n_idle > 0) {
         __syncthreads();
         if (L.do_rebuild == -1) {  // (workgroup-uniform)
-            if (tid == 0) st->done = -1;   // icp_collect / the batch driver turn this into PEDP_ERR_HIP
+            if (tid == 0) {
+                st->done = -1;   // icp_collect / the batch driver turn this into PEDP_ERR_HIP
+                if (f.down) *(int *)((char *)f.down + offsetof(IcpState, done)) = -1;  // (where icp_collect looks when no copy follows)
+            }
             return;
         }
     }
-    if (tid == 0) {
-        PEDP_STAMP(2, 0, 1);
-        if (pass == 5) PEDP_STAMP(2, 3, 3);
-        if (COHERENT) { st->ticket_base += (unsigned)f.n_busy; st->idle_base += (unsigned)f.n_idle; }
-        if (f.phase == 0) {
-            st->sum_tiles += (long long)L.pk[PACKET];
-            st->sum_fb += (long long)L.pk[PACKET + 1];
-            st->n_live = L.n_live_s;
-        }
-        L.do_rebuild = 0;
-        const double *pk = L.pk;
-        const double K = pk[28];
-        double fit = 0.0, rmse = 0.0;
-        if (K > 0.0) { fit = K / n_source; rmse = sqrt(pk[27] / K); }
-        st->prev_fitness = fit0;
-        st->prev_rmse = rmse0;
-        st->fitness = fit;
-        st->rmse = rmse;
-        if (f.trace) {
-            PEDP_GLOBAL double *tr = as_global(f.trace) + 18 * pass;
-            tr[0] = fit; tr[1] = rmse;
-            for (int k = 0; k < 16; ++k) tr[2 + k] = T0[k];
-        }
-        st->iters = pass;
-        bool stop = pass >= max_iter;
-        if (pass > 0 && fabs(fit0 - fit) < rel_fitness && fabs(rmse0 - rmse) < rel_rmse) stop = true;
-        if (stop) {
-            st->done = 1;
-        } else {
-            double upd[16];
-            ident4(upd);
-            PEDP_STAMP(2, 2, 0);
-            if (pass == 5) PEDP_STAMP(2, 3, 4);
-            if (K > 0.0) {
-                if (f.estimator == PEDP_POINT_TO_PLANE) {
-                    double A[36], nb[6], x[6];
-                    int k = 0;
+    // Everything from here to the state's last store is one dependent chain that 255 CUs wait for.  The serial close
+    // runs all of it on lane 0.  The wide close keeps lane 0 for what is one chain by nature (criteria, the pivoted
+    // solve, the motion bound) and gives wave 0's other lanes what is several independent pieces: a lane per angle
+    // for the three sincos, a lane per entry for upd x T0 and for the stores of both matrices.  Each output is
+    // computed by the sequence of float64 operations the serial close uses (sincos_to_T; mat4_mul_dev's sum).
+    if (wide ? tid < 64 : tid == 0) {
+        const bool l0 = tid == 0;
+        int stop_i = 0, angles_i = 0;  // angles: the update is made from x (point-to-plane, the solve succeeded)
+        double upd[16], x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        ident4(upd);
+        if (l0) {
+            PEDP_STAMP(2, 0, 1);
+            if (pass == 5) PEDP_STAMP(2, 3, 3);
+            if (COHERENT) { st->ticket_base += (unsigned)f.n_busy; st->idle_base += (unsigned)f.n_idle; }
+            if (f.phase == 0) {
+                st->sum_tiles += (long long)L.pk[PACKET];
+                st->sum_fb += (long long)L.pk[PACKET + 1];
+                st->n_live = L.n_live_s;
+            }
+            L.do_rebuild = 0;
+            const double *pk = L.pk;
+            const double K = pk[28];
+            double fit = 0.0, rmse = 0.0;
+            if (K > 0.0) { fit = K / n_source; rmse = sqrt(pk[27] / K); }
+            st->prev_fitness = fit0;
+            st->prev_rmse = rmse0;
+            st->fitness = fit;
+            st->rmse = rmse;
+            if (f.trace) {
+                PEDP_GLOBAL double *tr = as_global(f.trace) + 18 * pass;
+                tr[0] = fit; tr[1] = rmse;
+                for (int k = 0; k < 16; ++k) tr[2 + k] = L.t0[k];
+            }
+            st->iters = pass;
+            if (wide) st->n_wide = n_wide0 + 1;
+            bool stop = pass >= max_iter;
+            if (pass > 0 && fabs(fit0 - fit) < rel_fitness && fabs(rmse0 - rmse) < rel_rmse) stop = true;
+            if (stop) {
+                st->done = 1;
+                if (COHERENT && f.down) {  // the final state goes to the host from here (below): this lane's stores have left first
+                    L.stopped = 1;
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                stop_i = 1;
+            } else {
+                PEDP_STAMP(2, 2, 0);
+                if (pass == 5) PEDP_STAMP(2, 3, 4);
+                if (K > 0.0) {
+                    if (f.estimator == PEDP_POINT_TO_PLANE) {
+                        double A[36], nb[6];
+                        int k = 0;
 #pragma unroll
-                    for (int u = 0; u < 6; ++u)
+                        for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int v = u; v < 6; ++v) { A[6 * u + v] = pk[k]; A[6 * v + u] = pk[k]; ++k; }
+                            for (int v = u; v < 6; ++v) { A[6 * u + v] = pk[k]; A[6 * v + u] = pk[k]; ++k; }
 #pragma unroll
-                    for (int u = 0; u < 6; ++u) nb[u] = -pk[21 + u];
-                    const bool ok = solve6_ldlt_reg(A, nb, x);
-                    PEDP_STAMP(2, 2, 1);
-                    if (ok) vec6_to_T(x, upd);
-                    PEDP_STAMP(2, 2, 2);
-                } else {
-                    const double *c = st->centroid;
-                    double ms[3], mt[3], sig[9];
-                    for (int u = 0; u < 3; ++u) { ms[u] = pk[u] / K; mt[u] = pk[3 + u] / K; }
-                    for (int u = 0; u < 3; ++u)
-                        for (int v = 0; v < 3; ++v) sig[3 * u + v] = pk[6 + 3 * u + v] / K - mt[u] * ms[v];
-                    double U[9], w[3], V[9];
-                    svd3_dev(sig, U, w, V);
-                    const double sgn = (det3_dev(U) * det3_dev(V) < 0.0) ? -1.0 : 1.0;
-                    double R[9];
-                    for (int u = 0; u < 3; ++u)
-                        for (int v = 0; v < 3; ++v)
-                            R[3 * u + v] = U[3 * u] * V[3 * v] + U[3 * u + 1] * V[3 * v + 1] + sgn * U[3 * u + 2] * V[3 * v + 2];
-                    for (int u = 0; u < 3; ++u) {
-                        for (int v = 0; v < 3; ++v) upd[4 * u + v] = R[3 * u + v];
-                        const double msa[3] = {ms[0] + c[0], ms[1] + c[1], ms[2] + c[2]};
-                        upd[4 * u + 3] = (mt[u] + c[u]) - (R[3 * u] * msa[0] + R[3 * u + 1] * msa[1] + R[3 * u + 2] * msa[2]);
+                        for (int u = 0; u < 6; ++u) nb[u] = -pk[21 + u];
+                        const bool ok = solve6_ldlt_reg(A, nb, x);
+                        PEDP_STAMP(2, 2, 1);
+                        if (ok) {
+                            if (wide) angles_i = 1;
+                            else vec6_to_T(x, upd);
+                        }
+                        if (!wide) PEDP_STAMP(2, 2, 2);
+                    } else {
+                        const double *c = st->centroid;
+                        double ms[3], mt[3], sig[9];
+                        for (int u = 0; u < 3; ++u) { ms[u] = pk[u] / K; mt[u] = pk[3 + u] / K; }
+                        for (int u = 0; u < 3; ++u)
+                            for (int v = 0; v < 3; ++v) sig[3 * u + v] = pk[6 + 3 * u + v] / K - mt[u] * ms[v];
+                        double U[9], w[3], V[9];
+                        svd3_dev(sig, U, w, V);
+                        const double sgn = (det3_dev(U) * det3_dev(V) < 0.0) ? -1.0 : 1.0;
+                        double R[9];
+                        for (int u = 0; u < 3; ++u)
+                            for (int v = 0; v < 3; ++v)
+                                R[3 * u + v] = U[3 * u] * V[3 * v] + U[3 * u + 1] * V[3 * v + 1] + sgn * U[3 * u + 2] * V[3 * v + 2];
+                        for (int u = 0; u < 3; ++u) {
+                            for (int v = 0; v < 3; ++v) upd[4 * u + v] = R[3 * u + v];
+                            const double msa[3] = {ms[0] + c[0], ms[1] + c[1], ms[2] + c[2]};
+                            upd[4 * u + 3] = (mt[u] + c[u]) - (R[3 * u] * msa[0] + R[3 * u + 1] * msa[1] + R[3 * u + 2] * msa[2]);
+                        }
                     }
                 }
             }
-            PEDP_STAMP(2, 0, 2);
-            if (pass == 5) PEDP_STAMP(2, 3, 5);
-            for (int k = 0; k < 16; ++k) { st->upd[k] = upd[k]; as_global(f.hist)[16 * (pass + 1) + k] = upd[k]; }
-            {
+        }
+        if (wide) {  // (all 64 lanes of wave 0 are here: lane 0 is the first)
+            stop_i = __builtin_amdgcn_readfirstlane(stop_i);
+            angles_i = __builtin_amdgcn_readfirstlane(angles_i);
+        }
+        if (!stop_i) {
+            if (wide) {
+                if (angles_i) {  // wave-uniform
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) x[k] = bcast0(x[k]);
+                    double s, c;
+                    sincos(tid == 0 ? x[0] : (tid == 1 ? x[1] : x[2]), &s, &c);  // one angle per lane
+                    const double sa = __shfl(s, 0, 64), ca = __shfl(c, 0, 64), sb = __shfl(s, 1, 64), cb = __shfl(c, 1, 64),
+                                 sc = __shfl(s, 2, 64), cc = __shfl(c, 2, 64);
+                    sincos_to_T(sa, ca, sb, cb, sc, cc, x, upd);
+                    if (l0) PEDP_STAMP(2, 2, 2);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) upd[k] = bcast0(upd[k]);
+                }
+                if (l0) PEDP_STAMP(2, 0, 2);
+                if (l0 && pass == 5) PEDP_STAMP(2, 3, 5);
+                // lane k = 4 i + j holds entry (i, j) of the update and of upd x T0 (mat4_mul_dev's sum) and stores both
+                const int i = (tid >> 2) & 3, j = tid & 3;
+                double tn = 0.0, u_ij = 0.0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const double a = i == 0 ? upd[k] : (i == 1 ? upd[4 + k] : (i == 2 ? upd[8 + k] : upd[12 + k]));
+                    const double b = L.t0[4 * k + j];
+                    tn += a * b;
+                    u_ij = j == k ? a : u_ij;
+                }
+                if (tid < 16) {
+                    st->upd[tid] = u_ij;
+                    as_global(f.hist)[16 * (pass + 1) + tid] = u_ij;
+                    st->T[tid] = tn;
+                }
+            } else {
+                PEDP_STAMP(2, 0, 2);
+                if (pass == 5) PEDP_STAMP(2, 3, 5);
+                for (int k = 0; k < 16; ++k) { st->upd[k] = upd[k]; as_global(f.hist)[16 * (pass + 1) + k] = upd[k]; }
                 double Tn[16];
-                mat4_mul_dev(upd, T0, Tn);
+                mat4_mul_dev(upd, L.t0, Tn);
                 for (int k = 0; k < 16; ++k) st->T[k] = Tn[k];
             }
-            // how far this update can move a point near the target: |R - I|_F (>= the spectral norm) and
-            // |t + (R - I) c| about the box centre c
-            double th2 = 0.0, tv[3];
-            for (int u = 0; u < 3; ++u) {
-                tv[u] = upd[4 * u + 3];
-                const double cc[3] = {f.bcx, f.bcy, f.bcz};
-                for (int v = 0; v < 3; ++v) {
-                    const double dlt = upd[4 * u + v] - (u == v ? 1.0 : 0.0);
-                    th2 += dlt * dlt;
-                    tv[u] += dlt * cc[v];
+            if (l0) {
+                // how far this update can move a point near the target: |R - I|_F (>= the spectral norm) and
+                // |t + (R - I) c| about the box centre c
+                double th2 = 0.0, tv[3];
+                for (int u = 0; u < 3; ++u) {
+                    tv[u] = upd[4 * u + 3];
+                    const double cc[3] = {f.bcx, f.bcy, f.bcz};
+                    for (int v = 0; v < 3; ++v) {
+                        const double dlt = upd[4 * u + v] - (u == v ? 1.0 : 0.0);
+                        th2 += dlt * dlt;
+                        tv[u] += dlt * cc[v];
+                    }
                 }
+                double mu_th = mu_th0 + sqrt(th2), mu_ta = mu_ta0 + sqrt(tv[0] * tv[0] + tv[1] * tv[1] + tv[2] * tv[2]);
+                const double mu = mu_th * reachE + mu_ta;
+                if (!(mu < 0.95 * margin)) {  // also when mu is NaN
+                    L.do_rebuild = 1;
+                    mu_th = 0.0;
+                    mu_ta = 0.0;
+                    st->n_rebuilds += 1;
+                }
+                st->mu_theta = mu_th;
+                st->mu_tau = mu_ta;
+                st->rebuild = L.do_rebuild;
+                st->pass = pass + 1;
+                PEDP_STAMP(2, 2, 3);
+                if (pass == 5) PEDP_STAMP(2, 3, 6);
             }
-            double mu_th = mu_th0 + sqrt(th2), mu_ta = mu_ta0 + sqrt(tv[0] * tv[0] + tv[1] * tv[1] + tv[2] * tv[2]);
-            const double mu = mu_th * reachE + mu_ta;
-            if (!(mu < 0.95 * margin)) {  // also when mu is NaN
-                L.do_rebuild = 1;
-                mu_th = 0.0;
-                mu_ta = 0.0;
-                st->n_rebuilds += 1;
-            }
-            st->mu_theta = mu_th;
-            st->mu_tau = mu_ta;
-            st->rebuild = L.do_rebuild;
-            st->pass = pass + 1;
-            PEDP_STAMP(2, 2, 3);
-            if (pass == 5) PEDP_STAMP(2, 3, 6);
         }
-        PEDP_STAMP(2, 0, 3);
+        if (l0) PEDP_STAMP(2, 0, 3);
     }
     __syncthreads();
     if (L.do_rebuild)  // the next pass lists the live chunks anew; it resets what the old ones leave behind
         for (int wi = tid; wi < f.n_lw; wi += NT) { as_global(f.live)[f.n_lw + wi] = load_live<COHERENT>(&f.live[wi]); as_global(f.live)[wi] = 0ull; }
+    // The registration ends here: its final state goes straight into the executor's page-locked block (read past this
+    // CU's L1: lane 0's stores have reached L2, see above), so that no copy follows the last pass.
+    if (COHERENT && f.down && L.stopped)
+        for (int i = tid; i < (int)(sizeof(IcpState) / sizeof(double)); i += NT) ((double *)f.down)[i] = load_sc1((const double *)st + i);
 }
 
 constexpr int FIN_THREADS = 1024;
 __global__ __launch_bounds__(FIN_THREADS) void icp_finish_kernel(IcpState *st, unsigned long long *live, int32_t *live_list,
                                                          int n_lw, const double *partials, double *packet, int phase, int estimator,
                                                          double *__restrict__ trace, double *__restrict__ hist,
-                                                         double bcx, double bcy, double bcz, size_t pose_stride) {
+                                                         double bcx, double bcy, double bcz, size_t pose_stride, int serial) {
     {   // pose b = blockIdx.x of a batch: its state and buffers are b * pose_stride bytes behind pose 0's
         const size_t off = (size_t)blockIdx.x * pose_stride;
         st = pose_ptr(st, off); live = pose_ptr(live, off); live_list = pose_ptr(live_list, off);
@@ -2028,6 +2138,7 @@ __global__ __launch_bounds__(FIN_THREADS) void icp_finish_kernel(IcpState *st, u
     FinishArgs f;
     f.live = live; f.live_list = live_list; f.n_lw = n_lw; f.partials = partials; f.packet = packet; f.phase = phase;
     f.estimator = estimator; f.trace = trace; f.hist = hist; f.bcx = bcx; f.bcy = bcy; f.bcz = bcz;
+    f.serial = serial;
     icp_finish_body<FIN_THREADS, LIVE_CAP, false>(st, f, L, threadIdx.x);
 }
 
@@ -2799,6 +2910,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     f.n_idle = (int)gridDim.x - n_wg;
     f.n_busy = n_wg;
     if (!BATCH && planned && threadIdx.x == 0) st->n_planned += 1;
+    f.down = BATCH ? nullptr : a.down; f.serial = a.serial_close;
     f.known = 1; f.k_pass = pass; f.k_rebuild = rebuild ? 1 : 0; f.k_n_live = n_live;
     icp_finish_body<W * 64, 2048, true>(st, f, fin, threadIdx.x);
     PEDP_RT(pass, 4);
@@ -2821,6 +2933,18 @@ __global__ __launch_bounds__(256) void batch_state_gather_kernel(const char *__r
     const unsigned long long *src = (const unsigned long long *)(st0 + (size_t)blockIdx.x * pose_stride);
     unsigned long long *dst = down + (size_t)blockIdx.x * state_words;
     for (int i = threadIdx.x; i < state_words; i += blockDim.x) dst[i] = src[i];
+}
+
+// A single registration's start: the state from the page-locked block into its slot, tickets, sign-off counters and
+// live masks zeroed, and both parities of the visit plan and of the duration table too -- those are valid by tag
+// alone, and zeroing them here means that no bit of a registration rests on what earlier users left in the workspace.
+// One launch in front of pass 0 instead of a copy and a fill.
+__global__ __launch_bounds__(256) void icp_state_start_kernel(const unsigned long long *__restrict__ up, unsigned long long *__restrict__ st,
+                                                              int state_words, unsigned long long *__restrict__ zero, int zero_words,
+                                                              unsigned long long *__restrict__ plan, int plan_words) {
+    for (int i = threadIdx.x; i < state_words; i += blockDim.x) st[i] = up[i];
+    for (int i = threadIdx.x; i < zero_words; i += blockDim.x) zero[i] = 0ull;
+    for (int i = threadIdx.x; i < plan_words; i += blockDim.x) plan[i] = 0ull;
 }
 
 // ------------------------------------------------------------------ host side
@@ -3064,10 +3188,24 @@ inline bool no_visit_plan() {  // PEDP_ICP_NO_VISIT_PLAN=1: every workgroup take
     static const bool m = getenv("PEDP_ICP_NO_VISIT_PLAN") && atoi(getenv("PEDP_ICP_NO_VISIT_PLAN")) != 0;
     return m;
 }
+// PEDP_ICP_SERIAL_CLOSE=1: the close of a pass as it was -- the sign-off counters looked at only after the sums, and
+// everything behind them on one lane (A/B timing; tests compare the two bit for bit)
+inline bool serial_close() {
+    static const bool m = getenv("PEDP_ICP_SERIAL_CLOSE") && atoi(getenv("PEDP_ICP_SERIAL_CLOSE")) != 0;
+    return m;
+}
+// PEDP_ICP_COPY_BRACKET=1: a single registration bracketed as it was -- a host-to-device copy of the state and a fill
+// in front of pass 0, a device-to-host copy of the state behind the last pass -- instead of icp_state_start_kernel
+// and the closing workgroup's own write of the final state
+inline bool copy_bracket() {
+    static const bool m = getenv("PEDP_ICP_COPY_BRACKET") && atoi(getenv("PEDP_ICP_COPY_BRACKET")) != 0;
+    return m;
+}
 // Enqueue the kernel of a fused pass.  fuse: the workgroup that finishes last closes the pass
 // (sum, solve, update); otherwise icp_finish_kernel launches follow (exchange step in between).
 int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_cloud_t tgt, int estimator,
-                       const TargetPrep &tp, hipEvent_t ev0, hipEvent_t ev1, bool fuse, double *trace, int poses = 1) {
+                       const TargetPrep &tp, hipEvent_t ev0, hipEvent_t ev1, bool fuse, double *trace, int poses = 1,
+                       unsigned long long *down = nullptr) {
     PassArgs pa;
     pa.src = src->pts; pa.perm = w.src_perm; pa.N = src->N; pa.n_chunks = w.n_chunks;
     pa.hist = w.hist; pa.Pk = w.Pk; pa.Tprev = w.Tprev; pa.live = w.live; pa.live_list = w.live_list;
@@ -3082,6 +3220,7 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pe
     pa.pose_stride = poses > 1 ? w.pose_stride : 0;
     pa.fuse = fuse && !unfused_finish() ? 1 : 0; pa.n_lw = w.n_lw; pa.packet = w.packet; pa.trace = trace; pa.ticket = w.ticket;
     const bool plan = poses <= 1 && !no_visit_plan();
+    pa.down = poses <= 1 && pa.fuse ? down : nullptr; pa.serial_close = serial_close() ? 1 : 0;
     pa.visit = plan ? w.visit : nullptr; pa.dur = plan ? w.dur : nullptr; pa.visit_cap = w.visit_cap; pa.n_cu = c->num_cus;
     // grid-stride loop over the live chunks: any grid is correct; two workgroups per CU are resident
     int64_t g = w.n_chunks;
@@ -3215,7 +3354,13 @@ struct IcpJob {
     int64_t Ns = 0, Nt = 0;
     bool exhaustive = false;
     int timed_pass = -1;
+    // the final state is written into the page-locked block by the workgroup that ends the registration, RESULT_OFF
+    // bytes in (the start state is read from the block's first bytes while the passes run); false: a copy brings it
+    // to the block's start
+    bool dev_result = false;
 };
+constexpr size_t RESULT_OFF = 2048;
+static_assert(sizeof(IcpState) <= RESULT_OFF && sizeof(IcpState) % 8 == 0, "start and final state share the block's first 4 KB, as 8-byte words");
 
 int icp_check_args(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *prm) {
     PEDP_REQUIRE(source->ctx == c && target->ctx == c, "pedp_icp: cloud belongs to another context");
@@ -3263,6 +3408,7 @@ int icp_job_setup(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const 
     // the fused pass lists a target's mask words in LDS: up to BK_WCAP words of 1024 rows
     const bool fused = job.qt == 1 && !job.exhaustive && r > 0.0 && job.Ns > 0 && job.Nt > 0 &&
                        (job.Nt + 1023) / 1024 <= BK_WCAP;
+    job.dev_result = fused && !prm->allreduce && !prm->use_comm && !unfused_finish() && !copy_bracket();
     int rc = carve_workspace(x, job.Ns, job.Nt, job.max_iter, job.qt, w, fused);
     if (rc) return rc;
     w.tgt4 = (const float4 *)target->tgt4;
@@ -3303,6 +3449,11 @@ void icp_fill_state(IcpState *dst, const TargetPrep &tp, const double init[16], 
     *dst = h;
 }
 
+// The closing workgroup that ends the registration writes its final state RESULT_OFF bytes into the page-locked
+// block; until then the slot says "not done" (called in front of every enqueue or replay, with the stream's earlier
+// registration collected).
+void icp_arm_result(pedp_ctx_t x) { ((IcpState *)((char *)x->pinned + RESULT_OFF))->done = 0; }
+
 // every pass of one registration on x's stream; nothing here allocates or synchronises unless
 // early_stop is set, so the sequence can be captured into a graph
 int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp,
@@ -3316,7 +3467,8 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
     // Open3D: max_correspondence_distance <= 0 or an empty cloud gives an empty result
     const bool degenerate = (r <= 0.0 || Ns == 0 || Nt == 0);
     IcpState *hp = (IcpState *)x->pinned;
-    PEDP_HIP_CHECK(hipMemcpyAsync(w.st, hp, sizeof(IcpState), hipMemcpyHostToDevice, x->stream));
+    unsigned long long *down = job.dev_result ? (unsigned long long *)((char *)x->pinned + RESULT_OFF) : nullptr;
+    if (copy_bracket()) PEDP_HIP_CHECK(hipMemcpyAsync(w.st, hp, sizeof(IcpState), hipMemcpyHostToDevice, x->stream));
     const double r2 = r * r;
     const double ng = n_global > 0 ? n_global : 1.0;
     const bool exchange = prm->allreduce || prm->use_comm;  // the packet is summed over ranks before the solve
@@ -3326,9 +3478,19 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
         // tickets, sign-off counters and both live masks start at zero: one memset (they lie one behind the other); the
         // start transformation -- slot 0 of the history -- arrives inside the state; pass 0 itself writes "no
         // correspondence" for every chunk it does not visit
-        PEDP_HIP_CHECK(hipMemsetAsync(w.ticket, 0, (size_t)((char *)w.live - (char *)w.ticket) + sizeof(unsigned long long) * 2 * (size_t)w.n_lw, x->stream));
+        const size_t zero_bytes = (size_t)((char *)w.live - (char *)w.ticket) + sizeof(unsigned long long) * 2 * (size_t)w.n_lw;
+        if (copy_bracket())
+            PEDP_HIP_CHECK(hipMemsetAsync(w.ticket, 0, zero_bytes, x->stream));
+        else  // state, zeroes and an empty visit plan in one launch (the plan and the durations lie one behind the other)
+            hipLaunchKernelGGL(icp_state_start_kernel, dim3(1), dim3(256), 0, x->stream, (const unsigned long long *)hp, (unsigned long long *)w.st,
+                               (int)(sizeof(IcpState) / 8), (unsigned long long *)w.ticket, (int)(zero_bytes / 8),
+                               (unsigned long long *)w.visit, (int)((sizeof(int4) + sizeof(int2)) * 2 * (size_t)w.visit_cap / 8));
         for (int k = 0; k < 3; ++k) bc[k] = 0.5 * (tp.lo[k] + tp.hi[k]);
+    } else if (!copy_bracket()) {
+        hipLaunchKernelGGL(icp_state_start_kernel, dim3(1), dim3(256), 0, x->stream, (const unsigned long long *)hp, (unsigned long long *)w.st,
+                           (int)(sizeof(IcpState) / 8), (unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, 0);
     }
+    PEDP_HIP_CHECK(hipGetLastError());
     if (job.timed_pass != -1) { x->nn_pairs = 0; x->nn_span_launches = 1; }
     for (int pass = 0; pass <= max_iter; ++pass) {
         // timing: one chosen pass (pair nn_ev0/1), or -- timed_pass = -2 -- every fourth pass from
@@ -3347,14 +3509,14 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
             ++x->nn_pairs;
         }
         if (fused) {
-            rc = enqueue_fused_pass(x, w, source, target, prm->estimator, tp, ev0, ev1, !exchange, want_trace ? w.trace : nullptr);
+            rc = enqueue_fused_pass(x, w, source, target, prm->estimator, tp, ev0, ev1, !exchange, want_trace ? w.trace : nullptr, 1, down);
             if (rc) return rc;
             if (!exchange && unfused_finish())
                 hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(FIN_THREADS), 0, x->stream, w.st, w.live, w.live_list, w.n_lw, w.cpart, w.packet, 0,
-                                   prm->estimator, want_trace ? w.trace : nullptr, w.hist, bc[0], bc[1], bc[2], (size_t)0);
+                                   prm->estimator, want_trace ? w.trace : nullptr, w.hist, bc[0], bc[1], bc[2], (size_t)0, serial_close() ? 1 : 0);
             if (exchange) {  // sum -> all-reduce over the ranks -> solve
                 hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(FIN_THREADS), 0, x->stream, w.st, w.live, w.live_list, w.n_lw, w.cpart, w.packet, 1,
-                                   prm->estimator, want_trace ? w.trace : nullptr, w.hist, bc[0], bc[1], bc[2], (size_t)0);
+                                   prm->estimator, want_trace ? w.trace : nullptr, w.hist, bc[0], bc[1], bc[2], (size_t)0, serial_close() ? 1 : 0);
                 if (prm->use_comm) {
                     rc = pedp_comm_allreduce_sum_f64(x, w.packet, PACKET);
                     if (rc) { (void)hipStreamSynchronize(x->stream); return rc; }
@@ -3364,7 +3526,7 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
                     return PEDP_ERR_COLLECTIVE;
                 }
                 hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(FIN_THREADS), 0, x->stream, w.st, w.live, w.live_list, w.n_lw, w.cpart, w.packet, 2,
-                                   prm->estimator, want_trace ? w.trace : nullptr, w.hist, bc[0], bc[1], bc[2], (size_t)0);
+                                   prm->estimator, want_trace ? w.trace : nullptr, w.hist, bc[0], bc[1], bc[2], (size_t)0, serial_close() ? 1 : 0);
             }
             PEDP_HIP_CHECK(hipGetLastError());
         } else {
@@ -3405,7 +3567,7 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
             if (*flag) break;
         }
     }
-    PEDP_HIP_CHECK(hipMemcpyAsync(hp, w.st, sizeof(IcpState), hipMemcpyDeviceToHost, x->stream));
+    if (!job.dev_result) PEDP_HIP_CHECK(hipMemcpyAsync(hp, w.st, sizeof(IcpState), hipMemcpyDeviceToHost, x->stream));
     return PEDP_OK;
 }
 
@@ -3418,7 +3580,11 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     if (trace)
         PEDP_HIP_CHECK(hipMemcpyAsync(trace, w.trace, sizeof(double) * 18 * (size_t)(job.max_iter + 1), hipMemcpyDeviceToHost, x->stream));
     PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
-    const IcpState *hp = (const IcpState *)x->pinned;
+    const IcpState *hp = (const IcpState *)((const char *)x->pinned + (job.dev_result ? RESULT_OFF : 0));
+    if (job.dev_result && hp->done == 0) {  // (armed by icp_arm_result; the workgroup that sets `done` writes the state)
+        pedp_set_error("pedp_icp: the registration's final state did not arrive");
+        return PEDP_ERR_HIP;
+    }
     if (hp->done < 0) {
         pedp_set_error("pedp_icp: a pass could not be closed (workgroups of its launch did not sign off in time)");
         return PEDP_ERR_HIP;
@@ -3429,6 +3595,8 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     x->icp_last_fb = hp->sum_fb;
     x->icp_last_passes = hp->iters + 1;
     x->icp_last_planned = hp->n_planned;
+    x->icp_last_wide = hp->n_wide;
+    x->icp_last_bracket = (copy_bracket() ? 0 : 1) + (job.dev_result ? 2 : 0);
     x->icp_last_nt = job.Nt;
     if (fitness) *fitness = hp->fitness;
     if (inlier_rmse) *inlier_rmse = hp->rmse;
@@ -3452,6 +3620,7 @@ int icp_launch_replayed(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, 
     int rc = icp_job_setup(x, source, target, prm, job);
     if (rc) return rc;
     icp_fill_state((IcpState *)x->pinned, tp, init, prm, source->N);
+    icp_arm_result(x);
     pedp_icp_graph_key key;
     key.src_gen = source->gen; key.tgt_gen = target->gen; key.ws = x->icp_ws.ptr;
     key.Ns = job.Ns; key.Nt = job.Nt; key.max_iter = job.max_iter; key.qt = job.qt; key.estimator = prm->estimator;
@@ -3538,7 +3707,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
                 hipLaunchKernelGGL(icp_finish_kernel, dim3((unsigned)G), dim3(FIN_THREADS), 0, c->stream, w.st, w.live, w.live_list,
                                    w.n_lw, w.cpart, w.packet, 0, prms[0].estimator, (double *)nullptr, w.hist,
                                    0.5 * (tp.lo[0] + tp.hi[0]), 0.5 * (tp.lo[1] + tp.hi[1]), 0.5 * (tp.lo[2] + tp.hi[2]),
-                                   G > 1 ? w.pose_stride : (size_t)0);
+                                   G > 1 ? w.pose_stride : (size_t)0, serial_close() ? 1 : 0);
         }
         const hipError_t e = hipStreamEndCapture(c->stream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -3579,7 +3748,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
                         hipLaunchKernelGGL(icp_finish_kernel, dim3((unsigned)G), dim3(FIN_THREADS), 0, c->stream, w.st, w.live, w.live_list,
                                            w.n_lw, w.cpart, w.packet, 0, prms[0].estimator, (double *)nullptr, w.hist,
                                            0.5 * (tp.lo[0] + tp.hi[0]), 0.5 * (tp.lo[1] + tp.hi[1]), 0.5 * (tp.lo[2] + tp.hi[2]),
-                                           G > 1 ? w.pose_stride : (size_t)0);
+                                           G > 1 ? w.pose_stride : (size_t)0, serial_close() ? 1 : 0);
                 }
             } else
             PEDP_HIP_CHECK(hipGraphLaunch(c->icp_bgraph[slot], c->stream));
@@ -3636,6 +3805,7 @@ int pedp_icp(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const pedp_
     rc = icp_job_setup(c, source, target, prm, job);
     if (rc) return rc;
     icp_fill_state((IcpState *)c->pinned, tp, init, prm, source->N);
+    icp_arm_result(c);
     rc = icp_enqueue(c, source, target, tp, prm, trace != nullptr, true, job);
     if (rc) return rc;
     return icp_collect(c, job, T_out, fitness, inlier_rmse, n_iter_done, corr, trace);
@@ -3656,6 +3826,7 @@ int pedp_icp_begin(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const
     rc = icp_job_setup(c, source, target, prm, *job);
     if (!rc) {
         icp_fill_state((IcpState *)c->pinned, tp, init, prm, source->N);
+        icp_arm_result(c);
         rc = icp_enqueue(c, source, target, tp, prm, want_trace != 0, false, *job);
     }
     if (rc) { delete job; return rc; }
@@ -3717,6 +3888,7 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
                 rc = icp_job_setup(c, source, target, &prms[b], job);
                 if (rc) return rc;
                 icp_fill_state((IcpState *)c->pinned, tp, inits + 16 * b, &prms[b], source->N);
+                icp_arm_result(c);
                 rc = icp_enqueue(c, source, target, tp, &prms[b], false, true, job);
                 if (rc) return rc;
                 rc = icp_collect(c, job, T_out + 16 * b, fitness ? fitness + b : nullptr, inlier_rmse ? inlier_rmse + b : nullptr,
@@ -3902,6 +4074,13 @@ int pedp_debug_nn_bf16(pedp_ctx_t c, const float *src4, int64_t n_src, const flo
 int pedp_icp_last_planned_passes(pedp_ctx_t c, int64_t *planned) {
     PEDP_REQUIRE(c && planned, "pedp_icp_last_planned_passes: null argument");
     *planned = c->icp_last_planned;
+    return PEDP_OK;
+}
+
+int pedp_icp_last_serial_path(pedp_ctx_t c, int64_t *wide_closes, int64_t *bracket) {
+    PEDP_REQUIRE(c && wide_closes && bracket, "pedp_icp_last_serial_path: null argument");
+    *wide_closes = c->icp_last_wide;
+    *bracket = c->icp_last_bracket;
     return PEDP_OK;
 }
 

@@ -483,6 +483,19 @@ int pedp_icp_last_stats(pedp_ctx_t ctx, int64_t *passes, int64_t *pairs_swept, i
  * tests/test_icp_gpu.py compares).  No counterpart in the reference (src/pose_estimation.py:447-453 calls Open3D). */
 int pedp_icp_last_planned_passes(pedp_ctx_t ctx, int64_t *planned);
 
+/* The serial part of a pass and of a registration, for the last single registration collected on `ctx`.
+ * wide_closes: passes whose close ran in its wide form -- the first look at the sign-off counters requested with the
+ * partial sums' loads, the three sincos of the update on three lanes, the sixteen entries of the new pose on sixteen --
+ * each output by the same sequence of float64 operations as on one lane (PEDP_ICP_SERIAL_CLOSE=1: one lane, 0 here).
+ * bracket: bit 0 -- the start state was fetched from the context's page-locked block by a kernel that also zeroes the
+ * tickets, sign-off counters, live masks and the visit plan (one launch in front of pass 0 instead of a copy and a
+ * fill); bit 1 -- the final state was written into that block by the workgroup that ended the registration, no copy
+ * behind the last pass (PEDP_ICP_COPY_BRACKET=1: copies and fill as before, 0 here).  Results do not change in any
+ * bit either way (tests/test_icp_serial_path_gpu.py compares).  Between pedp_icp_begin and pedp_icp_end the device
+ * writes the page-locked block at a time of its own choosing: every entry point that touches the block's first 4 KB
+ * or the ICP workspace returns PEDP_ERR_BAD_ARG while a registration is pending. */
+int pedp_icp_last_serial_path(pedp_ctx_t ctx, int64_t *wide_closes, int64_t *bracket);
+
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
  * g[i * n_tgt + j] = |t'_j|^2 - 2 s'_i . t'_j exactly as the sweep's v_mfma_f32_16x16x32_bf16 produces it (same operand packing). */
