@@ -150,6 +150,9 @@ PROTOTYPES = {
                                    C.c_void_p, C.c_void_p]),
     "pedp_max_pair_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_double)]),
     "pedp_mask_depth_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "pedp_conv3x3_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
 }
@@ -333,6 +336,12 @@ class PoseUpdateParams(C.Structure):
     """pedp_pose_update_params (include/pedp.h)."""
     _fields_ = [("trans_rep", C.c_int32), ("rot_rep", C.c_int32), ("normalize_xyz", C.c_int32),
                 ("trans_normalizer", C.c_float * 3), ("rot_normalizer", C.c_float), ("mesh_diameter", C.c_double)]
+
+
+class Conv3x3Params(C.Structure):
+    """pedp_conv3x3_params (include/pedp.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
+                ("y_ld", C.c_int32), ("y_c0", C.c_int32), ("res_ld", C.c_int32), ("res_c0", C.c_int32), ("relu", C.c_int32)]
 
 
 TRANS_TRACKNET, TRANS_RAW = 0, 1

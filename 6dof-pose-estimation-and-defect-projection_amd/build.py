@@ -30,6 +30,7 @@ SOURCES = {
     "pedp_crop.hip": [],
     "pedp_pose.hip": [],
     "pedp_estimator.hip": [],
+    "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_cluster.cpp": [],
 }
 HEADERS = ["pedp_internal.h", os.path.join("..", "..", "include", "pedp.h")]

@@ -1,0 +1,322 @@
+"""FoundationPose's refine and score networks, with their residual blocks on this package's 3x3 convolution kernel.
+
+    RefineNet(cfg, c_in)            learning/models/refine_network.py:26-93      -> {'trans': B x 3, 'rot': B x 3 or B x 6}
+    ScoreNetMultiPair(cfg, c_in)    learning/models/score_network.py:27-90       -> {'score_logit': B/L x L}
+    load_refiner / load_scorer      the checkpoint loading of predict_pose_refine.py:109-120 and predict_score.py:131-141
+
+The modules are written here after the reference's architecture (network_modules.py); what they share with it is the
+contract: `state_dict()` has the reference's keys, shapes, dtypes and order, so a published checkpoint loads with
+strict=True.  Weights stay the user's file.
+
+Two forwards.  In eval mode on a GPU under float16 autocast (how the predictors call a network with
+amp=True) and with backend 'hip' or 'auto', the twelve stride-1 3x3 convolutions of the residual blocks run through
+conv.conv3x3 on channels-last float16 buffers kept per batch size, BatchNorm folded into packed weights that are built
+on first use and dropped by load_state_dict, .to() and .train().  Everything else (the stride-2 convolutions, the
+heads), and every other case (training, CPU, float32 / float64, backend 'torch'), is plain torch.  Weights changed in
+place after the first fused forward are not seen: call `drop_packed()`.
+"""
+import math
+
+import torch
+import torch.nn as nn
+
+from . import conv as _conv
+
+_BACKENDS = ("auto", "hip", "torch")
+
+# backend 'auto': which path a block convolution of this many channels takes -- the kernel where tools/networks_time.py
+# finds it not slower than F.conv2d on the same channels-last float16 tensors, torch otherwise.
+# NOT MEASURED YET: no figures exist for either side, so every shape stays on torch until profiles/networks_time.json
+# holds the pairs (kernel ms, torch ms) to quote here.
+_AUTO = {
+    128: "torch",   # 504 images of 40 x 40: unmeasured
+    256: "torch",   # 252 images of 40 x 40: unmeasured
+    512: "torch",   # 252 images of 20 x 20: unmeasured
+}
+
+
+def _get(cfg, key, default):
+    if cfg is None:
+        return default
+    try:
+        v = cfg[key]
+    except (KeyError, TypeError, AttributeError, IndexError):
+        v = getattr(cfg, key, None)
+    return default if v is None else v
+
+
+class _ConvNormReLU(nn.Module):
+    """Convolution, optional BatchNorm2d, ReLU as one `net` (keys net.0.*, net.1.*)."""
+
+    def __init__(self, c_in, c_out, kernel_size, stride, norm):
+        super().__init__()
+        layers = [nn.Conv2d(c_in, c_out, kernel_size, stride, (kernel_size - 1) // 2, bias=True)]
+        if norm:
+            layers.append(nn.BatchNorm2d(c_out))
+        layers.append(nn.ReLU(inplace=True))
+        self.net = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return self.net(x)
+
+
+class _BasicBlock(nn.Module):
+    """ResNet basic block without downsampling: relu(bn2(conv2(relu(bn1(conv1(x))))) + x), the convolutions with bias."""
+
+    def __init__(self, planes, norm):
+        super().__init__()
+        self.conv1 = nn.Conv2d(planes, planes, 3, 1, 1, bias=True)
+        if norm:
+            self.bn1 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=True)
+        if norm:
+            self.bn2 = nn.BatchNorm2d(planes)
+        self.norm = bool(norm)
+
+    def forward(self, x):
+        out = self.conv1(x)
+        if self.norm:
+            out = self.bn1(out)
+        out = self.relu(out)
+        out = self.conv2(out)
+        if self.norm:
+            out = self.bn2(out)
+        out += x
+        return self.relu(out)
+
+    def pairs(self):
+        return ((self.conv1, self.bn1 if self.norm else None), (self.conv2, self.bn2 if self.norm else None))
+
+
+class _PositionTable(nn.Module):
+    """Sinusoidal position table 1 x max_len x d_model (float32 arithmetic), added to the tokens."""
+
+    def __init__(self, d_model, max_len):
+        super().__init__()
+        pos = torch.arange(0, max_len).float().unsqueeze(1)
+        freq = (torch.arange(0, d_model, 2).float() * -(math.log(10000.0) / d_model)).exp()[None]
+        pe = torch.zeros(max_len, d_model).float()
+        pe[:, 0::2] = torch.sin(pos * freq)
+        pe[:, 1::2] = torch.cos(pos * freq)
+        self.register_buffer("pe", pe.unsqueeze(0))
+
+    def forward(self, x):
+        return x + self.pe[:, :x.size(1)]
+
+
+def _shared_encoder(c_in, norm):
+    return nn.Sequential(_ConvNormReLU(c_in, 64, 7, 2, norm), _ConvNormReLU(64, 128, 3, 2, norm), _BasicBlock(128, norm),
+                         _BasicBlock(128, norm))
+
+
+def _pair_encoder(norm):
+    return nn.Sequential(_BasicBlock(256, norm), _BasicBlock(256, norm), _ConvNormReLU(256, 512, 3, 2, norm),
+                         _BasicBlock(512, norm), _BasicBlock(512, norm))
+
+
+def _fp16_autocast():
+    return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
+
+
+class _PairNet(nn.Module):
+    """What both networks share: the two encoders' forward, in torch or fused, and the packed weights' life cycle.
+    Subclasses set `_enc_names` to their (shared encoder, pair encoder) attribute names."""
+
+    _enc_names = ("", "")
+
+    def _init_backend(self, backend):
+        self._packed = {}     # id(conv) -> PackedConv3x3 | None (None: a layer the kernel does not take, kept on torch)
+        self._buffers_nhwc = {}
+        self.set_backend(backend)
+
+    def set_backend(self, backend):
+        """'hip': every block convolution through the kernel; 'torch': none; 'auto': per layer by the measured table."""
+        if backend not in _BACKENDS:
+            raise ValueError(f"backend must be one of {_BACKENDS}, got {backend!r}")
+        self.backend = backend
+        return self
+
+    def drop_packed(self):
+        self._packed = {}
+        self._buffers_nhwc = {}
+
+    def train(self, mode=True):
+        self.drop_packed()
+        return super().train(mode)
+
+    def _apply(self, fn, *args, **kwargs):
+        self.drop_packed()
+        return super()._apply(fn, *args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        self.drop_packed()
+        return super().load_state_dict(*args, **kwargs)
+
+    # ------------------------------------------------------------ the encoders
+    def _encoders(self):
+        return getattr(self, self._enc_names[0]), getattr(self, self._enc_names[1])
+
+    def _uses_kernel(self, channels):
+        return self.backend == "hip" or (self.backend == "auto" and _AUTO.get(channels, "torch") == "hip")
+
+    def _fused(self, A):
+        return (any(self._uses_kernel(c) for c in (128, 256, 512)) and not self.training and A.is_cuda
+                and _fp16_autocast())
+
+    def encode(self, A, B):
+        """The pair encoder's output as tokens, bs x (h/8 * w/8) x 512, before the position table."""
+        if self._fused(A):
+            return self._encode_fused(A, B)
+        bs = len(A)
+        enc_a, enc_ab = self._encoders()
+        x = enc_a(torch.cat([A, B], dim=0))
+        ab = enc_ab(torch.cat((x[:bs], x[bs:]), 1).contiguous())
+        return ab.reshape(bs, ab.shape[1], -1).permute(0, 2, 1)
+
+    def _pack(self, conv, bn):
+        if not self._uses_kernel(conv.out_channels):
+            return None
+        key = id(conv)
+        if key not in self._packed:
+            self._packed[key] = _conv.pack_conv3x3(conv, bn) if _conv.supported(conv) else None
+        return self._packed[key]
+
+    def _conv(self, x, conv, bn, residual=None, out=None, out_c0=0):
+        """One block convolution with its norm, optional identity add and ReLU: x, residual N x H x W x C float16 ->
+        channels out_c0 ... of `out` (N x H x W x ld)."""
+        p = self._pack(conv, bn)
+        if p is not None:
+            return _conv.conv3x3(x, p, residual=residual, relu=True, out=out, out_c0=out_c0)
+        y = conv(x.permute(0, 3, 1, 2))          # a layer kept on torch: autocast's float16 convolution on the same view
+        if bn is not None:
+            y = bn(y)
+        y = y.permute(0, 2, 3, 1)
+        if residual is not None:
+            y = y + residual
+        dst = out[..., out_c0:out_c0 + conv.out_channels]
+        dst.copy_(torch.relu(y))
+        return dst
+
+    def _scratch(self, dev, bs, h, w):
+        key = (dev, bs, h, w)
+        buf = self._buffers_nhwc.get(key)
+        if buf is None:
+            if len(self._buffers_nhwc) >= 4:     # a tracker alternates between a few batch sizes; do not hoard more
+                self._buffers_nhwc.clear()
+            with torch.inference_mode(False):
+                def e(n, hh, ww, c):
+                    return torch.empty((n, hh, ww, c), dtype=torch.float16, device=dev)
+                buf = self._buffers_nhwc[key] = {"x": e(2 * bs, h, w, 128), "t": e(2 * bs, h, w, 128), "ab": e(bs, h, w, 256),
+                                                 "t2": e(bs, h, w, 256)}
+        return buf
+
+    def _encode_fused(self, A, B):
+        bs = len(A)
+        enc_a, enc_ab = self._encoders()
+        x = enc_a[1](enc_a[0](torch.cat([A, B], dim=0)))                   # the two stride-2 convolutions: torch
+        h, w = int(x.shape[2]), int(x.shape[3])
+        buf = self._scratch(x.device, bs, h, w)
+        xa, t, ab, t2 = buf["x"], buf["t"], buf["ab"], buf["t2"]
+        xa.copy_(x.permute(0, 2, 3, 1))                                    # the one conversion to channels-last float16
+        (c1, n1), (c2, n2) = enc_a[2].pairs()
+        self._conv(xa, c1, n1, out=t)
+        self._conv(t, c2, n2, residual=xa, out=xa)
+        (c1, n1), (c2, n2) = enc_a[3].pairs()
+        self._conv(xa, c1, n1, out=t)
+        self._conv(t[:bs], c2, n2, residual=xa[:bs], out=ab, out_c0=0)     # the A half and the B half land side by side:
+        self._conv(t[bs:], c2, n2, residual=xa[bs:], out=ab, out_c0=128)   # the channel concatenation costs no pass
+        for blk in (enc_ab[0], enc_ab[1]):
+            (c1, n1), (c2, n2) = blk.pairs()
+            self._conv(ab, c1, n1, out=t2)
+            self._conv(t2, c2, n2, residual=ab, out=ab)
+        y = enc_ab[2](ab.permute(0, 3, 1, 2))                              # 256 -> 512, stride 2: torch, zero-copy view
+        y = y.permute(0, 2, 3, 1).contiguous()
+        if y.dtype != torch.float16:
+            y = y.half()
+        t3 = torch.empty_like(y)
+        for blk in (enc_ab[3], enc_ab[4]):
+            (c1, n1), (c2, n2) = blk.pairs()
+            self._conv(y, c1, n1, out=t3)
+            self._conv(t3, c2, n2, residual=y, out=y)
+        return y.reshape(bs, -1, y.shape[3])
+
+
+class RefineNet(_PairNet):
+    """cfg: 'use_BN' (default False), 'rot_rep' ('axis_angle' or '6d', default 'axis_angle'), 'c_in' when the argument
+    is None (default 4)."""
+
+    _enc_names = ("encodeA", "encodeAB")
+
+    def __init__(self, cfg=None, c_in=None, n_view=1, backend="auto"):
+        super().__init__()
+        self.cfg = cfg
+        norm = bool(_get(cfg, "use_BN", False))
+        c_in = int(_get(cfg, "c_in", 4) if c_in is None else c_in)
+        rot_rep = _get(cfg, "rot_rep", "axis_angle")
+        if rot_rep not in ("axis_angle", "6d"):
+            raise ValueError(f"RefineNet: rot_rep {rot_rep!r}")
+        self.encodeA = _shared_encoder(c_in, norm)
+        self.encodeAB = _pair_encoder(norm)
+        self.pos_embed = _PositionTable(512, 400)
+        self.trans_head = nn.Sequential(nn.TransformerEncoderLayer(d_model=512, nhead=4, dim_feedforward=512, batch_first=True),
+                                        nn.Linear(512, 3))
+        self.rot_head = nn.Sequential(nn.TransformerEncoderLayer(d_model=512, nhead=4, dim_feedforward=512, batch_first=True),
+                                      nn.Linear(512, 3 if rot_rep == "axis_angle" else 6))
+        self._init_backend(backend)
+
+    def forward(self, A, B):
+        ab = self.pos_embed(self.encode(A, B))
+        return {"trans": self.trans_head(ab).mean(dim=1), "rot": self.rot_head(ab).mean(dim=1)}
+
+
+class ScoreNetMultiPair(_PairNet):
+    """cfg: 'use_BN' (default False), 'c_in' when the argument is None (default 4)."""
+
+    _enc_names = ("encoderA", "encoderAB")
+
+    def __init__(self, cfg=None, c_in=None, backend="auto"):
+        super().__init__()
+        self.cfg = cfg
+        norm = bool(_get(cfg, "use_BN", False))
+        c_in = int(_get(cfg, "c_in", 4) if c_in is None else c_in)
+        self.encoderA = _shared_encoder(c_in, norm)
+        self.encoderAB = _pair_encoder(norm)
+        self.att = nn.MultiheadAttention(embed_dim=512, num_heads=4, bias=True, batch_first=True)
+        self.att_cross = nn.MultiheadAttention(embed_dim=512, num_heads=4, bias=True, batch_first=True)
+        self.pos_embed = _PositionTable(512, 400)
+        self.linear = nn.Linear(512, 1)
+        self._init_backend(backend)
+
+    def extract_feat(self, A, B):
+        """A, B: (B*L) x C x H x W -> one 512-vector per pair."""
+        ab = self.pos_embed(self.encode(A, B))
+        ab, _ = self.att(ab, ab, ab)
+        return ab.mean(dim=1).reshape(len(A), -1)
+
+    def forward(self, A, B, L):
+        bs = A.shape[0] // L
+        x = self.extract_feat(A, B).reshape(bs, L, -1)
+        x, _ = self.att_cross(x, x, x)
+        return {"score_logit": self.linear(x).reshape(bs, L)}
+
+
+def _load(net, path_or_state, device):
+    state = path_or_state
+    if not hasattr(state, "keys"):
+        state = torch.load(state, weights_only=True, map_location="cpu")
+    if "model" in state:
+        state = state["model"]
+    net.load_state_dict(state, strict=True)
+    return net.to(device).eval()
+
+
+def load_refiner(path_or_state, cfg, backend="auto", device="cuda"):
+    """RefineNet(cfg) with a checkpoint (a path, a state dict, or {'model': state dict}) loaded strictly, on the GPU in
+    eval mode: `PoseRefinePredictor(model=load_refiner(path, cfg), cfg=cfg)`."""
+    return _load(RefineNet(cfg, backend=backend), path_or_state, device)
+
+
+def load_scorer(path_or_state, cfg, backend="auto", device="cuda"):
+    """ScoreNetMultiPair(cfg) the same way: `ScorePredictor(model=load_scorer(path, cfg), cfg=cfg)`."""
+    return _load(ScoreNetMultiPair(cfg, backend=backend), path_or_state, device)

@@ -669,6 +669,32 @@ typedef struct pedp_mask_depth_record {
 int pedp_mask_depth_stats(pedp_ctx_t ctx, const float *depth, const void *mask, int mask_dtype, int H, int W, int mem,
                           pedp_mask_depth_record *out);
 
+/* ---------------------------------------------------------------- 3x3 convolution of the networks' residual blocks
+ * The contract is DESIGN.md s4.12: stride 1, padding 1, NHWC float16 in and out, float32 accumulation in a fixed order
+ * (two calls give the same bits), device memory only, on the context's stream.  Cin and Cout are multiples of 32 up to
+ * 512 (PEDP_ERR_BAD_ARG otherwise); N, H, W >= 1. */
+typedef struct pedp_conv3x3_params {
+    int32_t N, H, W;         /* x is N x H x W x Cin, dense */
+    int32_t Cin, Cout;
+    int32_t y_ld, y_c0;      /* y[pixel * y_ld + y_c0 + co]: the destination's channel stride (>= y_c0 + Cout) and offset */
+    int32_t res_ld, res_c0;  /* the same for the residual (ignored when it is null) */
+    int32_t relu;            /* 0: identity */
+} pedp_conv3x3_params;
+
+/* Replaces the fold of `bn(conv(x))` in eval mode: with s = gamma / sqrt(var + eps) in float32, w_packed[co][tap][ci] =
+ * float16(w[co][ci][tap] * s[co]) (Cout x 9 x Cin, tap = 3 * ky + kx) and bias[co] = (b[co] - mean[co]) * s[co] + beta[co].
+ * w is the Conv2d weight Cout x Cin x 3 x 3 float32, b its bias or null (zeros); gamma, beta, mean, var are the
+ * BatchNorm2d's weight, bias, running_mean and running_var, or all null for a plain convolution (s = 1, bias = b). */
+int pedp_conv3x3_pack(pedp_ctx_t ctx, int Cin, int Cout, const float *w, const float *b, const float *gamma, const float *beta,
+                      const float *mean, const float *var, float eps, void *w_packed, float *bias);
+
+/* Replaces `relu(bn(F.conv2d(x, w, b, stride=1, padding=1)) + residual)` (ResnetBasicBlock.forward, network_modules.py:94-111)
+ * on channels-last float16 tensors: y = act(conv(x, w_packed) + bias [+ residual]).  x, w_packed and bias 16-byte
+ * aligned, y and residual 8-byte aligned; residual may be y itself (each element is read by the lane that then writes it),
+ * x may not. */
+int pedp_conv3x3_f16(pedp_ctx_t ctx, const pedp_conv3x3_params *prm, const void *x, const void *w_packed, const float *bias,
+                     const void *residual, void *y);
+
 /* ---------------------------------------------------------------- cluster_poses
  * Replaces mycpp.cluster_poses (mycpp/src/app/pybind_api.cpp:24-68; caller
  * estimater.py:118).  Host only.  poses: n x 16 float32 row-major, syms: s x 16.

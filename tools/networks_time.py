@@ -1,0 +1,310 @@
+"""Times of the refine and score networks on cuda:0 -> profiles/networks_time.json (or the path given).
+
+    layers      per block-convolution shape of a 252-pair forward at 160 x 160 (128 channels at 40 x 40 for 504 images, 256
+                at 40 x 40 for 252, 512 at 20 x 20 for 252): conv.conv3x3 against F.conv2d on the same channels-last float16
+                tensors (convolution and bias alone), and the whole fused step (norm folded, identity add, ReLU) against
+                torch's conv + BatchNorm + add + ReLU; the two taking turns in one loop after a warm-up, HIP events on a
+                side stream.  networks._AUTO is read off the first pair.
+    forward     one refiner forward and one scorer forward at 252 pairs of 160 x 160 under float16 autocast, backend
+                'torch' against 'hip' (and 'auto'), taking turns in one loop after a warm-up
+    first       the first forward's wall time in a fresh process, per backend (torch's convolution library chooses its
+                kernels then; the packed weights are built then)
+    estimator   register (252 hypotheses, 5 iterations) and track_one (2 iterations) at 576 x 640 around the real
+                architectures, as tools/estimator_time.py times them around its stand-ins
+
+Every step is a child process under its own time limit; the first one that fails ends the run.  Weights are the modules'
+random initial values (use_BN on): times do not depend on them.  Kernel times per forward come from a run of its own:
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d TRACE -- python tools/networks_time.py --step traced
+    python tools/networks_time.py --summarize TRACE profiles/networks_kernel_stats.csv"""
+import collections
+import csv
+import glob
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PAIRS, CROP = 252, 160
+SHAPES = [(2 * PAIRS, 40, 40, 128), (PAIRS, 40, 40, 256), (PAIRS, 20, 20, 512)]
+PEAK_F16_TFLOPS = 2500.0   # dense float16 MFMA peak of the MI355X
+STEPS = [("layers", 300), ("forward", 420), ("first torch", 300), ("first hip", 300), ("estimator", 420)]
+CFG = {"use_BN": True, "c_in": 6, "rot_rep": "axis_angle", "input_resize": (CROP, CROP), "trans_normalizer": [0.02, 0.02, 0.05],
+       "rot_normalizer": 0.35}
+
+
+def _stats(ms):
+    import numpy as np
+
+    return {"mean_ms": float(np.mean(ms)), "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms)), "reps": len(ms)}
+
+
+def _event_ms(fns, reps, warm=3):
+    """Milliseconds of each function by HIP events on a side stream, the functions taking turns within one loop."""
+    import torch
+
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    t = [[] for _ in fns]
+    with torch.cuda.stream(s):
+        for _ in range(warm):
+            for f in fns:
+                f()
+        for _ in range(reps):
+            for k, f in enumerate(fns):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                f()
+                b.record()
+                b.synchronize()
+                t[k].append(a.elapsed_time(b))
+    s.synchronize()
+    return [_stats(x) for x in t]
+
+
+def layers():
+    import torch
+    import torch.nn.functional as F
+    from pedp_hip.conv import conv3x3, pack_conv3x3
+
+    out = {}
+    for n, h, w, c in SHAPES:
+        conv = torch.nn.Conv2d(c, c, 3, 1, 1).cuda()
+        bn = torch.nn.BatchNorm2d(c).cuda().eval()
+        with torch.no_grad():
+            bn.running_var.uniform_(1.0, 1.25)
+            bn.running_mean.normal_(0, 0.1)
+        plain, folded = pack_conv3x3(conv), pack_conv3x3(conv, bn)
+        x = torch.randn((n, h, w, c), device="cuda").half()
+        res = torch.randn((n, h, w, c), device="cuda").half()
+        y = torch.empty_like(x)
+        xv, rv = x.permute(0, 3, 1, 2), res.permute(0, 3, 1, 2)          # the same memory as NCHW channels-last views
+        w16 = conv.weight.detach().half().contiguous(memory_format=torch.channels_last)
+        b16 = conv.bias.detach().half()
+        bnh = torch.nn.BatchNorm2d(c).cuda().eval().half()
+
+        def torch_step():
+            return torch.relu_(bnh(F.conv2d(xv, w16, b16, 1, 1)).add_(rv))
+
+        with torch.inference_mode():
+            k_conv, t_conv, k_step, t_step = _event_ms(
+                [lambda: conv3x3(x, plain, relu=False, out=y), lambda: F.conv2d(xv, w16, b16, 1, 1),
+                 lambda: conv3x3(x, folded, residual=res, relu=True, out=y), torch_step], 20)
+        flop = 2.0 * n * h * w * c * 9 * c
+        tf = flop / (k_conv["mean_ms"] * 1e-3) / 1e12
+        out[f"{c}ch_{h}x{w}_x{n}"] = {
+            "gflop": flop / 1e9, "kernel_conv": k_conv, "torch_conv": t_conv, "kernel_fused_step": k_step,
+            "torch_conv_bn_add_relu": t_step, "kernel_tflops": tf, "kernel_fraction_of_f16_peak": tf / PEAK_F16_TFLOPS,
+            "torch_tflops": flop / (t_conv["mean_ms"] * 1e-3) / 1e12,
+            "kernel_not_slower": bool(k_conv["mean_ms"] <= t_conv["mean_ms"])}
+    return out
+
+
+def _nets(backend):
+    from pedp_hip import networks
+
+    return networks.RefineNet(CFG, backend=backend).cuda().eval(), networks.ScoreNetMultiPair(CFG, backend=backend).cuda().eval()
+
+
+def _forward_fns(rn, sn, A, B):
+    import torch
+
+    def refine():
+        with torch.inference_mode(), torch.autocast("cuda"):
+            return rn(A, B)["trans"]
+
+    def score():
+        with torch.inference_mode(), torch.autocast("cuda"):
+            return sn(A, B, L=len(A))["score_logit"]
+
+    return refine, score
+
+
+def _inputs():
+    import torch
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+    return (torch.randn((PAIRS, 6, CROP, CROP), device="cuda", generator=g),
+            torch.randn((PAIRS, 6, CROP, CROP), device="cuda", generator=g))
+
+
+def forward():
+    A, B = _inputs()
+    rn, sn = _nets("torch")
+    refine, score = _forward_fns(rn, sn, A, B)
+
+    def with_backend(net, backend, fn):
+        def run():
+            net.set_backend(backend)
+            return fn()
+        return run
+
+    out = {}
+    for name, net, fn in (("refiner", rn, refine), ("scorer", sn, score)):
+        t, h, a = _event_ms([with_backend(net, b, fn) for b in ("torch", "hip", "auto")], 10, warm=2)
+        out[name] = {"torch": t, "hip": h, "auto": a, "hip_over_torch": h["mean_ms"] / t["mean_ms"]}
+    return out
+
+
+def first(backend):
+    import torch
+
+    A, B = _inputs()
+    rn, sn = _nets(backend)
+    out = {}
+    for name, fn in zip(("refiner", "scorer"), _forward_fns(rn, sn, A, B)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out[name] = {"first_forward_ms": (t1 - t0) * 1e3, "second_forward_ms": (time.perf_counter() - t1) * 1e3}
+    return out
+
+
+def _estimator(backend, H=576, W=640):
+    import numpy as np
+    import torch
+    from pedp_hip import synth
+    from pedp_hip.compat import TriangleMesh, make_mesh_tensors, nvdiffrast_render
+    from pedp_hip.estimator import FoundationPose, PoseRefinePredictor, ScorePredictor
+
+    v, t, n = synth.bumpy_torus(60, 40)
+    v = v * 0.0008
+    mesh = TriangleMesh(v, t)
+    mesh.vertex_normals = np.asarray(n, np.float64)
+    K = np.array([[W * 0.9, 0, W / 2 - 0.5], [0, W * 0.9, H / 2 - 0.5], [0, 0, 1]])
+    rn, sn = _nets(backend)
+    est = FoundationPose(v, mesh.vertex_normals, mesh=mesh, refiner=PoseRefinePredictor(rn, CFG), scorer=ScorePredictor(sn, CFG))
+    T = np.eye(4, dtype=np.float32)
+    T[:3, :3] = synth.rot_x(0.4)[:3, :3] @ synth.rot_z(0.3)[:3, :3]
+    T[:3, 3] = [0.01, -0.01, 0.5]
+    color, depth, _ = nvdiffrast_render(K=K, H=H, W=W, ob_in_cams=torch.as_tensor(T[None], device="cuda"),
+                                        mesh_tensors=make_mesh_tensors(mesh))
+    rgb = (color[0] * 255).clamp(0, 255).to(torch.uint8).cpu().numpy()
+    d = depth[0].cpu().numpy()
+    mask = d > 0
+    rng = np.random.default_rng(0)
+    d = (d + rng.normal(0, 0.002, d.shape).astype(np.float32) * mask + 1.2 * ~mask).astype(np.float32)
+    return est, K, rgb, d, mask
+
+
+def _wall_ms(f, reps, warm):
+    import torch
+
+    for _ in range(warm):
+        f()
+    t = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return _stats(t)
+
+
+def estimator():
+    out = {}
+    for backend in ("torch", "auto"):
+        est, K, rgb, depth, mask = _estimator(backend)
+        out[backend] = {
+            "register_5_iterations": _wall_ms(lambda: est.register(K=K, rgb=rgb, depth=depth, ob_mask=mask, iteration=5), 3, 1),
+            "track_one_2_iterations": _wall_ms(lambda: est.track_one(rgb=rgb, depth=depth, K=K, iteration=2), 10, 2)}
+    return out
+
+
+def traced():
+    import torch
+
+    A, B = _inputs()
+    rn, sn = _nets("hip")
+    refine, score = _forward_fns(rn, sn, A, B)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            refine(), score()
+        s.synchronize()
+        torch.empty(1, dtype=torch.int16, device="cuda").fill_(1)      # marker: the trace is cut here
+        s.synchronize()
+        refine()
+        s.synchronize()
+        torch.empty(1, dtype=torch.int16, device="cuda").fill_(2)
+        s.synchronize()
+        score()
+        s.synchronize()
+        torch.empty(1, dtype=torch.int16, device="cuda").fill_(3)
+        s.synchronize()
+
+
+def summarize(trace_dir, out_csv):
+    """Per phase of the traced run (one fused refiner forward, one fused scorer forward): every kernel's launches and time."""
+    paths = sorted(glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True))
+    kernels = sorted(csv.DictReader(open(paths[-1])), key=lambda r: int(r["Start_Timestamp"]))
+    is_marker = lambda r: "short" in r["Kernel_Name"] and "Fill" in r["Kernel_Name"]  # noqa: E731
+    cuts = [int(r["Start_Timestamp"]) for r in kernels if is_marker(r)]
+    phases = ["warm-up", "refiner forward (hip)", "scorer forward (hip)", "end"]
+    if len(cuts) != 3:
+        raise SystemExit(f"expected 3 marker launches, found {len(cuts)}")
+    groups = collections.defaultdict(list)
+    for r in kernels:
+        if is_marker(r):
+            continue
+        name = re.sub(r"^void |\(anonymous namespace\)::", "", r["Kernel_Name"]).split("(")[0]
+        groups[(phases[sum(int(r["Start_Timestamp"]) >= c for c in cuts)], name[:90])].append(
+            int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+    with open(out_csv, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["phase", "name", "calls", "total_ns", "mean_ns"])
+        for p in phases[1:-1]:
+            rows = [(k[1], d) for k, d in groups.items() if k[0] == p]
+            for name, d in sorted(rows, key=lambda kv: -sum(kv[1])):
+                w.writerow([p, name, len(d), sum(d), int(sum(d) / len(d))])
+            w.writerow([p, "total", sum(len(d) for _, d in rows), sum(sum(d) for _, d in rows), ""])
+    print(open(out_csv).read())
+
+
+def main(out_path):
+    res = {"pairs": PAIRS, "crop": CROP, "peak_f16_tflops": PEAK_F16_TFLOPS}
+    for step, limit in STEPS:
+        t0 = time.perf_counter()
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", *step.split()], capture_output=True, text=True,
+                               timeout=limit)
+        except subprocess.TimeoutExpired:
+            print(f"step {step!r} ran past {limit} s: stopping", flush=True)
+            res[step] = {"error": f"time limit of {limit} s"}
+            break
+        if p.returncode != 0:
+            print(f"step {step!r} failed with exit status {p.returncode}: stopping\n{p.stdout[-2000:]}\n{p.stderr[-4000:]}", flush=True)
+            res[step] = {"error": f"exit status {p.returncode}"}
+            break
+        res[step] = json.loads(p.stdout.strip().splitlines()[-1])
+        print(f"step {step!r}: {time.perf_counter() - t0:.1f} s", flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return 0 if all("error" not in v for v in res.values() if isinstance(v, dict)) else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--summarize":
+        summarize(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) > 2 and sys.argv[1] == "--step":
+        if sys.argv[2] == "traced":
+            traced()
+        else:
+            import torch
+
+            res = {"layers": layers, "forward": forward, "estimator": estimator}.get(sys.argv[2], lambda: first(sys.argv[3]))()
+            if sys.argv[2] == "layers":
+                res["device"] = torch.cuda.get_device_name(0)
+            print(json.dumps(res))
+    else:
+        sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "networks_time.json")))
