@@ -51,6 +51,8 @@ def up_to_date(out):
         return False
     t = os.path.getmtime(out)
     deps = [os.path.join(CSRC, s) for s in list(SOURCES) + HEADERS] + [os.path.abspath(__file__)]
+    # every header under csrc/ (pedp_icp.hip's kernels live in csrc/icp/*.h)
+    deps += [os.path.join(d, f) for d, _, fs in os.walk(CSRC) for f in fs if f.endswith(".h")]
     return all(os.path.getmtime(d) <= t for d in deps)
 
 

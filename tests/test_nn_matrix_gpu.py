@@ -2,7 +2,7 @@
 d^2 < r^2, lowest index on ties): geometries, sizes at chunk / tile / mask-word / list boundaries, radii on both
 sides of the qt switch, and every path the library picks between.
 
-Paths (pedp_icp.hip, icp_job_setup and icp_unit_size):
+Paths (pedp_icp.hip, icp_job_setup and icp_unit_size; BK_WCAP: icp/fused_close.h):
   fused      qt = 1: r^2 < diag^2 / 16 and Nt <= 524288 (BK_WCAP mask words of 1024 rows), not exhaustive;
   segmented  qt = 1: the same radius rule, a larger target;
   dense      qt = 4 (bf16 sweep): r^2 >= diag^2 / 16, or pedp_icp_configure(exhaustive).
