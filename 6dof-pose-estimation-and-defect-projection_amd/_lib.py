@@ -153,6 +153,7 @@ PROTOTYPES = {
     "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "pedp_conv3x3_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_mha_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
 }
@@ -342,6 +343,12 @@ class Conv3x3Params(C.Structure):
     """pedp_conv3x3_params (include/pedp.h)."""
     _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
                 ("y_ld", C.c_int32), ("y_c0", C.c_int32), ("res_ld", C.c_int32), ("res_c0", C.c_int32), ("relu", C.c_int32)]
+
+
+class MhaParams(C.Structure):
+    """pedp_mha_params (include/pedp.h)."""
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("q_ld", C.c_int32),
+                ("k_ld", C.c_int32), ("v_ld", C.c_int32), ("o_ld", C.c_int32), ("scale", C.c_float)]
 
 
 TRANS_TRACKNET, TRANS_RAW = 0, 1

@@ -14,15 +14,22 @@ conv.conv3x3 on channels-last float16 buffers kept per batch size, BatchNorm fol
 on first use and dropped by load_state_dict, .to() and .train().  Everything else (the stride-2 convolutions, the
 heads), and every other case (training, CPU, float32 / float64, backend 'torch'), is plain torch.  Weights changed in
 place after the first fused forward are not seen: call `drop_packed()`.
+
+The heads.  With heads='hip', under the same conditions (eval, GPU, float16 autocast), the attention of
+the refiner's two encoder layers and of the scorer's `att` and `att_cross` runs through attention.self_attention: torch's
+two projection GEMMs around the fused kernel, and no S x S weights are formed.  The default is heads='torch', the stock
+modules; in every other case they run whatever `heads` says.
 """
 import math
 
 import torch
 import torch.nn as nn
 
+from . import attention as _attn
 from . import conv as _conv
 
 _BACKENDS = ("auto", "hip", "torch")
+_HEADS = ("torch", "hip")
 
 # backend 'auto': which path a block convolution of this many channels takes -- the kernel where tools/networks_time.py
 # finds it not slower than F.conv2d on the same channels-last float16 tensors, torch otherwise (DESIGN.md s4.12).
@@ -125,10 +132,11 @@ class _PairNet(nn.Module):
 
     _enc_names = ("", "")
 
-    def _init_backend(self, backend):
+    def _init_backend(self, backend, heads="torch"):
         self._packed = {}     # id(conv) -> PackedConv3x3 | None (None: a layer the kernel does not take, kept on torch)
         self._buffers_nhwc = {}
         self.set_backend(backend)
+        self.set_heads(heads)
 
     def set_backend(self, backend):
         """'hip': every block convolution through the kernel; 'torch': none; 'auto': per layer by the measured table."""
@@ -136,6 +144,17 @@ class _PairNet(nn.Module):
             raise ValueError(f"backend must be one of {_BACKENDS}, got {backend!r}")
         self.backend = backend
         return self
+
+    def set_heads(self, heads):
+        """'hip': the heads' attention through attention.self_attention (eval, GPU, float16 autocast); 'torch': the stock
+        modules."""
+        if heads not in _HEADS:
+            raise ValueError(f"heads must be one of {_HEADS}, got {heads!r}")
+        self.heads = heads
+        return self
+
+    def _heads_fused(self, x):
+        return self.heads == "hip" and not self.training and x.is_cuda and _fp16_autocast()
 
     def drop_packed(self):
         self._packed = {}
@@ -248,7 +267,7 @@ class RefineNet(_PairNet):
 
     _enc_names = ("encodeA", "encodeAB")
 
-    def __init__(self, cfg=None, c_in=None, n_view=1, backend="auto"):
+    def __init__(self, cfg=None, c_in=None, n_view=1, backend="auto", heads="torch"):
         super().__init__()
         self.cfg = cfg
         norm = bool(_get(cfg, "use_BN", False))
@@ -263,10 +282,14 @@ class RefineNet(_PairNet):
                                         nn.Linear(512, 3))
         self.rot_head = nn.Sequential(nn.TransformerEncoderLayer(d_model=512, nhead=4, dim_feedforward=512, batch_first=True),
                                       nn.Linear(512, 3 if rot_rep == "axis_angle" else 6))
-        self._init_backend(backend)
+        self._init_backend(backend, heads)
 
     def forward(self, A, B):
         ab = self.pos_embed(self.encode(A, B))
+        if self._heads_fused(ab):
+            trans = self.trans_head[1](_attn.encoder_layer(self.trans_head[0], ab))
+            rot = self.rot_head[1](_attn.encoder_layer(self.rot_head[0], ab))
+            return {"trans": trans.mean(dim=1), "rot": rot.mean(dim=1)}
         return {"trans": self.trans_head(ab).mean(dim=1), "rot": self.rot_head(ab).mean(dim=1)}
 
 
@@ -275,7 +298,7 @@ class ScoreNetMultiPair(_PairNet):
 
     _enc_names = ("encoderA", "encoderAB")
 
-    def __init__(self, cfg=None, c_in=None, backend="auto"):
+    def __init__(self, cfg=None, c_in=None, backend="auto", heads="torch"):
         super().__init__()
         self.cfg = cfg
         norm = bool(_get(cfg, "use_BN", False))
@@ -286,18 +309,23 @@ class ScoreNetMultiPair(_PairNet):
         self.att_cross = nn.MultiheadAttention(embed_dim=512, num_heads=4, bias=True, batch_first=True)
         self.pos_embed = _PositionTable(512, 400)
         self.linear = nn.Linear(512, 1)
-        self._init_backend(backend)
+        self._init_backend(backend, heads)
+
+    def _attend(self, mha, x):
+        if self._heads_fused(x):
+            return _attn.self_attention(mha, x)
+        return mha(x, x, x)[0]
 
     def extract_feat(self, A, B):
         """A, B: (B*L) x C x H x W -> one 512-vector per pair."""
         ab = self.pos_embed(self.encode(A, B))
-        ab, _ = self.att(ab, ab, ab)
+        ab = self._attend(self.att, ab)
         return ab.mean(dim=1).reshape(len(A), -1)
 
     def forward(self, A, B, L):
         bs = A.shape[0] // L
         x = self.extract_feat(A, B).reshape(bs, L, -1)
-        x, _ = self.att_cross(x, x, x)
+        x = self._attend(self.att_cross, x)
         return {"score_logit": self.linear(x).reshape(bs, L)}
 
 
@@ -311,12 +339,12 @@ def _load(net, path_or_state, device):
     return net.to(device).eval()
 
 
-def load_refiner(path_or_state, cfg, backend="auto", device="cuda"):
+def load_refiner(path_or_state, cfg, backend="auto", device="cuda", heads="torch"):
     """RefineNet(cfg) with a checkpoint (a path, a state dict, or {'model': state dict}) loaded strictly, on the GPU in
     eval mode: `PoseRefinePredictor(model=load_refiner(path, cfg), cfg=cfg)`."""
-    return _load(RefineNet(cfg, backend=backend), path_or_state, device)
+    return _load(RefineNet(cfg, backend=backend, heads=heads), path_or_state, device)
 
 
-def load_scorer(path_or_state, cfg, backend="auto", device="cuda"):
+def load_scorer(path_or_state, cfg, backend="auto", device="cuda", heads="torch"):
     """ScoreNetMultiPair(cfg) the same way: `ScorePredictor(model=load_scorer(path, cfg), cfg=cfg)`."""
-    return _load(ScoreNetMultiPair(cfg, backend=backend), path_or_state, device)
+    return _load(ScoreNetMultiPair(cfg, backend=backend, heads=heads), path_or_state, device)

@@ -695,6 +695,27 @@ int pedp_conv3x3_pack(pedp_ctx_t ctx, int Cin, int Cout, const float *w, const f
 int pedp_conv3x3_f16(pedp_ctx_t ctx, const pedp_conv3x3_params *prm, const void *x, const void *w_packed, const float *bias,
                      const void *residual, void *y);
 
+/* ---------------------------------------------------------------- multi-head attention core of the networks' heads
+ * The contract is DESIGN.md s4.13: O = softmax(scale * Q K^T) V per (batch, head) without an S x S matrix in memory; float16
+ * operands, float32 scores, running maximum and sum, the probabilities rounded to float16 for the product with V, float32
+ * accumulation, one rounding to float16 into o.  No mask, no dropout.  The summation order is fixed (no atomics, the key
+ * axis is not split across workgroups): two calls give the same bits.  Device memory only, on the context's stream, no
+ * host wait.  D = 128 is the only head dimension built (PEDP_ERR_BAD_ARG otherwise); B, H >= 1, 1 <= S <= 4096. */
+typedef struct pedp_mha_params {
+    int32_t B, S, H, D;              /* batch, tokens, heads, head dimension */
+    int32_t q_ld, k_ld, v_ld, o_ld;  /* elements from token s to token s + 1 of each operand (>= H * D, multiples of 8) */
+    float scale;                     /* of the scores before the softmax: 1 / sqrt(D) for nn.MultiheadAttention */
+} pedp_mha_params;
+
+/* Replaces the middle of `nn.MultiheadAttention.forward` / `F.multi_head_attention_forward` in eval mode between the two
+ * projections, i.e. `F.scaled_dot_product_attention(q, k, v)` on B x H x S x D views, or with need_weights=True (what
+ * score_network.py:77 and :88 call) `softmax(baddbmm(q, k^T))`, `bmm(p, v)` and the head-averaged B x S x S weights, which
+ * are not formed here.  Element (b, s, h, d) of an operand x is x[(b * S + s) * x_ld + h * D + d]: with q, k = q + E and
+ * v = q + 2E, E = H * D, and q_ld = k_ld = v_ld = 3E the operands are read in place from the packed in-projection output
+ * B x S x 3E; three separate tensors work the same way.  q, k, v and o are 16-byte aligned; o's bytes may not overlap an
+ * input's (from its first element to its last), PEDP_ERR_BAD_ARG otherwise.  Rows >= S of no operand are touched. */
+int pedp_mha_f16(pedp_ctx_t ctx, const pedp_mha_params *prm, const void *q, const void *k, const void *v, void *o);
+
 /* ---------------------------------------------------------------- cluster_poses
  * Replaces mycpp.cluster_poses (mycpp/src/app/pybind_api.cpp:24-68; caller
  * estimater.py:118).  Host only.  poses: n x 16 float32 row-major, syms: s x 16.

@@ -5,6 +5,12 @@
                 tensors (convolution and bias alone), and the whole fused step (norm folded, identity add, ReLU) against
                 torch's conv + BatchNorm + add + ReLU; the two taking turns in one loop after a warm-up, HIP events on a
                 side stream.  networks._AUTO is read off the first pair.
+    heads       the heads' attention at (B, S) = (252, 400) and (1, 252), 4 heads of 128, on gaussian float16 data:
+                attention.mha_core on the packed in-projection output against F.scaled_dot_product_attention on its
+                B x H x S x D views, and attention.self_attention against nn.MultiheadAttention as the scorer calls it
+                (need_weights=True) and with need_weights=False, under float16 autocast; then one refiner and one scorer
+                forward at 252 pairs per `heads` value (backend 'torch').  The variants take turns in one loop; median
+                and minimum are reported besides the mean.
     forward     one refiner forward and one scorer forward at 252 pairs of 160 x 160 under float16 autocast, backend
                 'torch' against 'hip' (and 'auto'), taking turns in one loop after a warm-up
     first       the first forward's wall time in a fresh process, per backend (torch's convolution library chooses its
@@ -12,7 +18,8 @@
     estimator   register (252 hypotheses, 5 iterations) and track_one (2 iterations) at 576 x 640 around the real
                 architectures, as tools/estimator_time.py times them around its stand-ins
 
-Every step is a child process under its own time limit; the first one that fails ends the run.  Weights are the modules'
+Every step is a child process under its own time limit; the first one that fails ends the run.  `--only a,b` runs the
+named steps alone and keeps the other steps' results of an existing file.  Weights are the modules'
 random initial values (use_BN on): times do not depend on them.  Kernel times per forward come from a run of its own:
 
     rocprofv3 --kernel-trace --stats --output-format csv -d TRACE -- python tools/networks_time.py --step traced
@@ -32,7 +39,7 @@ sys.path.insert(0, ROOT)
 PAIRS, CROP = 252, 160
 SHAPES = [(2 * PAIRS, 40, 40, 128), (PAIRS, 40, 40, 256), (PAIRS, 20, 20, 512)]
 PEAK_F16_TFLOPS = 2500.0   # dense float16 MFMA peak of the MI355X
-STEPS = [("layers", 300), ("forward", 420), ("first torch", 300), ("first hip", 300), ("estimator", 420)]
+STEPS = [("layers", 300), ("heads", 300), ("forward", 420), ("first torch", 300), ("first hip", 300), ("estimator", 420)]
 CFG = {"use_BN": True, "c_in": 6, "rot_rep": "axis_angle", "input_resize": (CROP, CROP), "trans_normalizer": [0.02, 0.02, 0.05],
        "rot_normalizer": 0.35}
 
@@ -40,7 +47,8 @@ CFG = {"use_BN": True, "c_in": 6, "rot_rep": "axis_angle", "input_resize": (CROP
 def _stats(ms):
     import numpy as np
 
-    return {"mean_ms": float(np.mean(ms)), "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms)), "reps": len(ms)}
+    return {"mean_ms": float(np.mean(ms)), "median_ms": float(np.median(ms)), "min_ms": float(np.min(ms)),
+            "max_ms": float(np.max(ms)), "reps": len(ms)}
 
 
 def _event_ms(fns, reps, warm=3):
@@ -101,6 +109,49 @@ def layers():
             "torch_conv_bn_add_relu": t_step, "kernel_tflops": tf, "kernel_fraction_of_f16_peak": tf / PEAK_F16_TFLOPS,
             "torch_tflops": flop / (t_conv["mean_ms"] * 1e-3) / 1e12,
             "kernel_not_slower": bool(k_conv["mean_ms"] <= t_conv["mean_ms"])}
+    return out
+
+
+def heads():
+    import torch
+    import torch.nn.functional as F
+    from pedp_hip.attention import mha_core, self_attention
+
+    H, D = 4, 128
+    E = H * D
+    out = {"core": {}, "module": {}}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for B, S in ((PAIRS, 400), (1, PAIRS)):
+        qkv = torch.randn((B, S, 3 * E), device="cuda", generator=g).half()
+        q, k, v = (qkv[..., i * E:(i + 1) * E].reshape(B, S, H, D).transpose(1, 2) for i in range(3))
+        o = torch.empty((B, S, E), dtype=torch.float16, device="cuda")
+        mha = torch.nn.MultiheadAttention(E, H, bias=True, batch_first=True).cuda().eval()
+        x = torch.randn((B, S, E), device="cuda", generator=g)
+        with torch.inference_mode(), torch.autocast("cuda"):
+            k_core, t_core = _event_ms([lambda: mha_core(qkv, H, out=o), lambda: F.scaled_dot_product_attention(q, k, v)], 30)
+            k_mod, t_weights, t_plain = _event_ms([lambda: self_attention(mha, x), lambda: mha(x, x, x)[0],
+                                                   lambda: mha(x, x, x, need_weights=False)[0]], 30)
+        flop = 4.0 * B * H * S * S * D
+        tf = flop / (k_core["median_ms"] * 1e-3) / 1e12
+        out["core"][f"{B}x{S}"] = {"gflop": flop / 1e9, "mha_core": k_core, "torch_sdpa": t_core, "kernel_tflops": tf,
+                                   "kernel_fraction_of_f16_peak": tf / PEAK_F16_TFLOPS,
+                                   "kernel_over_sdpa": k_core["median_ms"] / t_core["median_ms"]}
+        out["module"][f"{B}x{S}"] = {"self_attention": k_mod, "torch_need_weights": t_weights, "torch_no_weights": t_plain,
+                                     "kernel_over_need_weights": k_mod["median_ms"] / t_weights["median_ms"]}
+    A, Bi = _inputs()
+    rn, sn = _nets("torch")
+    refine, score = _forward_fns(rn, sn, A, Bi)
+
+    def with_heads(net, value, fn):
+        def run():
+            net.set_heads(value)
+            return fn()
+        return run
+
+    out["forward"] = {}
+    for name, net, fn in (("refiner", rn, refine), ("scorer", sn, score)):
+        t, h = _event_ms([with_heads(net, v, fn) for v in ("torch", "hip")], 10, warm=2)
+        out["forward"][name] = {"torch": t, "hip": h, "hip_over_torch": h["median_ms"] / t["median_ms"]}
     return out
 
 
@@ -269,9 +320,14 @@ def summarize(trace_dir, out_csv):
     print(open(out_csv).read())
 
 
-def main(out_path):
+def main(out_path, only=None):
+    """`only`: step names to run; an existing result file's other steps are kept."""
     res = {"pairs": PAIRS, "crop": CROP, "peak_f16_tflops": PEAK_F16_TFLOPS}
+    if only and os.path.exists(out_path):
+        res.update(json.load(open(out_path)))
     for step, limit in STEPS:
+        if only and step not in only:
+            continue
         t0 = time.perf_counter()
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", *step.split()], capture_output=True, text=True,
@@ -302,9 +358,14 @@ if __name__ == "__main__":
         else:
             import torch
 
-            res = {"layers": layers, "forward": forward, "estimator": estimator}.get(sys.argv[2], lambda: first(sys.argv[3]))()
-            if sys.argv[2] == "layers":
+            res = {"layers": layers, "heads": heads, "forward": forward, "estimator": estimator}.get(sys.argv[2], lambda: first(sys.argv[3]))()
+            if sys.argv[2] in ("layers", "heads"):
                 res["device"] = torch.cuda.get_device_name(0)
             print(json.dumps(res))
     else:
-        sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "networks_time.json")))
+        args = sys.argv[1:]
+        only = None
+        if "--only" in args:                                   # --only heads,layers
+            i = args.index("--only")
+            only, args = args[i + 1].split(","), args[:i] + args[i + 2:]
+        sys.exit(main(args[0] if args else os.path.join(ROOT, "profiles", "networks_time.json"), only))
