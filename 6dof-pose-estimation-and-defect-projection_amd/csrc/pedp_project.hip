@@ -23,11 +23,13 @@ struct Cam {
     int width;
 };
 
-// MODE 0: element i is pixel i of the heat map, kept when heatmap[i] > threshold
+// MODE 0: element i is pixel i of the heat map, kept when heatmap[i] > threshold in the map's own type: numpy compares
+//         a float32 map with a Python number in float32 (the number rounded to it), so an entry equal to float32(0.3)
+//         is not above 0.3 although its widened value is
 // MODE 1: element i is selected ray i, kept when its t_hit is finite (t != inf)
 template <int MODE, typename H>
 __device__ __forceinline__ bool keep(const H *heat, const float *t, double threshold, int64_t i) {
-    if (MODE == 0) return (double)heat[i] > threshold;
+    if (MODE == 0) return heat[i] > (H)threshold;
     return t[i] != __builtin_inff();
 }
 

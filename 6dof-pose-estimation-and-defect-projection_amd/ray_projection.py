@@ -29,7 +29,11 @@ def heatmap_to_points(heatmap, threshold=0.5):
 def compute_rays(points, intrinsic):
     """Unit viewing directions (float64) of the given pixels through a pinhole camera:
     normalise((x - cx) / fx, (y - cy) / fy, 1).  The reference loops in Python per pixel
-    (defect_projection.py:216-222); this is the same arithmetic on whole arrays."""
+    (defect_projection.py:216-222); this is the same arithmetic on whole arrays.  The convention for the length
+    is the reference's: np.linalg.norm of a vector is sqrt(dot(ray, ray)) with the dot product from BLAS, formed here
+    as a stack of 1 x 3 by 3 x 1 products, which numpy hands to the same routine.  So a direction equals the
+    reference's in every bit on one machine, and is within one float64 step of a result formed with another BLAS
+    (a sum in another order, or without a fused multiply-add, moves the length by a step at most)."""
     K = np.asarray(intrinsic.intrinsic_matrix, dtype=np.float64)
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     if len(points) == 0:
@@ -38,7 +42,7 @@ def compute_rays(points, intrinsic):
     py = np.array([p[1] for p in points], dtype=np.float64)
     intensities = np.array([p[2] for p in points])
     d = np.stack([(px - cx) / fx, (py - cy) / fy, np.ones_like(px)], axis=1)
-    d /= np.sqrt(np.einsum("ij,ij->i", d, d))[:, None]
+    d /= np.sqrt(np.matmul(d[:, None, :], d[:, :, None])).reshape(-1, 1)
     return d, intensities
 
 

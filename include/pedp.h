@@ -171,7 +171,9 @@ int pedp_project_heatmap(pedp_ctx_t ctx, pedp_mesh_t mesh, const pedp_pinhole *c
 /* The same with what the reference does to the hits right after (src/defect_projection.py:268-294
  * create_intersection_pcd; run.py:118, :200 `.transform(reader.color_to_depth)`), and with the heat map where and as
  * it is.  opts (NULL = the call above):
- *   heat_f32   the heat map is float32 (upcast exactly; every comparison and the intensities in float64)
+ *   heat_f32   the heat map is float32: compared with the threshold in float32, the threshold rounded to float32 (what
+ *              numpy's `heatmap > threshold` does with a Python number: an entry equal to float32(0.3) is not above
+ *              0.3); the intensities are its values widened exactly to float64
  *   heat_mem   PEDP_HOST / PEDP_DEVICE for the heat map alone (a detector's output already on the GPU, or a map
  *              kept resident between detections, run.py:66, :147), whatever `mem` says about the outputs
  *   jet_lut    256 x 3 float64 on the host: matplotlib's `jet` lookup table (pedp_hip.ray_projection builds it);

@@ -140,9 +140,11 @@ def project_heatmap(verts32, tris, heatmap, K, threshold=0.5, origin=(0, 0, 0), 
     (defect_projection.py:165-179, :196-223, :225-266) on whole arrays: np.where order, float64
     directions with the norm formed as sqrt((xn*xn + yn*yn) + 1), [o | d] cast to float32 for the
     sweep, t != inf filter, o + d * t in float64."""
-    h = np.asarray(heatmap, np.float64)
+    src = np.asarray(heatmap)
+    h = src.astype(np.float64)
     K = np.asarray(K, np.float64)
-    ys, xs = np.nonzero(h > threshold)
+    # in a float map's own type, as numpy compares it with a Python number (float32(0.3) is not above 0.3)
+    ys, xs = np.nonzero(src > (src.dtype.type(threshold) if src.dtype.kind == "f" else threshold))
     xn = (xs.astype(np.float64) - K[0, 2]) / K[0, 0]
     yn = (ys.astype(np.float64) - K[1, 2]) / K[1, 1]
     ln = np.sqrt((xn * xn + yn * yn) + 1.0)
