@@ -153,6 +153,9 @@ PROTOTYPES = {
     "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "pedp_conv3x3_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_conv2d_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "pedp_conv2d_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_mha_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
@@ -343,6 +346,17 @@ class Conv3x3Params(C.Structure):
     """pedp_conv3x3_params (include/pedp.h)."""
     _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
                 ("y_ld", C.c_int32), ("y_c0", C.c_int32), ("res_ld", C.c_int32), ("res_c0", C.c_int32), ("relu", C.c_int32)]
+
+
+NHWC, NCHW = 0, 1
+F16 = 2
+
+
+class Conv2dParams(C.Structure):
+    """pedp_conv2d_params (include/pedp.h)."""
+    _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
+                ("KH", C.c_int32), ("KW", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("layout", C.c_int32),
+                ("dtype", C.c_int32), ("N0", C.c_int32), ("y_ld", C.c_int32), ("y_c0", C.c_int32), ("relu", C.c_int32)]
 
 
 class MhaParams(C.Structure):

@@ -11,14 +11,20 @@ strict=True.  Weights stay the user's file.
 Two forwards.  In eval mode on a GPU under float16 autocast (how the predictors call a network with
 amp=True) and with backend 'hip' or 'auto', the twelve stride-1 3x3 convolutions of the residual blocks run through
 conv.conv3x3 on channels-last float16 buffers kept per batch size, BatchNorm folded into packed weights that are built
-on first use and dropped by load_state_dict, .to() and .train().  Everything else (the stride-2 convolutions, the
-heads), and every other case (training, CPU, float32 / float64, backend 'torch'), is plain torch.  Weights changed in
+on first use and dropped by load_state_dict, .to() and .train().  Everything else (the stride-2 convolutions unless
+strided='hip', the heads unless heads='hip'), and every other case (training, CPU, float32 / float64, backend 'torch'), is plain torch.  Weights changed in
 place after the first fused forward are not seen: call `drop_packed()`.
 
 The heads.  With heads='hip', under the same conditions (eval, GPU, float16 autocast), the attention of
 the refiner's two encoder layers and of the scorer's `att` and `att_cross` runs through attention.self_attention: torch's
 two projection GEMMs around the fused kernel, and no S x S weights are formed.  The default is heads='torch', the stock
 modules; in every other case they run whatever `heads` says.
+
+The stride-2 layers.  With strided='hip', under the same conditions, the three convolutions that halve
+the resolution run through conv.conv_stem and conv.conv_strided: the 7x7 stem reads A and B as they arrive (no cat, no
+NCHW intermediate, no conversion pass) and the forward is channels-last float16 on kept buffers from the crops to the
+tokens, whatever `backend` says about the block convolutions.  The tokens `encode` returns are then a view of a kept
+buffer, valid until the next forward of the same batch size.  The default is strided='torch'.
 """
 import math
 
@@ -30,6 +36,7 @@ from . import conv as _conv
 
 _BACKENDS = ("auto", "hip", "torch")
 _HEADS = ("torch", "hip")
+_STRIDED = ("torch", "hip")
 
 # backend 'auto': which path a block convolution of this many channels takes -- the kernel where tools/networks_time.py
 # finds it not slower than F.conv2d on the same channels-last float16 tensors, torch otherwise.
@@ -132,11 +139,13 @@ class _PairNet(nn.Module):
 
     _enc_names = ("", "")
 
-    def _init_backend(self, backend, heads="torch"):
-        self._packed = {}     # id(conv) -> PackedConv3x3 | None (None: a layer the kernel does not take, kept on torch)
+    def _init_backend(self, backend, heads="torch", strided="torch"):
+        # id(conv) -> PackedConv3x3 | PackedConv | None (None: a block layer the kernel does not take, kept on torch)
+        self._packed = {}
         self._buffers_nhwc = {}
         self.set_backend(backend)
         self.set_heads(heads)
+        self.set_strided(strided)
 
     def set_backend(self, backend):
         """'hip': every block convolution through the kernel; 'torch': none; 'auto': per layer by the measured table."""
@@ -151,6 +160,14 @@ class _PairNet(nn.Module):
         if heads not in _HEADS:
             raise ValueError(f"heads must be one of {_HEADS}, got {heads!r}")
         self.heads = heads
+        return self
+
+    def set_strided(self, strided):
+        """'hip': the three stride-2 convolutions through conv.conv_stem / conv.conv_strided (eval, GPU, float16
+        autocast); 'torch': the stock modules."""
+        if strided not in _STRIDED:
+            raise ValueError(f"strided must be one of {_STRIDED}, got {strided!r}")
+        self.strided = strided
         return self
 
     def _heads_fused(self, x):
@@ -180,8 +197,8 @@ class _PairNet(nn.Module):
         return self.backend == "hip" or (self.backend == "auto" and _AUTO.get(channels, "torch") == "hip")
 
     def _fused(self, A):
-        return (any(self._uses_kernel(c) for c in (128, 256, 512)) and not self.training and A.is_cuda
-                and _fp16_autocast())
+        return ((self.strided == "hip" or any(self._uses_kernel(c) for c in (128, 256, 512))) and not self.training
+                and A.is_cuda and _fp16_autocast())
 
     def encode(self, A, B):
         """The pair encoder's output as tokens, bs x (h/8 * w/8) x 512, before the position table."""
@@ -201,6 +218,14 @@ class _PairNet(nn.Module):
             self._packed[key] = _conv.pack_conv3x3(conv, bn) if _conv.supported(conv) else None
         return self._packed[key]
 
+    def _pack_strided(self, block):
+        """The packed form of a stride-2 _ConvNormReLU; a layer the kernels do not take raises (conv.pack_conv)."""
+        conv = block.net[0]
+        key = id(conv)
+        if key not in self._packed:
+            self._packed[key] = _conv.pack_conv(conv, block.net[1] if isinstance(block.net[1], nn.BatchNorm2d) else None)
+        return self._packed[key]
+
     def _conv(self, x, conv, bn, residual=None, out=None, out_c0=0):
         """One block convolution with its norm, optional identity add and ReLU: x, residual N x H x W x C float16 ->
         channels out_c0 ... of `out` (N x H x W x ld)."""
@@ -217,8 +242,10 @@ class _PairNet(nn.Module):
         dst.copy_(torch.relu(y))
         return dst
 
-    def _scratch(self, dev, bs, h, w):
-        key = (dev, bs, h, w)
+    def _scratch(self, dev, bs, h, w, strided_hw=None):
+        """The buffers of a forward of `bs` pairs at h x w after the shared encoder's two stride-2 layers; with
+        strided_hw = (h1, w1, h3, w3), the sizes after the stem and after the pair encoder's stride-2 layer, also theirs."""
+        key = (dev, bs, h, w, strided_hw)
         buf = self._buffers_nhwc.get(key)
         if buf is None:
             if len(self._buffers_nhwc) >= 4:     # a tracker alternates between a few batch sizes; do not hoard more
@@ -228,16 +255,30 @@ class _PairNet(nn.Module):
                     return torch.empty((n, hh, ww, c), dtype=torch.float16, device=dev)
                 buf = self._buffers_nhwc[key] = {"x": e(2 * bs, h, w, 128), "t": e(2 * bs, h, w, 128), "ab": e(bs, h, w, 256),
                                                  "t2": e(bs, h, w, 256)}
+                if strided_hw is not None:
+                    h1, w1, h3, w3 = strided_hw
+                    buf.update({"s": e(2 * bs, h1, w1, 64), "y": e(bs, h3, w3, 512), "t3": e(bs, h3, w3, 512)})
         return buf
 
     def _encode_fused(self, A, B):
         bs = len(A)
         enc_a, enc_ab = self._encoders()
-        x = enc_a[1](enc_a[0](torch.cat([A, B], dim=0)))                   # the two stride-2 convolutions: torch
-        h, w = int(x.shape[2]), int(x.shape[3])
-        buf = self._scratch(x.device, bs, h, w)
-        xa, t, ab, t2 = buf["x"], buf["t"], buf["ab"], buf["t2"]
-        xa.copy_(x.permute(0, 2, 3, 1))                                    # the one conversion to channels-last float16
+        hip = self.strided == "hip"
+        if hip:
+            if A.dtype != B.dtype or A.dtype not in (torch.float32, torch.float16):
+                A, B = A.half(), B.half()                                      # autocast's cast of any other dtype
+            h1, w1 = _conv.out_hw(A.shape[2], A.shape[3], enc_a[0].net[0])
+            h, w = _conv.out_hw(h1, w1, enc_a[1].net[0])
+            buf = self._scratch(A.device, bs, h, w, (h1, w1, *_conv.out_hw(h, w, enc_ab[2].net[0])))
+            xa, t, ab, t2 = buf["x"], buf["t"], buf["ab"], buf["t2"]
+            _conv.conv_stem(A.contiguous(), B.contiguous(), self._pack_strided(enc_a[0]), out=buf["s"])   # A and B as they are
+            _conv.conv_strided(buf["s"], self._pack_strided(enc_a[1]), out=xa)
+        else:
+            x = enc_a[1](enc_a[0](torch.cat([A, B], dim=0)))               # the two stride-2 convolutions: torch
+            h, w = int(x.shape[2]), int(x.shape[3])
+            buf = self._scratch(x.device, bs, h, w)
+            xa, t, ab, t2 = buf["x"], buf["t"], buf["ab"], buf["t2"]
+            xa.copy_(x.permute(0, 2, 3, 1))                                # the one conversion to channels-last float16
         (c1, n1), (c2, n2) = enc_a[2].pairs()
         self._conv(xa, c1, n1, out=t)
         self._conv(t, c2, n2, residual=xa, out=xa)
@@ -249,11 +290,15 @@ class _PairNet(nn.Module):
             (c1, n1), (c2, n2) = blk.pairs()
             self._conv(ab, c1, n1, out=t2)
             self._conv(t2, c2, n2, residual=ab, out=ab)
-        y = enc_ab[2](ab.permute(0, 3, 1, 2))                              # 256 -> 512, stride 2: torch, zero-copy view
-        y = y.permute(0, 2, 3, 1).contiguous()
-        if y.dtype != torch.float16:
-            y = y.half()
-        t3 = torch.empty_like(y)
+        if hip:
+            y, t3 = buf["y"], buf["t3"]
+            _conv.conv_strided(ab, self._pack_strided(enc_ab[2]), out=y)       # 256 -> 512, stride 2
+        else:
+            y = enc_ab[2](ab.permute(0, 3, 1, 2))                          # 256 -> 512, stride 2: torch, zero-copy view
+            y = y.permute(0, 2, 3, 1).contiguous()
+            if y.dtype != torch.float16:
+                y = y.half()
+            t3 = torch.empty_like(y)
         for blk in (enc_ab[3], enc_ab[4]):
             (c1, n1), (c2, n2) = blk.pairs()
             self._conv(y, c1, n1, out=t3)
@@ -267,7 +312,7 @@ class RefineNet(_PairNet):
 
     _enc_names = ("encodeA", "encodeAB")
 
-    def __init__(self, cfg=None, c_in=None, n_view=1, backend="auto", heads="torch"):
+    def __init__(self, cfg=None, c_in=None, n_view=1, backend="auto", heads="torch", strided="torch"):
         super().__init__()
         self.cfg = cfg
         norm = bool(_get(cfg, "use_BN", False))
@@ -282,7 +327,7 @@ class RefineNet(_PairNet):
                                         nn.Linear(512, 3))
         self.rot_head = nn.Sequential(nn.TransformerEncoderLayer(d_model=512, nhead=4, dim_feedforward=512, batch_first=True),
                                       nn.Linear(512, 3 if rot_rep == "axis_angle" else 6))
-        self._init_backend(backend, heads)
+        self._init_backend(backend, heads, strided)
 
     def forward(self, A, B):
         ab = self.pos_embed(self.encode(A, B))
@@ -298,7 +343,7 @@ class ScoreNetMultiPair(_PairNet):
 
     _enc_names = ("encoderA", "encoderAB")
 
-    def __init__(self, cfg=None, c_in=None, backend="auto", heads="torch"):
+    def __init__(self, cfg=None, c_in=None, backend="auto", heads="torch", strided="torch"):
         super().__init__()
         self.cfg = cfg
         norm = bool(_get(cfg, "use_BN", False))
@@ -309,7 +354,7 @@ class ScoreNetMultiPair(_PairNet):
         self.att_cross = nn.MultiheadAttention(embed_dim=512, num_heads=4, bias=True, batch_first=True)
         self.pos_embed = _PositionTable(512, 400)
         self.linear = nn.Linear(512, 1)
-        self._init_backend(backend, heads)
+        self._init_backend(backend, heads, strided)
 
     def _attend(self, mha, x):
         if self._heads_fused(x):
@@ -339,12 +384,12 @@ def _load(net, path_or_state, device):
     return net.to(device).eval()
 
 
-def load_refiner(path_or_state, cfg, backend="auto", device="cuda", heads="torch"):
+def load_refiner(path_or_state, cfg, backend="auto", device="cuda", heads="torch", strided="torch"):
     """RefineNet(cfg) with a checkpoint (a path, a state dict, or {'model': state dict}) loaded strictly, on the GPU in
     eval mode: `PoseRefinePredictor(model=load_refiner(path, cfg), cfg=cfg)`."""
-    return _load(RefineNet(cfg, backend=backend, heads=heads), path_or_state, device)
+    return _load(RefineNet(cfg, backend=backend, heads=heads, strided=strided), path_or_state, device)
 
 
-def load_scorer(path_or_state, cfg, backend="auto", device="cuda", heads="torch"):
+def load_scorer(path_or_state, cfg, backend="auto", device="cuda", heads="torch", strided="torch"):
     """ScoreNetMultiPair(cfg) the same way: `ScorePredictor(model=load_scorer(path, cfg), cfg=cfg)`."""
-    return _load(ScoreNetMultiPair(cfg, backend=backend, heads=heads), path_or_state, device)
+    return _load(ScoreNetMultiPair(cfg, backend=backend, heads=heads, strided=strided), path_or_state, device)

@@ -697,6 +697,40 @@ int pedp_conv3x3_pack(pedp_ctx_t ctx, int Cin, int Cout, const float *w, const f
 int pedp_conv3x3_f16(pedp_ctx_t ctx, const pedp_conv3x3_params *prm, const void *x, const void *w_packed, const float *bias,
                      const void *residual, void *y);
 
+/* ---------------------------------------------------------------- the encoders' stride-2 convolutions
+ * The other three convolutions of an encoder, with the arithmetic of the block kernel: float16 products,
+ * float32 accumulation in an order fixed by the shape, float32 bias with the BatchNorm folded in, optional ReLU, one
+ * rounding to float16 into NHWC y.  Device memory only, on the context's stream.  Two forms are built, everything else is
+ * PEDP_ERR_BAD_ARG:
+ *   3 x 3, stride 2, padding 1   x N x H x W x Cin float16 (PEDP_NHWC, PEDP_F16), Cin and Cout multiples of 32 up to 512
+ *   7 x 7, stride 2, padding 3   x N x Cin x H x W float32 or float16 (PEDP_NCHW), Cin 1 .. 8, Cout a multiple of 32 up
+ *                                to 512; float32 input is rounded to float16 (to nearest even) before the products
+ * y is N x OH x OW with OH = (H + 2 * pad - KH) / stride + 1 (floor), OW likewise. */
+enum { PEDP_NHWC = 0, PEDP_NCHW = 1 };
+enum { PEDP_F16 = 2 };       /* with PEDP_U8 and PEDP_F32 above */
+typedef struct pedp_conv2d_params {
+    int32_t N, H, W;         /* of the input */
+    int32_t Cin, Cout;
+    int32_t KH, KW, stride, pad;
+    int32_t layout, dtype;   /* of the input: PEDP_NHWC / PEDP_NCHW, PEDP_F16 / PEDP_F32 */
+    int32_t N0;              /* images 0 .. N0 come from x, N0 .. N from x2 (7 x 7 only; N0 = N or 0 when x2 is null) */
+    int32_t y_ld, y_c0;      /* y[pixel * y_ld + y_c0 + co], as in pedp_conv3x3_params */
+    int32_t relu;            /* 0: identity */
+} pedp_conv2d_params;
+
+/* pedp_conv3x3_pack for a KH x KW kernel (3 x 3 or 7 x 7): the same float32 fold of `ConvBNReLU`'s BatchNorm2d
+ * (network_modules.py:37-50) into w Cout x Cin x KH x KW.  3 x 3: w_packed is Cout x 9 x Cin as above.  7 x 7 (Cin <= 8):
+ * w_packed is Cout x 416 float16, [co][8 * (7 * ky + kx) + ci], zero for ci >= Cin and past tap 48. */
+int pedp_conv2d_pack(pedp_ctx_t ctx, int Cin, int Cout, int KH, int KW, const float *w, const float *b, const float *gamma,
+                     const float *beta, const float *mean, const float *var, float eps, void *w_packed, float *bias);
+
+/* Replaces `ConvBNReLU.forward` (network_modules.py:37-50: `relu(bn(F.conv2d(x, w, b, stride=2, padding=(k - 1) // 2)))`)
+ * of the encoders' three stride-2 layers under float16 autocast, and for the 7 x 7 one the `torch.cat([A, B], 0)` in front
+ * of it (refine_network.py:80, score_network.py:66): x2, when not null, holds images N0 .. N.  x (3 x 3), w_packed and bias
+ * 16-byte aligned, y 8-byte aligned; y may not overlap an input.  residual must be null: the stride-2 layers add none. */
+int pedp_conv2d_f16(pedp_ctx_t ctx, const pedp_conv2d_params *prm, const void *x, const void *x2, const void *w_packed,
+                    const float *bias, const void *residual, void *y);
+
 /* ---------------------------------------------------------------- multi-head attention core of the networks' heads
  * The contract is DESIGN.md s4.13: O = softmax(scale * Q K^T) V per (batch, head) without an S x S matrix in memory; float16
  * operands, float32 scores, running maximum and sum, the probabilities rounded to float16 for the product with V, float32

@@ -15,6 +15,14 @@
                 'torch' against 'hip' (and 'auto'), taking turns in one loop after a warm-up
     first       the first forward's wall time in a fresh process, per backend (torch's convolution library chooses its
                 kernels then; the packed weights are built then)
+    strided     the three stride-2 layers of a 252-pair forward (the 7x7 stem on 2 x 252 float32 crops of 6 x 160 x 160, 3x3
+                64 -> 128 on 504 x 80 x 80, 3x3 256 -> 512 on 252 x 40 x 40): conv.conv_stem / conv.conv_strided against
+                F.conv2d on channels-last float16 tensors (convolution and bias alone; for the stem also torch's whole
+                entry: cat, autocast's cast and the convolution from the float32 crops), then one refiner and one scorer
+                forward at 252 pairs with strided 'torch' against 'hip' (backend 'hip'), taking turns in one loop
+    strided_first   the first forward's wall time in a fresh process per `strided` value (backend 'hip'): with 'hip' no
+                convolution of the encoders goes to torch's convolution library, whose search for kernels the first
+                forward otherwise pays
     estimator   register (252 hypotheses, 5 iterations) and track_one (2 iterations) at 576 x 640 around the real
                 architectures, as tools/estimator_time.py times them around its stand-ins
 
@@ -39,7 +47,8 @@ sys.path.insert(0, ROOT)
 PAIRS, CROP = 252, 160
 SHAPES = [(2 * PAIRS, 40, 40, 128), (PAIRS, 40, 40, 256), (PAIRS, 20, 20, 512)]
 PEAK_F16_TFLOPS = 2500.0   # dense float16 MFMA peak of the MI355X
-STEPS = [("layers", 300), ("heads", 300), ("forward", 420), ("first torch", 300), ("first hip", 300), ("estimator", 420)]
+STEPS = [("layers", 300), ("heads", 300), ("forward", 420), ("first torch", 300), ("first hip", 300), ("strided", 420),
+         ("strided_first torch", 300), ("strided_first hip", 300), ("estimator", 420)]
 CFG = {"use_BN": True, "c_in": 6, "rot_rep": "axis_angle", "input_resize": (CROP, CROP), "trans_normalizer": [0.02, 0.02, 0.05],
        "rot_normalizer": 0.35}
 
@@ -155,10 +164,63 @@ def heads():
     return out
 
 
-def _nets(backend):
+def _nets(backend, strided="torch"):
     from pedp_hip import networks
 
-    return networks.RefineNet(CFG, backend=backend).cuda().eval(), networks.ScoreNetMultiPair(CFG, backend=backend).cuda().eval()
+    return (networks.RefineNet(CFG, backend=backend, strided=strided).cuda().eval(),
+            networks.ScoreNetMultiPair(CFG, backend=backend, strided=strided).cuda().eval())
+
+
+def strided():
+    import torch
+    import torch.nn.functional as F
+    from pedp_hip.conv import conv_stem, conv_strided, pack_conv
+
+    out = {"layers": {}, "forward": {}}
+    A, B = _inputs()
+    for name, (n, h, w, cin, cout, k) in (("stem_7x7_6to64_160x160_x504", (2 * PAIRS, CROP, CROP, 6, 64, 7)),
+                                          ("3x3_64to128_80x80_x504", (2 * PAIRS, 80, 80, 64, 128, 3)),
+                                          ("3x3_256to512_40x40_x252", (PAIRS, 40, 40, 256, 512, 3))):
+        conv = torch.nn.Conv2d(cin, cout, k, 2, (k - 1) // 2).cuda()
+        packed = pack_conv(conv)
+        w16 = conv.weight.detach().half().contiguous(memory_format=torch.channels_last)
+        b16 = conv.bias.detach().half()
+        y = torch.empty((n, h // 2, w // 2, cout), dtype=torch.float16, device="cuda")
+        if k == 7:
+            x16 = torch.cat([A, B], 0).half().contiguous(memory_format=torch.channels_last)
+
+            def entry():
+                with torch.autocast("cuda"):
+                    return conv(torch.cat([A, B], 0))
+
+            fns = [lambda: conv_stem(A, B, packed, relu=False, out=y), lambda: F.conv2d(x16, w16, b16, 2, 3), entry]
+        else:
+            x = torch.randn((n, h, w, cin), device="cuda").half()
+            xv = x.permute(0, 3, 1, 2)                                   # the same memory as an NCHW channels-last view
+            fns = [lambda: conv_strided(x, packed, relu=False, out=y), lambda: F.conv2d(xv, w16, b16, 2, 1)]
+        with torch.inference_mode():
+            t = _event_ms(fns, 20)
+        flop = 2.0 * n * (h // 2) * (w // 2) * cout * k * k * cin
+        tf = flop / (t[0]["median_ms"] * 1e-3) / 1e12
+        out["layers"][name] = {"gflop": flop / 1e9, "kernel": t[0], "torch_conv": t[1], "kernel_tflops": tf,
+                               "kernel_fraction_of_f16_peak": tf / PEAK_F16_TFLOPS,
+                               "kernel_over_torch": t[0]["median_ms"] / t[1]["median_ms"]}
+        if k == 7:
+            out["layers"][name]["torch_cat_cast_conv"] = t[2]
+            del x16
+    rn, sn = _nets("hip")
+    refine, score = _forward_fns(rn, sn, A, B)
+
+    def with_strided(net, value, fn):
+        def run():
+            net.set_strided(value)
+            return fn()
+        return run
+
+    for name, net, fn in (("refiner", rn, refine), ("scorer", sn, score)):
+        t, h = _event_ms([with_strided(net, v, fn) for v in ("torch", "hip")], 10, warm=2)
+        out["forward"][name] = {"torch": t, "hip": h, "hip_over_torch": h["median_ms"] / t["median_ms"]}
+    return out
 
 
 def _forward_fns(rn, sn, A, B):
@@ -201,11 +263,11 @@ def forward():
     return out
 
 
-def first(backend):
+def first(backend, strided="torch"):
     import torch
 
     A, B = _inputs()
-    rn, sn = _nets(backend)
+    rn, sn = _nets(backend, strided)
     out = {}
     for name, fn in zip(("refiner", "scorer"), _forward_fns(rn, sn, A, B)):
         torch.cuda.synchronize()
@@ -358,8 +420,9 @@ if __name__ == "__main__":
         else:
             import torch
 
-            res = {"layers": layers, "heads": heads, "forward": forward, "estimator": estimator}.get(sys.argv[2], lambda: first(sys.argv[3]))()
-            if sys.argv[2] in ("layers", "heads"):
+            res = {"layers": layers, "heads": heads, "forward": forward, "estimator": estimator, "strided": strided,
+                   "strided_first": lambda: first("hip", sys.argv[3])}.get(sys.argv[2], lambda: first(sys.argv[3]))()
+            if sys.argv[2] in ("layers", "heads", "strided"):
                 res["device"] = torch.cuda.get_device_name(0)
             print(json.dumps(res))
     else:
