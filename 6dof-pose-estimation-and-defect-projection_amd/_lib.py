@@ -105,6 +105,11 @@ PROTOTYPES = {
     "pedp_cloud_create_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _P(C.c_void_p)]),
     "pedp_cloud_destroy": (None, [C.c_void_p]),
     "pedp_cloud_size": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int)]),
+    "pedp_icp_graph_captures": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
+    "pedp_cloud_set_target_order": (C.c_int, [C.c_void_p, C.c_int]),
+    "pedp_cloud_target_order": (C.c_int, [C.c_void_p, _P(C.c_int)]),
+    "pedp_debug_target_pack": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_int64), _P(C.c_int64), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_icp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_void_p,
                            _P(C.c_double), _P(C.c_double), _P(C.c_int32), C.c_void_p, C.c_void_p]),
     "pedp_icp_batched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int,
@@ -705,6 +710,13 @@ def icp_last_serial_path(ctx):
     return a.value, b.value
 
 
+def icp_graph_captures(ctx):
+    """Registration graphs captured on the context and its sub-contexts so far (pedp_icp_graph_captures)."""
+    a = C.c_int64(0)
+    check(load().pedp_icp_graph_captures(ctx._h, C.byref(a)), "pedp_icp_graph_captures")
+    return a.value
+
+
 def icp_last_planned_passes(ctx):
     """Passes of the last single icp() that ran under a visit plan (more live chunks than CUs; scheduling only)."""
     a = C.c_int64(0)
@@ -751,6 +763,39 @@ def icp(ctx, source, target, max_correspondence_distance, init, estimator=POINT_
         out["corr"] = corr
     if want_trace:
         out["trace"] = trace[: it.value + 1]
+    return out
+
+
+TARGET_ORDER_AUTO, TARGET_ORDER_HILBERT, TARGET_ORDER_COMPACT = 0, 1, 2
+
+
+def cloud_set_target_order(cloud, mode):
+    """Order of the cloud's rows in its target pack: TARGET_ORDER_AUTO (Hilbert first, compact from the second
+    registration against a large target), _HILBERT or _COMPACT (pedp_cloud_set_target_order).  Results do not depend
+    on it in any bit; the work of a pass does."""
+    check(load().pedp_cloud_set_target_order(cloud._h, int(mode)), "pedp_cloud_set_target_order")
+
+
+def cloud_target_order(cloud):
+    """The order of the pack the cloud holds now (TARGET_ORDER_HILBERT / _COMPACT; 0: it has not been a target)."""
+    v = C.c_int(0)
+    check(load().pedp_cloud_target_order(cloud._h, C.byref(v)), "pedp_cloud_target_order")
+    return v.value
+
+
+def debug_target_pack(ctx, cloud):
+    """The cloud's target pack (pedp_debug_target_pack): dict(rows, tile_perm, tgt4, sph16, sph64, sph1024)."""
+    n, pad = C.c_int64(0), C.c_int64(0)
+    lib = load()
+    check(lib.pedp_debug_target_pack(ctx._h, cloud._h, C.byref(n), C.byref(pad), None, None, None, None, None),
+          "pedp_debug_target_pack")
+    p = pad.value
+    out = {"rows": n.value, "tile_perm": np.empty(cloud.N, np.int32), "tgt4": np.empty((p, 4), np.float32),
+           "sph16": np.empty((p // 16, 4), np.float32), "sph64": np.empty((p // 64, 4), np.float32),
+           "sph1024": np.empty(((p // 16 + 63) // 64, 4), np.float32)}
+    check(lib.pedp_debug_target_pack(ctx._h, cloud._h, None, None, _ptr(out["tile_perm"]), _ptr(out["tgt4"]),
+                                     _ptr(out["sph16"]), _ptr(out["sph64"]), _ptr(out["sph1024"])),
+          "pedp_debug_target_pack")
     return out
 
 

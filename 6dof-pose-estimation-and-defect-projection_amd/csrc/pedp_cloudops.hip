@@ -2505,9 +2505,10 @@ SortPlan sort_plan(int64_t N, int bits) {
     const int used = 3 * per_axis < bits ? 3 * per_axis : bits;
     return {bits - used, bits, N >= 131072};
 }
-int sort64_layout(pedp_ctx_t c, int64_t N, int bits, Sort64Layout &L) {
+// every bit of the key counts (the target's tile order: segment id over a coordinate's bits)
+SortPlan sort_plan_exact(int64_t N, int bits) { return {0, bits, N >= 131072}; }
+int sort64_layout(pedp_ctx_t c, int64_t N, const SortPlan &sp, Sort64Layout &L) {
     size_t tmp_sort = 0;
-    const SortPlan sp = sort_plan(N, bits);
     if (sp.passes)
         PEDP_ROCPRIM(rocprim::radix_sort_pairs<RadixPasses>(nullptr, tmp_sort, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                                             (int *)nullptr, (int *)nullptr, (unsigned)N, sp.begin_bit, sp.end_bit, c->stream));
@@ -2526,20 +2527,33 @@ int sort64_layout(pedp_ctx_t c, int64_t N, int bits, Sort64Layout &L) {
     return PEDP_OK;
 }
 }  // namespace
-int pedp_sort_keys64_begin(pedp_ctx_t c, int64_t N, int bits, unsigned long long **d_keys) {
+namespace {
+int sort64_begin(pedp_ctx_t c, int64_t N, const SortPlan &sp, unsigned long long **d_keys) {
     Sort64Layout L;
-    int st = sort64_layout(c, N, bits, L);
+    int st = sort64_layout(c, N, sp, L);
     if (st) return st;
     *d_keys = L.keys;
     return PEDP_OK;
 }
-int pedp_sort_keys64_run(pedp_ctx_t c, int64_t N, int bits, int32_t *d_perm) {
+int sort64_run(pedp_ctx_t c, int64_t N, const SortPlan &sp, int32_t *d_perm);
+}  // namespace
+int pedp_sort_keys64_begin(pedp_ctx_t c, int64_t N, int bits, unsigned long long **d_keys) {
+    return sort64_begin(c, N, sort_plan(N, bits), d_keys);
+}
+int pedp_sort_keys64_run(pedp_ctx_t c, int64_t N, int bits, int32_t *d_perm) { return sort64_run(c, N, sort_plan(N, bits), d_perm); }
+int pedp_sort_keys64_exact_begin(pedp_ctx_t c, int64_t N, int bits, unsigned long long **d_keys) {
+    return sort64_begin(c, N, sort_plan_exact(N, bits), d_keys);
+}
+int pedp_sort_keys64_exact_run(pedp_ctx_t c, int64_t N, int bits, int32_t *d_perm) {
+    return sort64_run(c, N, sort_plan_exact(N, bits), d_perm);
+}
+namespace {
+int sort64_run(pedp_ctx_t c, int64_t N, const SortPlan &sp, int32_t *d_perm) {
     if (N <= 0) return PEDP_OK;
     Sort64Layout L;
-    int st = sort64_layout(c, N, bits, L);  // same sizes as _begin: the scratch does not move
+    int st = sort64_layout(c, N, sp, L);  // same sizes as _begin: the scratch does not move
     if (st) return st;
     hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, L.val, N);
-    const SortPlan sp = sort_plan(N, bits);
     if (sp.passes)
         PEDP_ROCPRIM(rocprim::radix_sort_pairs<RadixPasses>(L.tmp, L.tmp_bytes, L.keys, L.keys_s, L.val, (int *)d_perm, (unsigned)N,
                                                             sp.begin_bit, sp.end_bit, c->stream));
@@ -2549,3 +2563,4 @@ int pedp_sort_keys64_run(pedp_ctx_t c, int64_t N, int bits, int32_t *d_perm) {
     PEDP_HIP_CHECK(hipGetLastError());
     return PEDP_OK;
 }
+}  // namespace

@@ -42,6 +42,8 @@
 //   icp/common.h             build switches (PEDP_NN_EXPERIMENT, PEDP_ICP_STAMPS), constants, IcpState, dmul/dadd/dsub, dist2
 //   icp/prep.h               hilbert3, cell_key_kernel, chunk_sphere_kernel, pack_target_kernel, sort_rows_kernel,
 //                            tile_sphere_kernel
+//   icp/target_order.h       the compact row order of a target pack: tord_init_kernel, tord_block_box_kernel,
+//                            tord_key_kernel, tord_leaf_kernel
 //   icp/segmented_sweep.h    icp_transform_pack_kernel, nn_cull_kernel, nn_segment_kernel, nn_sweep_kernel,
 //                            pack_target_bf16_kernel, nn_sweep_bf16_kernel, nn_bf16_debug_kernel
 //   icp/segmented_select.h   nn_select_kernel, nn_fallback_kernel, icp_accumulate_kernel, icp_reduce_kernel
@@ -68,6 +70,7 @@
 
 #include "icp/common.h"
 #include "icp/prep.h"
+#include "icp/target_order.h"
 #include "icp/segmented_sweep.h"
 #include "icp/segmented_select.h"
 #include "icp/solve.h"
@@ -243,7 +246,7 @@ void bind_clouds(IcpWorkspace &w, pedp_cloud_t source, pedp_cloud_t target, int 
     w.word_sph = (const float4 *)target->tile_sphw;
     w.tgt_s = (const double *)target->tgt_s;
     w.tile_sph = (const float4 *)(qt == 4 ? target->tile_sph4 : target->tile_sph);
-    w.tgt_perm = (const int32_t *)target->perm;
+    w.tgt_perm = (const int32_t *)target->tile_perm;
     w.src_perm = (const int32_t *)source->perm;
 }
 
@@ -443,55 +446,163 @@ int ensure_spatial_perm(pedp_ctx_t c, pedp_cloud_t cl) {
     return PEDP_OK;
 }
 
-// Target-side operand of the sweep, built once per cloud and kept in the handle (the
-// reference re-runs ICP ~50x per frame against the same model, pose_estimation.py:577-613).
-int ensure_target_pack(pedp_ctx_t c, pedp_cloud_t tgt, TargetPrep &tp) {
-    { const int rs = pedp_cloud_host_stats(c, tgt); if (rs) return rs; }
-    for (int k = 0; k < 3; ++k) tp.c[k] = tgt->centroid[k];
-    tp.Tn = tgt->Tn;
-    tp.T2 = tgt->T2;
-    for (int k = 0; k < 3; ++k) { tp.lo[k] = tgt->lo[k]; tp.hi[k] = tgt->hi[k]; tp.bc[k] = 0.5 * (tp.lo[k] + tp.hi[k]); }
-    if (tgt->tgt4) return PEDP_OK;
-    int rc = ensure_spatial_perm(c, tgt);
-    if (rc) return rc;
-    const int64_t nt = target_rows(tgt);  // the finite rows: first in the spatial order, the only ones in the operand
-    // real tiles rounded to NN_TU, plus readable pad tiles the pipelined sweep may prefetch
-    int64_t pad = (int64_t)align_up((size_t)(tgt->N > 0 ? tgt->N : 1), 16 * NN_TU) + 16 * NN_TILE_PAD;
-    // all three or none: a half-built pack must not look finished to the next call
-    void *t4 = nullptr, *s1 = nullptr, *s4 = nullptr, *sw = nullptr, *ts = nullptr;
+// The pack's kernels over the target's tile order (tgt->tile_perm), into the pack's buffers where they are: the first
+// build and every change of order.  A bf16 operand that exists follows.
+int write_target_pack(pedp_ctx_t c, pedp_cloud_t tgt, const TargetPrep &tp) {
+    const int64_t nt = target_rows(tgt), pad = tgt->tgt4_pad;
     const int64_t n_wsph = (pad / 16 + 63) / 64;  // one sphere per mask word of 16-row tiles (1024 rows)
-    hipError_t e = hipMalloc(&t4, sizeof(float4) * (size_t)pad);
-    if (e == hipSuccess) e = hipMalloc(&s1, sizeof(float4) * (size_t)(pad / 16));
-    if (e == hipSuccess) e = hipMalloc(&s4, sizeof(float4) * (size_t)(pad / 64));
-    if (e == hipSuccess) e = hipMalloc(&sw, sizeof(float4) * (size_t)n_wsph);
-    if (e == hipSuccess) e = hipMalloc(&ts, sizeof(double) * 6 * (size_t)pad);
-    if (e != hipSuccess) {
-        if (t4) (void)hipFree(t4);
-        if (s1) (void)hipFree(s1);
-        if (s4) (void)hipFree(s4);
-        if (sw) (void)hipFree(sw);
-        if (ts) (void)hipFree(ts);
-        pedp_set_error("pedp_icp: target pack allocation failed: %s", hipGetErrorString(e));
-        return PEDP_ERR_ALLOC;
-    }
-    tgt->tgt4 = t4;
-    tgt->tile_sph = s1;
-    tgt->tile_sph4 = s4;
-    tgt->tile_sphw = sw;
-    tgt->tgt_s = ts;
-    tgt->tgt4_pad = pad;
+    const int32_t *order = (const int32_t *)tgt->tile_perm;
     int64_t grid = (pad + 255) / 256;
-    hipLaunchKernelGGL(pack_target_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, tgt->pts,
-                       (const int32_t *)tgt->perm, nt, pad, tp.c[0], tp.c[1], tp.c[2], (float4 *)tgt->tgt4);
+    hipLaunchKernelGGL(pack_target_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, tgt->pts, order, nt, pad, tp.c[0], tp.c[1],
+                       tp.c[2], (float4 *)tgt->tgt4);
     hipLaunchKernelGGL(tile_sphere_kernel, dim3((unsigned)((pad / 16 + 255) / 256)), dim3(256), 0, c->stream,
                        (const float4 *)tgt->tgt4, nt, pad / 16, 16, (float4 *)tgt->tile_sph);
     hipLaunchKernelGGL(tile_sphere_kernel, dim3((unsigned)((pad / 64 + 255) / 256)), dim3(256), 0, c->stream,
                        (const float4 *)tgt->tgt4, nt, pad / 64, 64, (float4 *)tgt->tile_sph4);
     hipLaunchKernelGGL(tile_sphere_kernel, dim3((unsigned)((n_wsph + 63) / 64)), dim3(64), 0, c->stream,
                        (const float4 *)tgt->tgt4, nt, n_wsph, 1024, (float4 *)tgt->tile_sphw);
-    hipLaunchKernelGGL(sort_rows_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, tgt->pts, tgt->normals,
-                       (const int32_t *)tgt->perm, nt, pad, (double *)tgt->tgt_s);
+    hipLaunchKernelGGL(sort_rows_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, tgt->pts, tgt->normals, order, nt, pad,
+                       (double *)tgt->tgt_s);
+    if (tgt->tgt_bf) {
+        const int64_t n = pad * 4;
+        hipLaunchKernelGGL(pack_target_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                           (const float4 *)tgt->tgt4, pad, (uint4 *)tgt->tgt_bf);
+    }
     PEDP_HIP_CHECK(hipGetLastError());
+    return PEDP_OK;
+}
+
+// The compact tile order (icp/target_order.h) into tgt->tile_perm, from the Hilbert pack that tgt->tgt4 holds.
+int build_compact_order(pedp_ctx_t c, pedp_cloud_t tgt) {
+    const int64_t nt64 = target_rows(tgt);
+    if (nt64 <= 16) return PEDP_OK;  // one tile: the Hilbert order is the compact one
+    const int nt = (int)nt64;
+    const int n_blocks = (nt + TORD_BLOCK - 1) / TORD_BLOCK, levels = tord_top_levels(nt);
+    const size_t rows = align_up(sizeof(int32_t) * (size_t)nt, 256);
+    const size_t off_box = 3 * rows, off_seg = off_box + align_up(sizeof(float) * 6 * (size_t)n_blocks, 256);
+    size_t cap = 0;
+    char *ws = (char *)c->cloud_pool.take(off_seg + sizeof(int2) * (size_t)n_blocks, &cap);
+    if (!ws) { pedp_set_error("pedp_icp: target order: allocation failed"); return PEDP_ERR_ALLOC; }
+    int32_t *cur[2] = {(int32_t *)ws, (int32_t *)(ws + rows)}, *sigma = (int32_t *)(ws + 2 * rows);
+    float *blk_box = (float *)(ws + off_box);
+    int2 *blk_seg = (int2 *)(ws + off_seg);
+    const float4 *t4 = (const float4 *)tgt->tgt4;
+    int rc = PEDP_OK, side = 0;
+    bool sorted = false;
+    if (levels > 0) {
+        int key_bits = 32;
+        while (((int64_t)1 << (key_bits - 32)) < n_blocks) ++key_bits;
+        unsigned long long *keys = nullptr;
+        rc = pedp_sort_keys64_exact_begin(c, nt, key_bits, &keys);
+        if (!rc) hipLaunchKernelGGL(tord_init_kernel, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, c->stream, blk_seg, n_blocks, nt);
+        for (int l = 0; l < levels && !rc; ++l) {
+            hipLaunchKernelGGL(tord_block_box_kernel, dim3((unsigned)n_blocks), dim3(256), 0, c->stream, t4, (const int32_t *)cur[side],
+                               sorted ? (const int32_t *)sigma : nullptr, cur[side ^ 1], nt, blk_box);
+            side ^= 1;
+            hipLaunchKernelGGL(tord_key_kernel, dim3((unsigned)n_blocks), dim3(256), 0, c->stream, t4, (const int32_t *)cur[side], nt,
+                               (const float *)blk_box, blk_seg, keys);
+            rc = pedp_sort_keys64_exact_run(c, nt, key_bits, sigma);
+            sorted = true;
+        }
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(tord_leaf_kernel, dim3((unsigned)n_blocks), dim3(256), 0, c->stream, t4, (const int32_t *)cur[side],
+                           sorted ? (const int32_t *)sigma : nullptr, (const int32_t *)tgt->perm, nt, (int32_t *)tgt->tile_perm);
+        if (hipGetLastError() != hipSuccess) { pedp_set_error("pedp_icp: target order: launch failed"); rc = PEDP_ERR_HIP; }
+    }
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    c->cloud_pool.give(ws, cap);  // (reuse is ordered by the stream)
+    return rc;
+}
+
+// Which order a target's pack should have now.  Automatic mode: the Hilbert runs that the first registration gets for
+// the price of five launches, the compact order from the second registration on against targets large enough that the
+// shorter tile lists pay the build back.  PEDP_ICP_TARGET_ORDER=hilbert|compact decides for every
+// cloud in automatic mode (A/B runs).
+constexpr int64_t TORD_AUTO_MIN_ROWS = 16384;
+constexpr int TORD_AUTO_REGISTRATION = 2;
+// a registration against tgt has been enqueued whole (counted up to the one that upgrades the order)
+inline void count_registration(pedp_cloud_t tgt) {
+    if (tgt->registrations < TORD_AUTO_REGISTRATION) ++tgt->registrations;
+}
+inline int target_order_env() {
+    static const int m = [] {
+        const char *v = getenv("PEDP_ICP_TARGET_ORDER");
+        if (v && !strcmp(v, "hilbert")) return PEDP_TARGET_ORDER_HILBERT;
+        if (v && !strcmp(v, "compact")) return PEDP_TARGET_ORDER_COMPACT;
+        return PEDP_TARGET_ORDER_AUTO;
+    }();
+    return m;
+}
+// upcoming: the call is a registration (it becomes number registrations + 1 once its passes are enqueued)
+inline int target_order_wanted(pedp_cloud_t tgt, bool upcoming) {
+    if (tgt->order_mode != PEDP_TARGET_ORDER_AUTO) return tgt->order_mode;
+    if (target_order_env() != PEDP_TARGET_ORDER_AUTO) return target_order_env();
+    return tgt->registrations + (upcoming ? 1 : 0) >= TORD_AUTO_REGISTRATION && target_rows(tgt) >= TORD_AUTO_MIN_ROWS ? PEDP_TARGET_ORDER_COMPACT
+                                                                                                 : PEDP_TARGET_ORDER_HILBERT;
+}
+
+// Target-side operand of the sweep, built once per cloud and kept in the handle (the
+// reference re-runs ICP ~50x per frame against the same model, pose_estimation.py:577-613).
+// Its rows follow the target's tile order: the cloud's Hilbert order at first, the compact order once that is
+// wanted (target_order_wanted).  A change of order rewrites the pack where it is -- no buffer moves, so captured
+// graphs and sub-contexts stay valid -- in front of the caller's passes on the owner's stream.
+int ensure_target_pack(pedp_ctx_t c, pedp_cloud_t tgt, TargetPrep &tp, bool registration = false) {
+    { const int rs = pedp_cloud_host_stats(c, tgt); if (rs) return rs; }
+    for (int k = 0; k < 3; ++k) tp.c[k] = tgt->centroid[k];
+    tp.Tn = tgt->Tn;
+    tp.T2 = tgt->T2;
+    for (int k = 0; k < 3; ++k) { tp.lo[k] = tgt->lo[k]; tp.hi[k] = tgt->hi[k]; tp.bc[k] = 0.5 * (tp.lo[k] + tp.hi[k]); }
+    const int want = target_order_wanted(tgt, registration);
+    if (tgt->tgt4 && tgt->order_in_force == want) return PEDP_OK;
+    int rc = ensure_spatial_perm(c, tgt);
+    if (rc) return rc;
+    if (!tgt->tgt4) {
+        // real tiles rounded to NN_TU, plus readable pad tiles the pipelined sweep may prefetch
+        int64_t pad = (int64_t)align_up((size_t)(tgt->N > 0 ? tgt->N : 1), 16 * NN_TU) + 16 * NN_TILE_PAD;
+        // all or none: a half-built pack must not look finished to the next call
+        void *t4 = nullptr, *s1 = nullptr, *s4 = nullptr, *sw = nullptr, *ts = nullptr, *tq = nullptr;
+        const int64_t n_wsph = (pad / 16 + 63) / 64;
+        hipError_t e = hipMalloc(&t4, sizeof(float4) * (size_t)pad);
+        if (e == hipSuccess) e = hipMalloc(&s1, sizeof(float4) * (size_t)(pad / 16));
+        if (e == hipSuccess) e = hipMalloc(&s4, sizeof(float4) * (size_t)(pad / 64));
+        if (e == hipSuccess) e = hipMalloc(&sw, sizeof(float4) * (size_t)n_wsph);
+        if (e == hipSuccess) e = hipMalloc(&ts, sizeof(double) * 6 * (size_t)pad);
+        if (e == hipSuccess) e = hipMalloc(&tq, sizeof(int32_t) * (size_t)(tgt->N > 0 ? tgt->N : 1));
+        if (e != hipSuccess) {
+            if (t4) (void)hipFree(t4);
+            if (s1) (void)hipFree(s1);
+            if (s4) (void)hipFree(s4);
+            if (sw) (void)hipFree(sw);
+            if (ts) (void)hipFree(ts);
+            if (tq) (void)hipFree(tq);
+            pedp_set_error("pedp_icp: target pack allocation failed: %s", hipGetErrorString(e));
+            return PEDP_ERR_ALLOC;
+        }
+        tgt->tgt4 = t4;
+        tgt->tile_sph = s1;
+        tgt->tile_sph4 = s4;
+        tgt->tile_sphw = sw;
+        tgt->tgt_s = ts;
+        tgt->tile_perm = tq;
+        tgt->tgt4_pad = pad;
+        tgt->order_in_force = PEDP_TARGET_ORDER_AUTO;  // (none yet)
+    }
+    if (tgt->order_in_force != PEDP_TARGET_ORDER_HILBERT) {  // the Hilbert pack: what is wanted, or what the split starts from
+        tgt->order_in_force = PEDP_TARGET_ORDER_AUTO;  // (no order holds while the pack is rewritten: a failure leaves "none")
+        if (tgt->N > 0)
+            PEDP_HIP_CHECK(hipMemcpyAsync(tgt->tile_perm, tgt->perm, sizeof(int32_t) * (size_t)tgt->N, hipMemcpyDeviceToDevice, c->stream));
+        rc = write_target_pack(c, tgt, tp);
+        if (rc) return rc;
+        tgt->order_in_force = PEDP_TARGET_ORDER_HILBERT;
+    }
+    if (want == PEDP_TARGET_ORDER_COMPACT) {
+        tgt->order_in_force = PEDP_TARGET_ORDER_AUTO;
+        rc = build_compact_order(c, tgt);
+        if (!rc) rc = write_target_pack(c, tgt, tp);
+        if (rc) return rc;  // (rebuilt from the Hilbert order next time)
+        tgt->order_in_force = PEDP_TARGET_ORDER_COMPACT;
+    }
     return PEDP_OK;
 }
 
@@ -554,7 +665,7 @@ int icp_unit_size(pedp_cloud_t target, double r) {
 // Cached per-cloud preparation on the owner's stream: sorted target operand + unit spheres, spatial
 // order of the scene.
 int icp_prepare(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, TargetPrep &tp) {
-    int rc = ensure_target_pack(c, target, tp);
+    int rc = ensure_target_pack(c, target, tp, true);
     if (rc) return rc;
     rc = ensure_target_bf16(c, target);   // (with the pack, on the owner's stream: sub-contexts start after it is complete)
     if (rc) return rc;
@@ -820,7 +931,7 @@ int icp_launch_replayed(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, 
             const hipError_t e = hipStreamEndCapture(x->stream, &graph);
             if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
             if (e == hipSuccess && graph && hipGraphInstantiate(&x->icp_graph, graph, nullptr, nullptr, 0) == hipSuccess)
-                x->icp_graph_key = key;
+                { x->icp_graph_key = key; ++x->icp_graph_captures; }
             else
                 x->icp_graph = nullptr;
             if (graph) (void)hipGraphDestroy(graph);
@@ -893,6 +1004,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
         }
         (void)hipGraphDestroy(graph);
         c->icp_bgraph_key[slot] = key;
+        ++c->icp_graph_captures;
     }
     IcpState *up = (IcpState *)c->pinned, *down = (IcpState *)((char *)c->pinned + 32768);
     c->icp_last_cand = c->icp_last_fb = c->icp_last_passes = 0;  // statistics: totals over the batch
@@ -973,6 +1085,7 @@ int pedp_icp(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const pedp_
     IcpJob job;
     rc = icp_start(c, source, target, tp, prm, init, job, trace != nullptr, true);
     if (rc) return rc;
+    count_registration(target);
     return icp_collect(c, job, T_out, fitness, inlier_rmse, n_iter_done, corr, trace);
 }
 
@@ -990,6 +1103,7 @@ int pedp_icp_begin(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const
     PEDP_REQUIRE(job, "pedp_icp_begin: out of memory");
     rc = icp_start(c, source, target, tp, prm, init, *job, want_trace != 0, false);
     if (rc) { delete job; return rc; }
+    count_registration(target);
     c->icp_pending = job;
     return PEDP_OK;
 }
@@ -1040,7 +1154,11 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
         all_fused = icp_unit_size(target, r) == 1 && r > 0.0 && source->N > 0 && target_rows(target) > 0 &&
                     (target_rows(target) + 1023) / 1024 <= BK_WCAP;
     }
-    if (all_fused) return icp_batch_fused(c, source, target, tp, prms, inits, B, T_out, fitness, inlier_rmse, n_iter_done);
+    if (all_fused) {
+        rc = icp_batch_fused(c, source, target, tp, prms, inits, B, T_out, fitness, inlier_rmse, n_iter_done);
+        if (!rc) count_registration(target);
+        return rc;
+    }
     if (!uniform) {
         for (int b = 0; b < B; ++b) {
             IcpJob job;
@@ -1050,6 +1168,7 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
                              n_iter_done ? n_iter_done + b : nullptr, nullptr, nullptr);
             if (rc) return rc;
         }
+        count_registration(target);
         return PEDP_OK;
     }
     PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));  // preparation is visible to the sub-streams
@@ -1087,6 +1206,7 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
             c->icp_last_passes += c->sub[k]->icp_last_passes;
         }
     }
+    count_registration(target);
     return PEDP_OK;
 }
 
@@ -1188,6 +1308,42 @@ int pedp_icp_configure(pedp_ctx_t c, int exhaustive, int timed_pass) {
     return PEDP_OK;
 }
 
+int pedp_cloud_set_target_order(pedp_cloud_t cl, int mode) {
+    PEDP_REQUIRE(cl, "pedp_cloud_set_target_order: null cloud");
+    PEDP_REQUIRE(mode == PEDP_TARGET_ORDER_AUTO || mode == PEDP_TARGET_ORDER_HILBERT || mode == PEDP_TARGET_ORDER_COMPACT,
+                 "pedp_cloud_set_target_order: unknown mode %d", mode);
+    PEDP_REQUIRE(!pedp_ctx_is_live(cl->ctx) || !cl->ctx->icp_pending,
+                 "pedp_cloud_set_target_order: a registration is pending on the cloud's context (pedp_icp_end first)");
+    cl->order_mode = mode;  // a pack in the other order is rewritten by the next call that uses the cloud as a target
+    return PEDP_OK;
+}
+
+int pedp_cloud_target_order(pedp_cloud_t cl, int *in_force) {
+    PEDP_REQUIRE(cl && in_force, "pedp_cloud_target_order: null argument");
+    *in_force = cl->tgt4 ? cl->order_in_force : PEDP_TARGET_ORDER_AUTO;
+    return PEDP_OK;
+}
+
+int pedp_debug_target_pack(pedp_ctx_t c, pedp_cloud_t cl, int64_t *rows, int64_t *pad_rows, int32_t *tile_perm, float *tgt4,
+                           float *sph16, float *sph64, float *sph1024) {
+    PEDP_REQUIRE(c && cl && cl->ctx == c, "pedp_debug_target_pack: null context / cloud of another context");
+    PEDP_REQUIRE(cl->tgt4, "pedp_debug_target_pack: the cloud has not been a target yet");
+    PEDP_REQUIRE(!c->icp_pending, "pedp_debug_target_pack: a registration is pending on this context (pedp_icp_end first)");
+    PEDP_HIP_CHECK(hipSetDevice(c->device));
+    const int64_t pad = cl->tgt4_pad;
+    if (rows) *rows = target_rows(cl);
+    if (pad_rows) *pad_rows = pad;
+    struct { void *dst; const void *src; size_t bytes; } part[5] = {
+        {tile_perm, cl->tile_perm, sizeof(int32_t) * (size_t)cl->N},
+        {tgt4, cl->tgt4, sizeof(float4) * (size_t)pad},
+        {sph16, cl->tile_sph, sizeof(float4) * (size_t)(pad / 16)},
+        {sph64, cl->tile_sph4, sizeof(float4) * (size_t)(pad / 64)},
+        {sph1024, cl->tile_sphw, sizeof(float4) * (size_t)((pad / 16 + 63) / 64)}};
+    for (const auto &p : part)
+        if (p.dst && p.bytes) { int dn_ = pedp_download(c, p.dst, p.src, p.bytes); if (dn_) return dn_; }
+    return PEDP_OK;
+}
+
 int pedp_icp_last_stats(pedp_ctx_t c, int64_t *passes, int64_t *pairs_swept, int64_t *fallback_points) {
     PEDP_REQUIRE(c, "pedp_icp_last_stats: null context");
     if (passes) *passes = c->icp_last_passes;
@@ -1219,6 +1375,15 @@ int pedp_debug_nn_bf16(pedp_ctx_t c, const float *src4, int64_t n_src, const flo
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d_s); (void)hipFree(d_t); (void)hipFree(d_b); (void)hipFree(d_g);
     PEDP_HIP_CHECK(e);
+    return PEDP_OK;
+}
+
+int pedp_icp_graph_captures(pedp_ctx_t c, int64_t *captures) {
+    PEDP_REQUIRE(c && captures, "pedp_icp_graph_captures: null argument");
+    long long n = c->icp_graph_captures;
+    for (int k = 0; k < PEDP_MAX_SUB; ++k)
+        if (c->sub[k]) n += c->sub[k]->icp_graph_captures;
+    *captures = n;
     return PEDP_OK;
 }
 

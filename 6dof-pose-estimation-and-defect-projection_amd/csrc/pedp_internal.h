@@ -27,6 +27,9 @@ int pedp_download_parts(pedp_ctx_s *c, const void *src, size_t span, int n, cons
 struct pedp_ctx_s;
 int pedp_sort_keys64_begin(pedp_ctx_s *c, int64_t N, int bits, unsigned long long **d_keys);
 int pedp_sort_keys64_run(pedp_ctx_s *c, int64_t N, int bits, int32_t *d_perm);
+// the same pooled sort on all `bits` low bits of the keys (the Hilbert sort above looks only at the leading levels)
+int pedp_sort_keys64_exact_begin(pedp_ctx_s *c, int64_t N, int bits, unsigned long long **d_keys);
+int pedp_sort_keys64_exact_run(pedp_ctx_s *c, int64_t N, int bits, int32_t *d_perm);
 
 // Row i of an N x 3 float64 array has no NaN / infinite coordinate.  Tested on the exponent bits, so that no
 // compiler assumption about NaNs (-fno-honor-nans) can fold it away.
@@ -158,6 +161,7 @@ struct pedp_ctx_s {
     // [0] one pass (evaluation), [1] two (single-iteration probes), [2] the rest -- a frame alternates between them
     hipGraphExec_t icp_bgraph[18] = {};
     pedp_icp_graph_key icp_bgraph_key[18];
+    long long icp_graph_captures = 0;  // graphs captured and instantiated on this executor so far (pedp_icp_graph_captures)
     void *pinned = nullptr;  // small pinned host block for result read-back
     size_t pinned_cap = 0;
     void *stage[2] = {nullptr, nullptr};  // pinned staging buffers of pedp_upload [0] / pedp_download [1], grown on demand
@@ -220,6 +224,12 @@ struct pedp_cloud_s {
     void *tgt_s = nullptr;      // sorted rows as float64 x 3 (exact re-scoring)
     void *tgt_bf = nullptr;     // the sorted operand as bf16 pieces for the dense sweep's v_mfma_f32_16x16x32_bf16 (1 KB per 16-row tile; built on first use)
     int64_t tgt4_pad = 0;
+    // the order of the pack's rows (device int32[N], allocated with the pack): a copy of perm, or the compact order of
+    // icp/target_order.h; perm itself stays what defines the source role and every sum
+    void *tile_perm = nullptr;
+    int order_mode = 0;      // pedp_cloud_set_target_order (PEDP_TARGET_ORDER_*)
+    int order_in_force = 0;  // what the pack holds (0: none)
+    int registrations = 0;   // registrations against this handle whose passes were all enqueued, counted up to the one that upgrades the order
 };
 
 // pedp_icp.hip: frees the job of a pedp_icp_begin that was never ended (called by pedp_ctx_destroy)

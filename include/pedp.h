@@ -369,6 +369,24 @@ int pedp_cloud_create_device(pedp_ctx_t ctx, const double *d_pts, const double *
 void pedp_cloud_destroy(pedp_cloud_t cloud);
 int pedp_cloud_size(pedp_cloud_t cloud, int64_t *N, int *has_normals);
 
+/* Order of a cloud's rows in the pack it gets as a registration TARGET (sorted operand, tile spheres, sorted rows).
+ * Any partition of the target's rows into tiles of 16 gives the same results in every bit; the order decides how many
+ * tiles a pass has to look at.  HILBERT: runs of the cloud's spatial order (five launches).  COMPACT: a balanced k-d
+ * split of that order (csrc/icp/target_order.h), about a third fewer tiles listed per pass on a surface model, built
+ * on the device (1.4 ms of kernel time for 50,000 rows on an MI355X).  AUTO (default): Hilbert for the
+ * first registration against the handle; from the second on -- a call of pedp_icp, pedp_icp_begin or
+ * pedp_icp_batched[_ex] that comes after one whose passes were all enqueued -- the compact order if the target has at
+ * least 16,384 finite rows; the pack is rewritten where it is, in front of that call's passes.  The environment
+ * variable PEDP_ICP_TARGET_ORDER=hilbert|compact, read once per process, decides for every cloud left in AUTO.
+ * A change of mode takes effect at the cloud's next use as a target: a pack in the other order is rewritten in place
+ * (buffers keep their addresses).  No counterpart in the reference (src/pose_estimation.py:447-453 calls Open3D). */
+#define PEDP_TARGET_ORDER_AUTO 0
+#define PEDP_TARGET_ORDER_HILBERT 1
+#define PEDP_TARGET_ORDER_COMPACT 2
+int pedp_cloud_set_target_order(pedp_cloud_t cloud, int mode);
+/* in_force: the order of the pack the cloud holds now (HILBERT / COMPACT), 0 while it has none. */
+int pedp_cloud_target_order(pedp_cloud_t cloud, int *in_force);
+
 /* Optional hook called once per correspondence pass with a DEVICE pointer to the
  * n-double partial-sum packet of this rank; it must enqueue an in-place sum over all
  * ranks on `stream` (RCCL all-reduce through torch.distributed) and return 0. */
@@ -485,6 +503,11 @@ int pedp_icp_last_stats(pedp_ctx_t ctx, int64_t *passes, int64_t *pairs_swept, i
  * tests/test_icp_gpu.py compares).  No counterpart in the reference (src/pose_estimation.py:447-453 calls Open3D). */
 int pedp_icp_last_planned_passes(pedp_ctx_t ctx, int64_t *planned);
 
+/* Registration graphs captured and instantiated on `ctx` and its sub-contexts since the context was created (the
+ * per-pose graph of a batch on the segmented path, the group graphs of a fused batch).  A count that stands still
+ * over a call means the call replayed what it had (tests: a target whose order changes keeps its graphs). */
+int pedp_icp_graph_captures(pedp_ctx_t ctx, int64_t *captures);
+
 /* The serial part of a pass and of a registration, for the last single registration collected on `ctx`.
  * wide_closes: passes whose close ran in its wide form -- the first look at the sign-off counters requested with the
  * partial sums' loads, the three sincos of the update on three lanes, the sixteen entries of the new pose on sixteen --
@@ -502,6 +525,13 @@ int pedp_icp_last_serial_path(pedp_ctx_t ctx, int64_t *wide_closes, int64_t *bra
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
  * g[i * n_tgt + j] = |t'_j|^2 - 2 s'_i . t'_j exactly as the sweep's v_mfma_f32_16x16x32_bf16 produces it (same operand packing). */
 int pedp_debug_nn_bf16(pedp_ctx_t ctx, const float *src4, int64_t n_src, const float *tgt4, int64_t n_tgt, float *g);
+
+/* Read-out of a target's pack for tests: rows = its finite rows, pad_rows = rows of the padded operand; tile_perm
+ * (int32 x N: original index of pack row k), tgt4 (float32 x 4 x pad_rows: centred x y z, |.|^2), and the spheres
+ * (float32 x 4: centre, radius; radius < 0: no rows) of every 16 rows (pad_rows / 16), every 64 rows (pad_rows / 64)
+ * and every 1024 rows (ceil(pad_rows / 1024)).  Any array may be null.  The cloud must have been a target. */
+int pedp_debug_target_pack(pedp_ctx_t ctx, pedp_cloud_t cloud, int64_t *rows, int64_t *pad_rows, int32_t *tile_perm,
+                           float *tgt4, float *sph16, float *sph64, float *sph1024);
 
 /* ---------------------------------------------------------------- multi-GPU collectives
  * One process per GPU.  The reference has no distributed path; these entry points
