@@ -121,6 +121,7 @@ PROTOTYPES = {
     "pedp_icp_last_stats": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_planned_passes": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_icp_last_serial_path": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
+    "pedp_icp_last_head_closed": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
     "pedp_icp_end": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int32), C.c_void_p, C.c_void_p]),
@@ -708,6 +709,15 @@ def icp_last_serial_path(ctx):
     a, b = C.c_int64(0), C.c_int64(0)
     check(load().pedp_icp_last_serial_path(ctx._h, C.byref(a), C.byref(b)), "pedp_icp_last_serial_path")
     return a.value, b.value
+
+
+def icp_last_head_closed(ctx, rebuilds=False):
+    """Passes of the last single icp() closed at the head of the next launch (pedp_icp_last_head_closed);
+    PEDP_ICP_HEAD_CLOSE=0 gives 0.  With rebuilds=True: (that, rebuilds of the live set asked for after pass 0,
+    passes enqueued)."""
+    a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(load().pedp_icp_last_head_closed(ctx._h, C.byref(a), C.byref(b), C.byref(c)), "pedp_icp_last_head_closed")
+    return (a.value, b.value, c.value) if rebuilds else a.value
 
 
 def icp_graph_captures(ctx):

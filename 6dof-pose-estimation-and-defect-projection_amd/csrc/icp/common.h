@@ -25,7 +25,8 @@ extern "C" int pedp_debug_icp_stamps(long long *out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_icp_stamps), sizeof(long long) * 3 * 4096 * 8) == hipSuccess ? 0 : -3;
 }
 // s_memrealtime (100 MHz, one clock for the whole device) per pass and workgroup of the pass kernel:
-// [0] entry, [1] state read, [2] chunks done, [3] ticket returned, [4] pass closed (last workgroup only)
+// [0] entry, [1] state read, [2] chunks done, [3] ticket returned, [4] pass closed (last workgroup only); the head close of the
+// pass before: [5] partial sums' loads back, [6] sums done, [7] U published
 __device__ long long g_icp_rt[32][512][8];
 // per wave of the pass kernel (last pass that ran): [0] start [1] slots ready [2] culled+swept [3] selected [4] sums done (s_memtime),
 // [5] words << 32 | batches << 16 | wide << 8 | slots, [6] tiles
@@ -106,7 +107,7 @@ struct IcpState {
     int n_planned;             // passes of this registration that ran under a visit plan (statistics)
     int nonce;                 // of this registration (<< 16 in the tags of the visit plan: entries of an earlier registration never match)
     int n_wide;                // passes of this registration closed by the wide close (statistics: tests check it was in force)
-    int reserved_;
+    int n_head;                // passes of this registration closed at the head of the next launch (statistics, as n_wide)
     double T_init[16];         // the start transformation: slot 0 of the update history (arrives with the state, no copy of its own)
 };
 

@@ -225,6 +225,15 @@ struct PassArgs {
     // executor's page-locked block: no copy follows the last pass (single registration; null: the host copies)
     unsigned long long *down;
     int serial_close;           // PEDP_ICP_SERIAL_CLOSE=1: the close as it was, everything after the sums on one lane
+    // Head close (single registration, fused, wide close, final state written by the device; PEDP_ICP_HEAD_CLOSE=0: off).
+    // A steady pass ends with its partial sums; the NEXT launch closes it, in every workgroup, before it transforms its
+    // chunk.  The state has two slots by pass parity (slot p & 1 holds the state pass p starts from); `launch` is the
+    // index of this launch = the pass it runs.  The grid has one workgroup more than chunks can fill: the first
+    // workgroup without a chunk (the service workgroup) writes what a head close leaves behind.
+    int head, launch;
+    // Head close: pass p stores its partial sums into copy p & 1 (part_stride doubles apart).  The head of launch L reads
+    // pass L - 1's while workgroups of launch L that are through already store pass L's: not into the same buffer.
+    size_t part_stride;
 };
 
 template <typename T>
@@ -263,6 +272,11 @@ struct FinishArgs {
     // solve the three sincos run on three lanes, the sixteen entries of the new pose on sixteen; 1: all of it on lane 0,
     // one step after the other, as it was.  Every output is computed by the same sequence of float64 operations.
     int serial = 0;
+    // the mask the rebuild pass before this close read "was live" from (today: the copy the closer makes aside when it
+    // asks for a rebuild; gen_masks: the other of two masks used in turn, rebuild g ORs into mask g & 1 -- its closer
+    // zeroes the other one, nothing is copied aside when a rebuild is asked for)
+    unsigned long long *live_old = nullptr;
+    int gen_masks = 0;
 };
 template <int NT, int LCAP>
 struct FinishLds {
@@ -301,17 +315,27 @@ __device__ __forceinline__ unsigned long long load_live(unsigned long long *p) {
     return *p;
 }
 
-template <int NT, int LCAP, bool COHERENT>
+// MODE 0: `st` is the state in memory.  MODE 1: `st` is the workgroup's copy of the state in LDS; the caller writes it
+// out (and the final state to f.down's block) behind the body.  MODE 2: the head close -- as 1, and every workgroup of
+// the launch runs it: nothing is written to memory here (the service workgroup does that from LDS), no live list, no
+// sign-off poll, no live-mask upkeep.
+// the close's stamps (diagnostic build): of a head close, which every workgroup runs, workgroup 0's only
+#define PEDP_STAMP_CLOSE(unit, slot) do { if (!HEAD || blockIdx.x == 0) PEDP_STAMP(2, unit, slot); } while (0)
+template <int NT, int LCAP, bool COHERENT, int MODE = 0>
 __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &f, FinishLds<NT, LCAP> &L, const int tid) {
-    const int pass = f.known ? f.k_pass : st->pass, max_iter = st->max_iter;
-    const double n_source = st->n_source, rel_fitness = st->rel_fitness, rel_rmse = st->rel_rmse, reachE = st->reachE,
-                 margin = st->margin;
+    constexpr bool LOCAL = MODE != 0, HEAD = MODE == 2;
+    static_assert(!HEAD || !COHERENT, "the head close reads what the launch before stored");
+    // (a state in LDS comes back in vector registers: the parameters, the same in every lane, are made scalar again)
+    auto uni = [](double v) { return LOCAL ? bcast0(v) : v; };
+    const int pass = f.known ? f.k_pass : st->pass, max_iter = LOCAL ? __builtin_amdgcn_readfirstlane(st->max_iter) : st->max_iter;
+    const double n_source = uni(st->n_source), rel_fitness = uni(st->rel_fitness), rel_rmse = uni(st->rel_rmse), reachE = uni(st->reachE),
+                 margin = uni(st->margin);
     constexpr int PARTS = 32, TPARTS = NT / 32, PPT = PARTS / TPARTS;  // ranges; ranges in flight; ranges per thread
     static_assert(NT % 32 == 0 && PARTS % TPARTS == 0, "thread count");
     const bool wide = f.serial == 0;
     if (tid == 0) { L.do_rebuild = 0; L.stopped = 0; }
-    if (tid == 0) PEDP_STAMP(2, 0, 0);
-    if (tid == 0 && pass == 5) PEDP_STAMP(2, 3, 0);
+    if (tid == 0) PEDP_STAMP_CLOSE(0, 0);
+    if (tid == 0 && pass == 5) PEDP_STAMP_CLOSE(3, 0);
     // The first look at the sign-off counters is requested here, with the partial sums' loads, and evaluated where
     // the poll stands: the counters only grow, so a look that is complete now is complete then, and only a look that
     // comes back short enters the spin.  (With fewer live chunks than workgroups there are idle workgroups in every
@@ -333,12 +357,12 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         if (wide) n_wide0 = st->n_wide;
     }
 #if PEDP_ICP_STAMPS
-    if (tid == 0) { g_icp_stamps[2][1][0] = (long long)__builtin_amdgcn_s_memtime(); g_icp_stamps[2][1][1] = (long long)__builtin_amdgcn_s_memrealtime(); }
+    if (tid == 0 && (!HEAD || blockIdx.x == 0)) { g_icp_stamps[2][1][0] = (long long)__builtin_amdgcn_s_memtime(); g_icp_stamps[2][1][1] = (long long)__builtin_amdgcn_s_memrealtime(); }
 #endif
     if (f.phase != 2) {
         // Partial sums are indexed by chunk id in a rebuild pass and by live rank otherwise; either
         // way they are summed in ascending chunk order.
-        const bool listing = f.known ? f.k_rebuild != 0 : st->rebuild != 0;
+        const bool listing = !HEAD && (f.known ? f.k_rebuild != 0 : st->rebuild != 0);
         int n_live = f.known ? f.k_n_live : st->n_live;
         bool listed = true;
         if (listing) {
@@ -400,8 +424,15 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                     for (int u = 0; u < BW; ++u) at[u] = position(q + u < l_hi ? q + u : l_hi - 1);
 #pragma unroll
                     for (int u = 0; u < BW; ++u) {
-                        x0[u] = load_partial<COHERENT>(&f.partials[(size_t)at[u] * PSTRIDE + k0]);
-                        x1[u] = has1 ? load_partial<COHERENT>(&f.partials[(size_t)at[u] * PSTRIDE + k1]) : 0.0;
+                        if constexpr (HEAD) {  // k0 is even and PSTRIDE is 32: the two entries are one aligned 16-byte load
+                            typedef double v2d __attribute__((ext_vector_type(2)));
+                            const v2d t = *(const PEDP_GLOBAL v2d *)(uintptr_t)&f.partials[(size_t)at[u] * PSTRIDE + k0];
+                            x0[u] = t[0];
+                            x1[u] = has1 ? t[1] : 0.0;
+                        } else {
+                            x0[u] = load_partial<COHERENT>(&f.partials[(size_t)at[u] * PSTRIDE + k0]);
+                            x1[u] = has1 ? load_partial<COHERENT>(&f.partials[(size_t)at[u] * PSTRIDE + k1]) : 0.0;
+                        }
                     }
 #pragma unroll
                     for (int u = 0; u < BW; ++u) {
@@ -436,17 +467,19 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         if (!listing) sum_ranges([&](int q) { return q; });
         else if (listed) sum_ranges([&](int q) { return L.lst[q]; });
         else sum_ranges([&](int q) { return load_sc1(&f.live_list[q]); });
-        if (tid == 0 && pass == 5) PEDP_STAMP(2, 3, 1);
+        if (tid == 0 && pass == 5) PEDP_STAMP_CLOSE(3, 1);
+        if (HEAD) PEDP_RT(pass + 1, 5);  // head close: this workgroup's loads of the partial sums are back
         if (tid == 0) L.n_live_s = n_live;
         __syncthreads();
-        if (tid == 0 && pass == 5) PEDP_STAMP(2, 3, 2);
+        if (tid == 0 && pass == 5) PEDP_STAMP_CLOSE(3, 2);
         if (tid < 32) {
             double t = 0.0;
             for (int q = 0; q < PARTS; ++q) t += L.slice[q][tid];
             L.pk[tid] = t;
-            if (tid < PACKET) as_global(f.packet)[tid] = t;
+            if (!HEAD && tid < PACKET) as_global(f.packet)[tid] = t;
         }
         __syncthreads();
+        if (HEAD) PEDP_RT(pass + 1, 6);  // head close: the sums are done
         if (tid == 0 && f.phase == 1) {  // (phase 0 writes these further down, with the rest of the state)
             st->sum_tiles += (long long)L.pk[PACKET];
             st->sum_fb += (long long)L.pk[PACKET + 1];
@@ -454,7 +487,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         }
         if (tid == 0) {
 #if PEDP_ICP_STAMPS
-            g_icp_stamps[2][1][2] = (long long)__builtin_amdgcn_s_memtime(); g_icp_stamps[2][1][3] = (long long)__builtin_amdgcn_s_memrealtime();
+            if (!HEAD || blockIdx.x == 0) { g_icp_stamps[2][1][2] = (long long)__builtin_amdgcn_s_memtime(); g_icp_stamps[2][1][3] = (long long)__builtin_amdgcn_s_memrealtime(); }
 #endif
         }
         if (f.phase == 1) return;
@@ -482,7 +515,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         if (L.do_rebuild == -1) {  // (workgroup-uniform)
             if (tid == 0) {
                 st->done = -1;   // icp_collect / the batch driver turn this into PEDP_ERR_HIP
-                if (f.down) *(int *)((char *)f.down + offsetof(IcpState, done)) = -1;  // (where icp_collect looks when no copy follows)
+                if (!LOCAL && f.down) *(int *)((char *)f.down + offsetof(IcpState, done)) = -1;  // (where icp_collect looks when no copy follows)
             }
             return;
         }
@@ -498,8 +531,8 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         double upd[16], x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         ident4(upd);
         if (l0) {
-            PEDP_STAMP(2, 0, 1);
-            if (pass == 5) PEDP_STAMP(2, 3, 3);
+            PEDP_STAMP_CLOSE(0, 1);
+            if (pass == 5) PEDP_STAMP_CLOSE(3, 3);
             if (COHERENT) { st->ticket_base += (unsigned)f.n_busy; st->idle_base += (unsigned)f.n_idle; }
             if (f.phase == 0) {
                 st->sum_tiles += (long long)L.pk[PACKET];
@@ -515,25 +548,26 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
             st->prev_rmse = rmse0;
             st->fitness = fit;
             st->rmse = rmse;
-            if (f.trace) {
+            if (!HEAD && f.trace) {
                 PEDP_GLOBAL double *tr = as_global(f.trace) + 18 * pass;
                 tr[0] = fit; tr[1] = rmse;
                 for (int k = 0; k < 16; ++k) tr[2 + k] = L.t0[k];
             }
             st->iters = pass;
             if (wide) st->n_wide = n_wide0 + 1;
+            if (HEAD) st->n_head = st->n_head + 1;
             bool stop = pass >= max_iter;
             if (pass > 0 && fabs(fit0 - fit) < rel_fitness && fabs(rmse0 - rmse) < rel_rmse) stop = true;
             if (stop) {
                 st->done = 1;
-                if (COHERENT && f.down) {  // the final state goes to the host from here (below): this lane's stores have left first
+                if (!LOCAL && COHERENT && f.down) {  // the final state goes to the host from here (below): this lane's stores have left first
                     L.stopped = 1;
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
                 stop_i = 1;
             } else {
-                PEDP_STAMP(2, 2, 0);
-                if (pass == 5) PEDP_STAMP(2, 3, 4);
+                PEDP_STAMP_CLOSE(2, 0);
+                if (pass == 5) PEDP_STAMP_CLOSE(3, 4);
                 if (K > 0.0) {
                     if (f.estimator == PEDP_POINT_TO_PLANE) {
                         double A[36], nb[6];
@@ -545,12 +579,12 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
 #pragma unroll
                         for (int u = 0; u < 6; ++u) nb[u] = -pk[21 + u];
                         const bool ok = solve6_ldlt_reg(A, nb, x);
-                        PEDP_STAMP(2, 2, 1);
+                        PEDP_STAMP_CLOSE(2, 1);
                         if (ok) {
                             if (wide) angles_i = 1;
                             else vec6_to_T(x, upd);
                         }
-                        if (!wide) PEDP_STAMP(2, 2, 2);
+                        if (!wide) PEDP_STAMP_CLOSE(2, 2);
                     } else {
                         const double *c = st->centroid;
                         double ms[3], mt[3], sig[9];
@@ -587,13 +621,13 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                     const double sa = __shfl(s, 0, 64), ca = __shfl(c, 0, 64), sb = __shfl(s, 1, 64), cb = __shfl(c, 1, 64),
                                  sc = __shfl(s, 2, 64), cc = __shfl(c, 2, 64);
                     sincos_to_T(sa, ca, sb, cb, sc, cc, x, upd);
-                    if (l0) PEDP_STAMP(2, 2, 2);
+                    if (l0) PEDP_STAMP_CLOSE(2, 2);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 16; ++k) upd[k] = bcast0(upd[k]);
                 }
-                if (l0) PEDP_STAMP(2, 0, 2);
-                if (l0 && pass == 5) PEDP_STAMP(2, 3, 5);
+                if (l0) PEDP_STAMP_CLOSE(0, 2);
+                if (l0 && pass == 5) PEDP_STAMP_CLOSE(3, 5);
                 // lane k = 4 i + j holds entry (i, j) of the update and of upd x T0 (mat4_mul_dev's sum) and stores both
                 const int i = (tid >> 2) & 3, j = tid & 3;
                 double tn = 0.0, u_ij = 0.0;
@@ -606,13 +640,13 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 }
                 if (tid < 16) {
                     st->upd[tid] = u_ij;
-                    as_global(f.hist)[16 * (pass + 1) + tid] = u_ij;
+                    if (!HEAD) as_global(f.hist)[16 * (pass + 1) + tid] = u_ij;
                     st->T[tid] = tn;
                 }
             } else {
-                PEDP_STAMP(2, 0, 2);
-                if (pass == 5) PEDP_STAMP(2, 3, 5);
-                for (int k = 0; k < 16; ++k) { st->upd[k] = upd[k]; as_global(f.hist)[16 * (pass + 1) + k] = upd[k]; }
+                PEDP_STAMP_CLOSE(0, 2);
+                if (pass == 5) PEDP_STAMP_CLOSE(3, 5);
+                for (int k = 0; k < 16; ++k) { st->upd[k] = upd[k]; if (!HEAD) as_global(f.hist)[16 * (pass + 1) + k] = upd[k]; }
                 double Tn[16];
                 mat4_mul_dev(upd, L.t0, Tn);
                 for (int k = 0; k < 16; ++k) st->T[k] = Tn[k];
@@ -642,18 +676,20 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 st->mu_tau = mu_ta;
                 st->rebuild = L.do_rebuild;
                 st->pass = pass + 1;
-                PEDP_STAMP(2, 2, 3);
-                if (pass == 5) PEDP_STAMP(2, 3, 6);
+                PEDP_STAMP_CLOSE(2, 3);
+                if (pass == 5) PEDP_STAMP_CLOSE(3, 6);
             }
         }
-        if (l0) PEDP_STAMP(2, 0, 3);
+        if (l0) PEDP_STAMP_CLOSE(0, 3);
     }
     __syncthreads();
-    if (L.do_rebuild)  // the next pass lists the live chunks anew; it resets what the old ones leave behind
-        for (int wi = tid; wi < f.n_lw; wi += NT) { as_global(f.live)[f.n_lw + wi] = load_live<COHERENT>(&f.live[wi]); as_global(f.live)[wi] = 0ull; }
+    if (!HEAD && !f.gen_masks && L.do_rebuild)  // the next pass lists the live chunks anew; it resets what the old ones leave behind
+        for (int wi = tid; wi < f.n_lw; wi += NT) { as_global(f.live_old)[wi] = load_live<COHERENT>(&f.live[wi]); as_global(f.live)[wi] = 0ull; }
+    if (!HEAD && f.gen_masks && f.known && f.k_rebuild)  // this rebuild pass is over (all have signed off): the next one ORs into the other mask
+        for (int wi = tid; wi < f.n_lw; wi += NT) as_global(f.live_old)[wi] = 0ull;
     // The registration ends here: its final state goes straight into the executor's page-locked block (read past this
     // CU's L1: lane 0's stores have reached L2, see above), so that no copy follows the last pass.
-    if (COHERENT && f.down && L.stopped)
+    if (!LOCAL && COHERENT && f.down && L.stopped)
         for (int i = tid; i < (int)(sizeof(IcpState) / sizeof(double)); i += NT) ((double *)f.down)[i] = load_sc1((const double *)st + i);
 }
 
@@ -671,7 +707,7 @@ __global__ __launch_bounds__(FIN_THREADS) void icp_finish_kernel(IcpState *st, u
     FinishArgs f;
     f.live = live; f.live_list = live_list; f.n_lw = n_lw; f.partials = partials; f.packet = packet; f.phase = phase;
     f.estimator = estimator; f.trace = trace; f.hist = hist; f.bcx = bcx; f.bcy = bcy; f.bcz = bcz;
-    f.serial = serial;
+    f.serial = serial; f.live_old = live + n_lw;
     icp_finish_body<FIN_THREADS, LIVE_CAP, false>(st, f, L, threadIdx.x);
 }
 

@@ -102,6 +102,13 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     static_assert(W == 8 && CH == 128, "a chunk is two halves of four 16-slot sub-blocks");
     const size_t pose_off = BATCH ? (size_t)blockIdx.y * a0.pose_stride : 0;
     IcpState *st = pose_ptr(st0, pose_off);
+    // A single registration works on a copy of its state in LDS (one 8-byte word per thread, requested with everything
+    // else at entry): what a pass reads of it comes from there, a close writes it there, and the closing workgroup --
+    // or, behind a head close, the service workgroup -- stores it as one block.  A batch reads its pose's state in memory.
+    __shared__ IcpState cur;
+    typedef double __attribute__((may_alias)) state_word;
+    constexpr int SWORDS = (int)(sizeof(IcpState) / sizeof(double));
+#define PEDP_ST (*(BATCH ? st : &cur))
     // The argument block (with this pose's pointers) is parked in LDS and read from there where it is
     // used: held in scalar registers for the whole kernel its 40-odd fields overflow the SGPR file,
     // and the spills -- executed at entry by EVERY launched workgroup -- left tens of MB of dirty
@@ -140,22 +147,135 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     }
     // word spheres do not depend on the chunk: the first 64 are requested before anything else and parked in LDS
     if (threadIdx.x < 64) wsph0[threadIdx.x] = a0.word_sph[(int)threadIdx.x < a0.n_words ? threadIdx.x : 0];
-    if (st->done) return;
-    const bool rebuild = st->rebuild != 0;
-    const int n_live = st->n_live, pass = st->pass;
-    const unsigned ticket_base = st->ticket_base;
+    // Head close: launch L asks for both state slots and decides from their fields alone.  Slot (L - 1) & 1 holds pass
+    // L - 1, not done and left open (no rebuild pass, not the last): close it here, then run pass L.  Else slot L & 1 holds
+    // pass L: it was closed in the launch before (or this is pass 0) -- run the pass.  Else the registration is over.
+    const bool head = !BATCH && a0.head != 0;
+    bool close_here = false;
+    if constexpr (!BATCH) {
+        IcpState *sA = st0 + (head ? (a0.launch & 1) : 0), *sB = st0 + (head ? ((a0.launch + 1) & 1) : 0);
+        double wA = 0.0, wB = 0.0;
+        if (threadIdx.x < SWORDS) {
+            wA = ((const state_word *)sA)[threadIdx.x];
+            if (head) wB = ((const state_word *)sB)[threadIdx.x];
+        }
+        if (head) {
+            // Slot (L - 1) & 1 is looked at FIRST: nobody writes it before every workgroup of this launch has read it (only
+            // an in-launch closer of pass L does, behind all tickets and sign-offs).  Slot L & 1 is being rewritten by the
+            // service workgroup while a workgroup that starts late reads it -- so it counts only where no head close happens.
+            if (a0.launch > 0 && sB->pass == a0.launch - 1 && sB->done == 0 && sB->rebuild == 0 && sB->pass < sB->max_iter) close_here = true;
+            else if (sA->pass != a0.launch || sA->done) return;
+        } else if (sA->done) return;
+        if (threadIdx.x < SWORDS) ((state_word *)&cur)[threadIdx.x] = close_here ? wB : wA;
+        __syncthreads();  // the state (and the argument block) is in LDS
+    } else {
+        if (st->done) return;
+    }
+    if (close_here) {
+        // ---- the close of pass L - 1, by every workgroup of launch L: same inputs, same float64 sequence, same bits.
+        // Plain loads: the launch boundary made the partial sums visible.  The new state stays in LDS.
+        FinishArgs f;
+        f.live = nullptr; f.live_list = nullptr; f.n_lw = 0; f.partials = a0.partials + (size_t)((a0.launch - 1) & 1) * a0.part_stride; f.packet = nullptr; f.phase = 0;
+        f.estimator = a0.estimator; f.trace = nullptr; f.hist = nullptr; f.bcx = a0.bc[0]; f.bcy = a0.bc[1]; f.bcz = a0.bc[2];
+        f.serial = 0;
+        f.known = 1; f.k_pass = a0.launch - 1; f.k_rebuild = 0; f.k_n_live = cur.n_live;
+        icp_finish_body<W * 64, 2048, false, 2>(&cur, f, fin, threadIdx.x);  // (ends behind a barrier: U and the new state are published)
+        PEDP_RT(a0.launch, 7);
+    }
+    // (what comes out of LDS is made scalar again: these live through the whole kernel)
+    auto uni = [](int v) { return BATCH ? v : __builtin_amdgcn_readfirstlane(v); };
+    auto unid = [](double v) { return BATCH ? v : bcast0(v); };
+    auto unif = [](float v) { return BATCH ? v : __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    const bool rebuild = uni(PEDP_ST.rebuild) != 0;
+    const int n_live = uni(PEDP_ST.n_live), pass = uni(PEDP_ST.pass);
+    const unsigned ticket_base = (unsigned)uni((int)PEDP_ST.ticket_base);
     const v4i vis = (pass & 1) ? vis1 : vis0;
-    const int tag_now = st->nonce + pass + 1;  // (a registration runs well under 65,535 passes; beyond that no plan is made)
-    const bool planned = !BATCH && !rebuild && vis[2] == tag_now && vis[3] == n_live;  // (all workgroups agree: the plan is written whole)
+    const int tag_now = uni(PEDP_ST.nonce) + pass + 1;  // (a registration runs well under 65,535 passes; beyond that no plan is made)
+    bool planned = !BATCH && !rebuild && vis[2] == tag_now && vis[3] == n_live;  // (all workgroups with a chunk agree: the plan is written whole)
+    // a pass left open: no ticket, no sign-off, no close in this launch
+    const bool stopped_here = close_here && uni(PEDP_ST.done) != 0;  // the head close ended the registration
+    const bool open = head && !rebuild && pass < uni(PEDP_ST.max_iter) && !stopped_here;
+    const int gdim = (int)gridDim.x - (head ? 1 : 0);  // workgroups the chunks are dealt to
+    // rebuild g ORs into live mask g & 1 and reads "was live" from the other (head close); else: the mask, and the copy made aside
+    const int mask_gen = head ? (uni(PEDP_ST.n_rebuilds) & 1) : 0;
+#define PEDP_MASK_CUR (sa.live + (size_t)mask_gen * sa.n_lw)
+#define PEDP_MASK_OLD (sa.live + (size_t)(mask_gen ^ 1) * sa.n_lw)
     // Workgroups with chunks take a ticket when they are through; the one that draws the last closes the
     // pass.  The others leave at once -- but sign off first (a counter of sixteen, each on a line of its own:
     // hundreds of atomics on one word in the first microsecond held up everybody's loads), and the closing
     // workgroup rewrites the state only after all of them have: a batch's grid is not resident at once, a
     // workgroup that starts late must not find the next pass's state.
     int n_wg = rebuild ? a0.n_chunks : n_live;
-    n_wg = n_wg < (int)gridDim.x ? n_wg : (int)gridDim.x;
+    n_wg = n_wg < gdim ? n_wg : gdim;
     n_wg = n_wg < 1 ? 1 : n_wg;  // (no live chunk at all: workgroup 0 still closes the pass)
+    // The plan of the pass after this one: the first workgroup through writes it (a pass closed in its launch), or the
+    // service workgroup (a pass left open: nobody takes a ticket).  All of it, valid or void.
+    auto write_next_plan = [&]() {
+        typedef int v2i __attribute__((ext_vector_type(2)));
+        const int tid = threadIdx.x, n_cu = sa.n_cu, extra = n_live - n_cu;
+        PEDP_GLOBAL v4i *plan = (PEDP_GLOBAL v4i *)(uintptr_t)sa.visit + (size_t)((pass + 1) & 1) * sa.visit_cap;
+        const bool want = !rebuild && pass < 65000 && extra > 0 && n_live <= 2 * n_cu && n_live <= gdim && n_live <= W * 64 && n_live <= sa.visit_cap;
+        int d = 0x7FFFFFFF, mine_ok = 1;
+        if (want && tid < n_live) {
+            const v2i e = ((const PEDP_GLOBAL v2i *)(uintptr_t)sa.dur)[(size_t)((pass + 1) & 1) * sa.visit_cap + tid];  // pass - 1 wrote this copy
+            mine_ok = e[1] == tag_now - 1;
+            d = e[0];
+        }
+        const int chunk_of_rank = (want && tid < n_live) ? as_global(sa.live_list)[tid] : 0;
+        if (__syncthreads_and(mine_ok) && want) {
+            fin.scan[tid] = d;
+            __syncthreads();
+            if (tid < n_live) {
+                int r = 0;  // rank of this chunk by (duration, live rank)
+                for (int q = 0; q < n_live; ++q) {
+                    const int dq = fin.scan[q];
+                    r += (dq < d || (dq == d && q < tid)) ? 1 : 0;
+                }
+                const int pos = r < extra ? r : (r < 2 * extra ? n_cu + (2 * extra - 1 - r) : r - extra);
+                const v4i e = {tid, chunk_of_rank, tag_now + 1, n_live};
+                plan[pos] = e;
+            }
+        } else {
+            const v4i none = {0, 0, 0, 0};
+            const int n = (int)gridDim.x < sa.visit_cap ? (int)gridDim.x : sa.visit_cap;
+            for (int i = tid; i < n; i += W * 64) plan[i] = none;
+        }
+    };
+    if (head) {
+        // A planned pass is counted when its state is made: by the head close in front of it.  (A pass whose state an
+        // in-launch close made follows a rebuild pass, or is one: never planned.)  The service workgroup has no entry
+        // of its own in the plan: it looks at entry 0.
+        const bool service = (int)blockIdx.x == n_wg;
+        if (close_here && service && !rebuild && sa.visit && sa.visit_cap > 0) {
+            const v4i e0 = ((const PEDP_GLOBAL v4i *)(uintptr_t)sa.visit)[(size_t)(pass & 1) * sa.visit_cap];
+            planned = e0[2] == tag_now && e0[3] == n_live;
+        }
+        if (close_here && planned && !stopped_here && threadIdx.x == 0) cur.n_planned += 1;
+        if (service) {
+            // ---- the service workgroup: the first without a chunk.  What the head close leaves behind: the state
+            // into its slot (the final one into the page-locked block too), the row of the trace, the history slot,
+            // the packet, and the plan of the next pass.
+            __syncthreads();
+            const int tid = threadIdx.x;
+            if (close_here) {
+                const int prev = a0.launch - 1;
+                const bool stopped = cur.done != 0;
+                if (tid < SWORDS) {
+                    const double wd = ((const state_word *)&cur)[tid];
+                    ((PEDP_GLOBAL state_word *)(uintptr_t)(st0 + (a0.launch & 1)))[tid] = wd;
+                    if (stopped && sa.down) ((state_word *)sa.down)[tid] = wd;
+                }
+                if (sa.trace && tid < 18)
+                    as_global(sa.trace)[18 * prev + tid] = tid == 0 ? cur.fitness : (tid == 1 ? cur.rmse : fin.t0[tid >= 2 ? tid - 2 : 0]);
+                if (!stopped && tid < 16) as_global(sa.hist)[16 * (prev + 1) + tid] = cur.upd[tid];
+                if (open && tid < PACKET) as_global(sa.packet)[tid] = fin.pk[tid];  // (the closer of this launch's pass writes its own)
+            }
+            if (open && sa.visit) write_next_plan();
+        }
+        if (stopped_here) return;  // the head close ended the registration: nobody runs a pass
+    }
     if ((int)blockIdx.x >= n_wg) {
+        if (open) return;
         if (a0.fuse && threadIdx.x == 0)
             __hip_atomic_fetch_add((g_u32 *)(uintptr_t)(pose_ptr(a0.ticket, pose_off) + 32 * (1 + (blockIdx.x & 15))), 1u, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -168,8 +288,20 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     const float inf = __uint_as_float(0x7F800000u);
     const double dinf = __longlong_as_double(0x7FF0000000000000ll);
     const double dnan = __longlong_as_double(0x7FF8000000000000ll);
-    const double ccx = st->centroid[0], ccy = st->centroid[1], ccz = st->centroid[2];
-    const float r_search = st->r_search;
+    // "no neighbour" in Tprev is this NaN's bits, stored as two integer words made where they are stored: as a double
+    // constant the pair was kept in registers through the chunk loop, and spilled.  (dprev's start value stays the
+    // constant: it folds into the code at compile time.)
+    auto store_nan = [](PEDP_GLOBAL double *p) {
+        int z = 0;
+        asm volatile("" : "+v"(z));
+        typedef int v2i_ __attribute__((ext_vector_type(2)));
+        const v2i_ w = {z, 0x7FF80000 | z};
+        *(PEDP_GLOBAL v2i_ *)p = w;
+    };
+    // (a batch keeps these in scalar registers; a single registration reads them from the state in LDS where they are used)
+    const double ccx_b = BATCH ? st->centroid[0] : 0.0, ccy_b = BATCH ? st->centroid[1] : 0.0, ccz_b = BATCH ? st->centroid[2] : 0.0;
+    const float r_search_b = BATCH ? st->r_search : 0.f;
+#define PEDP_CC(k, b) (BATCH ? (b) : bcast0(cur.centroid[k]))
     // A rebuild pass asks the chunks' bounding spheres first (64 of this workgroup's chunks per round, one
     // per lane, every wave for itself): a sphere moved by the pose so far that stays farther than r + margin
     // from the target's box holds no live point -- the chunk is not touched (only, if it was live before,
@@ -179,7 +311,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     if (rebuild && threadIdx.x == 0) {
         double Rs[12];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) { Rs[k] = st->T[k]; rbs[k] = Rs[k]; }
+        for (int k = 0; k < 12; ++k) { Rs[k] = PEDP_ST.T[k]; rbs[k] = Rs[k]; }
         // |R x| <= rscale |x|: the square root of the largest row sum of |R^T R| bounds the spectral norm
         double m = 0.0;
 #pragma unroll
@@ -190,7 +322,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             m = row > m ? row : m;
         }
         rbs[12] = sqrt(m) * (1.0 + 1e-9);
-        rbs[13] = sqrt(st->r2live) * (1.0 + 1e-9);
+        rbs[13] = sqrt(PEDP_ST.r2live) * (1.0 + 1e-9);
     }
     __syncthreads();  // the argument block, the word spheres (and the rebuild constants) are in LDS
     for (;;) {
@@ -213,15 +345,15 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             bool more = true;
             while (todo == 0ull) {  // wave-uniform
                 todo_base += 64;
-                if ((long long)blockIdx.x + (long long)todo_base * (long long)gridDim.x >= (long long)a.n_chunks) { more = false; break; }
-                const long long u = (long long)blockIdx.x + (long long)(todo_base + lane) * (long long)gridDim.x;
+                if ((long long)blockIdx.x + (long long)todo_base * (long long)gdim >= (long long)a.n_chunks) { more = false; break; }
+                const long long u = (long long)blockIdx.x + (long long)(todo_base + lane) * (long long)gdim;
                 bool visit = false, withdraw = false;
                 if (u < (long long)a.n_chunks) {
                     double Rs[12];
 #pragma unroll
                     for (int k = 0; k < 12; ++k) Rs[k] = rbs[k];
                     const double rscale = rbs[12], reach = rbs[13];
-                    const bool was_live = (as_global(a.live)[a.n_lw + (u >> 6)] >> (u & 63)) & 1ull;
+                    const bool was_live = (as_global(PEDP_MASK_OLD)[u >> 6] >> (u & 63)) & 1ull;
 #pragma unroll 2
                     for (int sb = 0; sb < 8; ++sb) {
                         const PEDP_GLOBAL double *sp8 = as_global(a.chunk_sph) + (size_t)(8 * u + sb) * 4;
@@ -240,17 +372,17 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 while (wd != 0ull) {  // rare: a chunk that was live and no longer is
                     const int i = __builtin_ctzll(wd);
                     wd &= wd - 1ull;
-                    const int64_t k = ((int64_t)blockIdx.x + (int64_t)(todo_base + i) * gridDim.x) * CH + tid;
+                    const int64_t k = ((int64_t)blockIdx.x + (int64_t)(todo_base + i) * gdim) * CH + tid;
                     if (tid < CH && k < a.N) as_global(a.idx_out)[as_global(a.perm)[k]] = -1;
                 }
             }
             if (!more) break;
             const int i = __builtin_ctzll(todo);
             todo &= todo - 1ull;
-            unit = (int)(blockIdx.x + (unsigned)(todo_base + i) * gridDim.x);
+            unit = (int)(blockIdx.x + (unsigned)(todo_base + i) * (unsigned)gdim);
             chunk = unit;
         } else {
-            unit = (int)(blockIdx.x + (unsigned)it * gridDim.x);
+            unit = (int)(blockIdx.x + (unsigned)it * (unsigned)gdim);
             ++it;
             if (unit >= n_live) break;
             if (planned && it == 1) { unit = vis[0]; chunk = vis[1]; }
@@ -278,16 +410,18 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 pi = as_global(a.perm)[k];
                 if (rebuild) {
                     x = as_global(a.src)[3 * (int64_t)pi]; y = as_global(a.src)[3 * (int64_t)pi + 1]; z = as_global(a.src)[3 * (int64_t)pi + 2];
-                    xform(st->T_init, x, y, z);
-                    for (int q = 1; q <= pass; ++q) xform_g(as_global(a.hist) + 16 * q, x, y, z);
+                    xform(PEDP_ST.T_init, x, y, z);
+                    // (behind a head close the last step is not in the history yet: it is the update in LDS)
+                    for (int q = 1; q <= (close_here ? pass - 1 : pass); ++q) xform_g(as_global(a.hist) + 16 * q, x, y, z);
+                    if (close_here) xform(PEDP_ST.upd, x, y, z);
                     // a chunk that was live in the pass before has that pass's neighbours (every point of a live
                     // chunk gets one, or NaN): the search radii need not start from r again
-                    if ((as_global(a.live)[a.n_lw + (chunk >> 6)] >> (chunk & 63)) & 1ull)
+                    if ((as_global(PEDP_MASK_OLD)[chunk >> 6] >> (chunk & 63)) & 1ull)
                         dprev = sqrt(dist2(x, y, z, Tp_in[3 * k], Tp_in[3 * k + 1], Tp_in[3 * k + 2]));
                 } else {
                     x = Pk_in[3 * k]; y = Pk_in[3 * k + 1]; z = Pk_in[3 * k + 2];
                     const double ux = Tp_in[3 * k], uy = Tp_in[3 * k + 1], uz = Tp_in[3 * k + 2];
-                    xform(st->upd, x, y, z);
+                    xform(PEDP_ST.upd, x, y, z);
                     // Temporal coherence: last pass's neighbour is still a target point, so the new nearest
                     // neighbour is no farther than it is now.  NaN (no neighbour last pass) fails the
                     // comparison below and leaves the full radius.
@@ -296,25 +430,25 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 const double ex = fmax(fmax(a.lo[0] - x, x - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - y, y - a.hi[1]), 0.0),
                              ez = fmax(fmax(a.lo[2] - z, z - a.hi[2]), 0.0);
                 const double d2box = ex * ex + ey * ey + ez * ez;
-                cand = d2box <= st->r2cut;   // r2cut = r^2 (1 + 1e-12): rounding-safe
-                near = d2box <= st->r2live;
+                cand = d2box <= unid(PEDP_ST.r2cut);   // r2cut = r^2 (1 + 1e-12): rounding-safe
+                near = d2box <= unid(PEDP_ST.r2live);
             }
             const unsigned long long mc = __builtin_amdgcn_ballot_w64(cand), mn = __builtin_amdgcn_ballot_w64(near);
             const int wc = __builtin_popcountll(mc);
             if (q4 == 0) {  // (the other copy: a wave of this half that comes late still reads this pass's inputs)
                 if (lane == 0) misc[half] = mn != 0ull;
                 if (valid) {  // (a rebuild pass stores every visited chunk's coordinates; only the live ones are read again)
-                    if (!cand) { as_global(a.idx_out)[pi] = -1; Tp_out[3 * k] = dnan; }
+                    if (!cand) { as_global(a.idx_out)[pi] = -1; store_nan(&Tp_out[3 * k]); }
                     Pk_out[3 * k] = x; Pk_out[3 * k + 1] = y; Pk_out[3 * k + 2] = z;
                 }
             }
             const int sl = __builtin_popcountll(mc & lt) - 16 * q4;
             if (cand && sl >= 0 && sl < 16) {
-                const float sx = (float)(x - ccx), sy = (float)(y - ccy), sz = (float)(z - ccz);
+                const float sx = (float)(x - PEDP_CC(0, ccx_b)), sy = (float)(y - PEDP_CC(1, ccy_b)), sz = (float)(z - PEDP_CC(2, ccz_b));
                 // error bound of the fp32 surrogate against the float64 distance
                 const float s1 = fabsf(sx) + fabsf(sy) + fabsf(sz);
                 const float Mi = 2.0f * s1 * a.Tn + a.T2;
-                weps[wv][sl] = 1.1920929e-7f * (5.0f * Mi + 2.0f * fminf(st->r1, s1 + a.Tn) * (a.Tn + s1)) * 1.0001f;
+                weps[wv][sl] = 1.1920929e-7f * (5.0f * Mi + 2.0f * fminf(unif(PEDP_ST.r1), s1 + a.Tn) * (a.Tn + s1)) * 1.0001f;
                 wS[wv][sl] = sx * sx + sy * sy + sz * sz;
                 wpi[wv][sl] = pi;
                 wkk[wv][sl] = half * 64 + lane;
@@ -322,6 +456,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 wcs[wv][0][sl] = sx; wcs[wv][1][sl] = sy; wcs[wv][2][sl] = sz;
                 // search radius of the slot: the distance to last pass's neighbour, rounded up, at most r
                 const float rp = (float)dprev * 1.00001f + 1e-5f * s1 + 1e-6f;
+                const float r_search = BATCH ? r_search_b : unif(cur.r_search);
                 wrho[wv][sl] = rp < r_search ? rp : r_search;
             }
             nsl = wc - 16 * q4;
@@ -335,7 +470,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 __syncthreads();  // (the flags are rewritten by the next chunk)
                 continue;
             }
-            if (tid == 0) __hip_atomic_fetch_or((g_u64 *)(uintptr_t)&a.live[chunk >> 6], 1ull << (chunk & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) __hip_atomic_fetch_or((g_u64 *)(uintptr_t)&PEDP_MASK_CUR[chunk >> 6], 1ull << (chunk & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (tid == 0) PEDP_STAMP(1, blockIdx.x, 1);
         PEDP_WV(1, __builtin_amdgcn_s_memtime());
@@ -357,7 +492,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             const float rho_j = real ? wrho[wv][j] : 0.f;
             int nn;  // nodes of the cover
             {
-                const float big = 3e38f, wr = st->wide_radius;
+                const float big = 3e38f, wr = unif(PEDP_ST.wide_radius);
                 float lx = real ? px : big, hx = real ? px : -big, ly = real ? py : big, hy = real ? py : -big,
                       lz = real ? pz : big, hz = real ? pz : -big, rmx = rho_j;
                 // level 0: the point itself, widened by the rounding of its centred coordinates
@@ -523,7 +658,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             const double qx = wp[wv][0][j], qy = wp[wv][1][j], qz = wp[wv][2][j];
             float mg = fminf(b1, __shfl_xor(b1, 16, 64));
             mg = fminf(mg, __shfl_xor(mg, 32, 64));
-            const bool maybe = real && mg + Si <= st->r2f + 4.0f * e + 4.8e-7f * Si;  // else certainly farther than r
+            const bool maybe = real && mg + Si <= unif(PEDP_ST.r2f) + 4.0f * e + 4.8e-7f * Si;  // else certainly farther than r
             const float win = mg + 2.0f * e;
             double bd = dinf;
             int bj = 0x7FFFFFFF;
@@ -640,11 +775,11 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             int jn = fj;
             const double dd = fd;
             if (i >= 0) {
-                if (jn >= 0 && !(dd < st->r2)) jn = -1;  // strict, as SearchHybrid's lower_bound
+                if (jn >= 0 && !(dd < unid(PEDP_ST.r2))) jn = -1;  // strict, as SearchHybrid's lower_bound
                 const int64_t kp = (int64_t)chunk * CH + wkk[wv][j];
                 if (g == 0) {
                     as_global(a.idx_out)[i] = jn;
-                    if (jn < 0) Tp_out[3 * kp] = dnan;
+                    if (jn < 0) store_nan(&Tp_out[3 * kp]);
                 }
                 if (jn >= 0) {
                     const double sx = wp[wv][0][j], sy = wp[wv][1][j], sz = wp[wv][2][j];
@@ -673,6 +808,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
 #pragma unroll
                         for (int u = 0; u < 6; ++u) PEDP_PUT(21 + u, J[u] * r);
                     } else {
+                        const double ccx = PEDP_CC(0, ccx_b), ccy = PEDP_CC(1, ccy_b), ccz = PEDP_CC(2, ccz_b);
                         const double s3[3] = {sx - ccx, sy - ccy, sz - ccz}, t3[3] = {tx - ccx, ty - ccy, tz - ccz};
 #pragma unroll
                         for (int u = 0; u < 3; ++u) { PEDP_PUT(u, s3[u]); PEDP_PUT(3 + u, t3[u]); }
@@ -704,8 +840,8 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             double v = 0.0;
 #pragma unroll
             for (int w = 0; w < W; ++w) v += accsh[w][tid];
-            double *dst = &a.partials[(size_t)unit * PSTRIDE + tid];
-            if (a.fuse) store_sc1(dst, v);
+            double *dst = &a.partials[(head ? (size_t)(pass & 1) * a.part_stride : 0) + (size_t)unit * PSTRIDE + tid];
+            if (a.fuse && !open) store_sc1(dst, v);  // (an open pass: the launch boundary hands the sums over)
             else *as_global(dst) = v;
         }
         if (!BATCH && !rebuild && tid == 0 && a.dur && unit < a.visit_cap) {
@@ -724,7 +860,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
         __syncthreads();  // the waves' sums are reused by the next chunk
     }
     PEDP_RT(pass, 2);
-    if (!a.fuse) return;
+    if (!a.fuse || open) return;
     // ---- the pass is closed by the workgroup that finishes last
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its stores have left
     __syncthreads();
@@ -736,52 +872,41 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     __syncthreads();
     PEDP_RT(pass, 3);
     if (!BATCH && misc[5] && !misc[4] && a.visit) {
-        // ---- the first workgroup through writes the next pass's visit plan: all of it, valid or not
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        const int tid = threadIdx.x, n_cu = a.n_cu, extra = n_live - n_cu;
-        PEDP_GLOBAL v4i *plan = (PEDP_GLOBAL v4i *)(uintptr_t)a.visit + (size_t)((pass + 1) & 1) * a.visit_cap;
-        const bool want = !rebuild && pass < 65000 && extra > 0 && n_live <= 2 * n_cu && n_live <= (int)gridDim.x && n_live <= W * 64 && n_live <= a.visit_cap;
-        int d = 0x7FFFFFFF, mine_ok = 1;
-        if (want && tid < n_live) {
-            const v2i e = ((const PEDP_GLOBAL v2i *)(uintptr_t)a.dur)[(size_t)((pass + 1) & 1) * a.visit_cap + tid];  // pass - 1 wrote this copy
-            mine_ok = e[1] == tag_now - 1;
-            d = e[0];
-        }
-        const int chunk_of_rank = (want && tid < n_live) ? as_global(a.live_list)[tid] : 0;
-        if (__syncthreads_and(mine_ok) && want) {
-            fin.scan[tid] = d;
-            __syncthreads();
-            if (tid < n_live) {
-                int r = 0;  // rank of this chunk by (duration, live rank)
-                for (int q = 0; q < n_live; ++q) {
-                    const int dq = fin.scan[q];
-                    r += (dq < d || (dq == d && q < tid)) ? 1 : 0;
-                }
-                const int pos = r < extra ? r : (r < 2 * extra ? n_cu + (2 * extra - 1 - r) : r - extra);
-                const v4i e = {tid, chunk_of_rank, tag_now + 1, n_live};
-                plan[pos] = e;
-            }
-        } else {
-            const v4i none = {0, 0, 0, 0};
-            const int n = (int)gridDim.x < a.visit_cap ? (int)gridDim.x : a.visit_cap;
-            for (int i = tid; i < n; i += W * 64) plan[i] = none;
-        }
+        // ---- the first workgroup through writes the next pass's visit plan
+        write_next_plan();
         return;
     }
     if (!misc[4]) return;
 
     if (threadIdx.x == 0) PEDP_STAMP(1, blockIdx.x, 6);
     FinishArgs f;
-    f.live = a.live; f.live_list = a.live_list; f.n_lw = a.n_lw; f.partials = a.partials; f.packet = a.packet; f.phase = 0;
+    f.live = PEDP_MASK_CUR; f.live_old = PEDP_MASK_OLD; f.gen_masks = head ? 1 : 0; f.live_list = a.live_list; f.n_lw = a.n_lw; f.partials = a.partials + (head ? (size_t)(pass & 1) * a.part_stride : 0); f.packet = a.packet; f.phase = 0;
     f.estimator = a.estimator; f.trace = a.trace; f.hist = a.hist; f.bcx = a.bc[0]; f.bcy = a.bc[1]; f.bcz = a.bc[2];
     f.idle = a.ticket + 32;
     f.n_idle = (int)gridDim.x - n_wg;
     f.n_busy = n_wg;
-    if (!BATCH && planned && threadIdx.x == 0) st->n_planned += 1;
+    if (!BATCH && !head && planned && threadIdx.x == 0) cur.n_planned += 1;  // (head close: counted where the pass's state was made)
     f.down = BATCH ? nullptr : a.down; f.serial = a.serial_close;
     f.known = 1; f.k_pass = pass; f.k_rebuild = rebuild ? 1 : 0; f.k_n_live = n_live;
-    icp_finish_body<W * 64, 2048, true>(st, f, fin, threadIdx.x);
+    if constexpr (BATCH) {
+        icp_finish_body<W * 64, 2048, true>(st, f, fin, threadIdx.x);
+    } else {
+        // the close works on the state in LDS; the state goes to its slot -- with the head close the one pass + 1 names -- as
+        // one block, and, when the registration ends here, into the executor's page-locked block as well
+        icp_finish_body<W * 64, 2048, true, 1>(&cur, f, fin, threadIdx.x);
+        __syncthreads();
+        IcpState *out = head ? st0 + ((pass + 1) & 1) : st0;
+        if (threadIdx.x < SWORDS) {
+            const double wd = ((const state_word *)&cur)[threadIdx.x];
+            ((PEDP_GLOBAL state_word *)(uintptr_t)out)[threadIdx.x] = wd;
+            if (cur.done != 0 && a.down) ((state_word *)a.down)[threadIdx.x] = wd;
+        }
+    }
     PEDP_RT(pass, 4);
+#undef PEDP_ST
+#undef PEDP_CC
+#undef PEDP_MASK_CUR
+#undef PEDP_MASK_OLD
 }
 
 // Start states of a batch's group: from the page-locked block straight into the poses' state slots (G blocks
@@ -809,8 +934,15 @@ __global__ __launch_bounds__(256) void batch_state_gather_kernel(const char *__r
 // One launch in front of pass 0 instead of a copy and a fill.
 __global__ __launch_bounds__(256) void icp_state_start_kernel(const unsigned long long *__restrict__ up, unsigned long long *__restrict__ st,
                                                               int state_words, unsigned long long *__restrict__ zero, int zero_words,
-                                                              unsigned long long *__restrict__ plan, int plan_words) {
-    for (int i = threadIdx.x; i < state_words; i += blockDim.x) st[i] = up[i];
+                                                              unsigned long long *__restrict__ plan, int plan_words, int slots) {
+    for (int i = threadIdx.x; i < state_words; i += blockDim.x) {
+        unsigned long long v = up[i];
+        st[i] = v;
+        if (slots > 1) {  // the second slot of the state: the same parameters, and no pass (-1)
+            if (i == (int)(offsetof(IcpState, pass) / 8)) v |= 0xFFFFFFFFull << (8 * (offsetof(IcpState, pass) % 8));
+            st[state_words + i] = v;
+        }
+    }
     for (int i = threadIdx.x; i < zero_words; i += blockDim.x) zero[i] = 0ull;
     for (int i = threadIdx.x; i < plan_words; i += blockDim.x) plan[i] = 0ull;
 }

@@ -170,7 +170,7 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
     // what only the segmented (dense / large-radius) path uses shrinks to nothing in the fused pass,
     // which keeps a chunk's slots, masks and triples in LDS
     const size_t seg_only = fused ? 0 : 1;
-    take(w.st, sizeof(IcpState));
+    take(w.st, 2 * sizeof(IcpState));  // two slots by pass parity (head close); every other path keeps to the first
     take(w.P, sizeof(double) * 3 * (size_t)w.Ns_pad * seg_only);
     take(w.d2, sizeof(double) * (size_t)w.Ns_pad * seg_only);
     take(w.partials, sizeof(double) * ACC_BLOCKS * PACKET);
@@ -197,7 +197,7 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
         take(w.Pk, sizeof(double) * 3 * (size_t)w.Ns_pad * 2);     // read from [pass & 1], written to the other: no wave
         take(w.Tprev, sizeof(double) * 3 * (size_t)w.Ns_pad * 2);  // ever reads what a faster wave of the same pass has rewritten
         take(w.hist, sizeof(double) * 16 * (size_t)iter_capacity(max_iter));
-        take(w.cpart, sizeof(double) * PSTRIDE * (size_t)w.blocks_cap);
+        take(w.cpart, sizeof(double) * PSTRIDE * (size_t)w.blocks_cap * 2);  // two copies by pass parity (head close; else the first)
         // the ticket and the sixteen sign-off counters, a line each, and the live masks right behind them: one span
         // that starts every registration at zero (zeroed_span_bytes) -- nothing may come between these two
         take(w.ticket, 17 * 128);
@@ -269,9 +269,9 @@ inline IcpRadii icp_radii(double r, double r_cull) {
 }
 
 // An environment switch: set, and to something other than 0.  (The switches below each ask once per process.)
-inline bool env_flag(const char *name) {
+inline bool env_flag(const char *name, bool unset = false) {
     const char *v = getenv(name);
-    return v && atoi(v) != 0;
+    return v ? atoi(v) != 0 : unset;
 }
 inline bool nn_bf16_sweep() {  // PEDP_NN_F32=1: the dense sweep on the f32-input MFMA (A/B, tests)
     static const bool off = env_flag("PEDP_NN_F32");
@@ -298,6 +298,14 @@ inline bool serial_close() {
 // and the closing workgroup's own write of the final state
 inline bool copy_bracket() {
     static const bool m = env_flag("PEDP_ICP_COPY_BRACKET");
+    return m;
+}
+
+// PEDP_ICP_HEAD_CLOSE=0: every pass is closed inside its own launch again.  (Default: a single registration on the fused
+// path, with the wide close and the final state written by the device, leaves its steady passes open; the next launch
+// closes them at its head, see fused_close.h.)
+inline bool head_close() {
+    static const bool m = env_flag("PEDP_ICP_HEAD_CLOSE", true);
     return m;
 }
 
@@ -373,7 +381,7 @@ inline double fused_margin(double r) { return 2.0 * r; }   // (1 r ... 4 r measu
 // (sum, solve, update); otherwise icp_finish_kernel launches follow (exchange step in between).
 int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_cloud_t tgt, int estimator,
                        const TargetPrep &tp, hipEvent_t ev0, hipEvent_t ev1, bool fuse, double *trace, int poses = 1,
-                       unsigned long long *down = nullptr) {
+                       unsigned long long *down = nullptr, int head_launch = -1) {
     PassArgs pa;
     pa.src = src->pts; pa.perm = w.src_perm; pa.N = src->N; pa.n_chunks = w.n_chunks;
     pa.hist = w.hist; pa.Pk = w.Pk; pa.Tprev = w.Tprev; pa.live = w.live; pa.live_list = w.live_list;
@@ -389,11 +397,15 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pe
     pa.fuse = fuse && !unfused_finish() ? 1 : 0; pa.n_lw = w.n_lw; pa.packet = w.packet; pa.trace = trace; pa.ticket = w.ticket;
     const bool plan = poses <= 1 && !no_visit_plan();
     pa.down = poses <= 1 && pa.fuse ? down : nullptr; pa.serial_close = serial_close() ? 1 : 0;
+    // head close: the launch index, and one workgroup more than the chunks can fill (the service workgroup)
+    pa.head = head_launch >= 0 ? 1 : 0; pa.launch = pa.head ? head_launch : 0;
+    pa.part_stride = (size_t)PSTRIDE * (size_t)w.blocks_cap;
     pa.visit = plan ? w.visit : nullptr; pa.dur = plan ? w.dur : nullptr; pa.visit_cap = w.visit_cap; pa.n_cu = c->num_cus;
     // grid-stride loop over the live chunks: any grid is correct; two workgroups per CU are resident
     int64_t g = w.n_chunks;
     if (g > 2 * c->num_cus) g = 2 * c->num_cus;
     if (g < 1) g = 1;
+    if (pa.head) g += 1;
     if (ev0) PEDP_HIP_CHECK(hipEventRecord(ev0, c->stream));
     if (poses > 1)
         hipLaunchKernelGGL((icp_pass_kernel<BK_W, true>), dim3((unsigned)g, (unsigned)poses), dim3(BK_W * 64), 0, c->stream, w.st, pa);
@@ -636,6 +648,9 @@ struct IcpJob {
     // bytes in (the start state is read from the block's first bytes while the passes run); false: a copy brings it
     // to the block's start
     bool dev_result = false;
+    // steady passes are left open and closed at the head of the next launch (fused_close.h); decided once, here: the
+    // kernels' slots and the slots the host looks at follow from this one flag
+    bool head = false;
 };
 constexpr size_t RESULT_OFF = 2048;
 static_assert(sizeof(IcpState) <= RESULT_OFF && sizeof(IcpState) % 8 == 0, "start and final state share the block's first 4 KB, as 8-byte words");
@@ -687,6 +702,7 @@ int icp_job_setup(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const 
     const bool fused = job.qt == 1 && !job.exhaustive && r > 0.0 && job.Ns > 0 && job.Nt > 0 &&
                        (job.Nt + 1023) / 1024 <= BK_WCAP;
     job.dev_result = fused && !prm->allreduce && !prm->use_comm && !unfused_finish() && !copy_bracket();
+    job.head = job.dev_result && !serial_close() && head_close();
     int rc = carve_workspace(x, job.Ns, job.Nt, job.max_iter, job.qt, w, fused);
     if (rc) return rc;
     bind_clouds(w, source, target, job.qt);
@@ -783,6 +799,8 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
     const double ng = n_global > 0 ? n_global : 1.0;
     const bool exchange = prm->allreduce || prm->use_comm;  // the packet is summed over ranks before the solve
     const bool fused = w.fused && !degenerate;
+    const bool head = fused && job.head;
+    int launches = 0;
     double *trace = want_trace ? w.trace : nullptr;
     if (fused) {
         // tickets, sign-off counters and both live masks start at zero: one memset (they lie one behind the other); the
@@ -793,10 +811,10 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
         else  // state, zeroes and an empty visit plan in one launch (the plan and the durations lie one behind the other)
             hipLaunchKernelGGL(icp_state_start_kernel, dim3(1), dim3(256), 0, x->stream, (const unsigned long long *)hp, (unsigned long long *)w.st,
                                (int)(sizeof(IcpState) / 8), (unsigned long long *)w.ticket, (int)(zeroed_span_bytes(w) / 8),
-                               (unsigned long long *)w.visit, (int)(plan_span_bytes(w) / 8));
+                               (unsigned long long *)w.visit, (int)(plan_span_bytes(w) / 8), head ? 2 : 1);
     } else if (!copy_bracket()) {
         hipLaunchKernelGGL(icp_state_start_kernel, dim3(1), dim3(256), 0, x->stream, (const unsigned long long *)hp, (unsigned long long *)w.st,
-                           (int)(sizeof(IcpState) / 8), (unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, 0);
+                           (int)(sizeof(IcpState) / 8), (unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, 0, 1);
     }
     PEDP_HIP_CHECK(hipGetLastError());
     if (job.timed_pass != -1) { x->nn_pairs = 0; x->nn_span_launches = 1; }
@@ -804,8 +822,9 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
         hipEvent_t ev0, ev1;
         rc = pass_timing_events(x, job.timed_pass, pass, max_iter, ev0, ev1);
         if (rc) return rc;
+        x->icp_last_launches = ++launches;  // passes enqueued (statistics: the early exit stops enqueuing)
         if (fused) {
-            rc = enqueue_fused_pass(x, w, source, target, prm->estimator, tp, ev0, ev1, !exchange, trace, 1, down);
+            rc = enqueue_fused_pass(x, w, source, target, prm->estimator, tp, ev0, ev1, !exchange, trace, 1, down, head ? pass : -1);
             if (rc) return rc;
             if (!exchange && unfused_finish()) launch_finish(x, w, tp, 1, 0, prm->estimator, trace, 0);
             if (exchange) {  // sum -> all-reduce over the ranks -> solve
@@ -840,9 +859,14 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
         // on every rank of a sharded run) and stop enqueuing once it is set.
         if (early_stop && prm->relative_fitness >= 0.0 && (pass & 7) == 7 && pass < max_iter) {
             int *flag = (int *)((char *)x->pinned + 4096);
+            // (head close: the slot this pass's index names -- the one a head close in this launch wrote)
+            // (head close: whoever ends the registration writes `done` into the slot of the pass behind the one it closed,
+            // either parity; the other slot's `done` stays 0 -- both are read)
+            flag[1] = 0;
             PEDP_HIP_CHECK(hipMemcpyAsync(flag, &w.st->done, sizeof(int), hipMemcpyDeviceToHost, x->stream));
+            if (head) PEDP_HIP_CHECK(hipMemcpyAsync(flag + 1, &(w.st + 1)->done, sizeof(int), hipMemcpyDeviceToHost, x->stream));
             PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
-            if (*flag) break;
+            if (flag[0] || flag[1]) break;
         }
     }
     if (!job.dev_result) PEDP_HIP_CHECK(hipMemcpyAsync(hp, w.st, sizeof(IcpState), hipMemcpyDeviceToHost, x->stream));
@@ -892,6 +916,8 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     x->icp_last_passes = hp->iters + 1;
     x->icp_last_planned = hp->n_planned;
     x->icp_last_wide = hp->n_wide;
+    x->icp_last_head = hp->n_head;
+    x->icp_last_rebuilds = hp->n_rebuilds;
     x->icp_last_bracket = (copy_bracket() ? 0 : 1) + (job.dev_result ? 2 : 0);
     x->icp_last_nt = job.Nt;
     if (fitness) *fitness = hp->fitness;
@@ -1397,6 +1423,14 @@ int pedp_icp_last_serial_path(pedp_ctx_t c, int64_t *wide_closes, int64_t *brack
     PEDP_REQUIRE(c && wide_closes && bracket, "pedp_icp_last_serial_path: null argument");
     *wide_closes = c->icp_last_wide;
     *bracket = c->icp_last_bracket;
+    return PEDP_OK;
+}
+
+int pedp_icp_last_head_closed(pedp_ctx_t c, int64_t *head_closed, int64_t *rebuilds, int64_t *launches) {
+    PEDP_REQUIRE(c && head_closed, "pedp_icp_last_head_closed: null argument");
+    *head_closed = c->icp_last_head;
+    if (rebuilds) *rebuilds = c->icp_last_rebuilds;
+    if (launches) *launches = c->icp_last_launches;
     return PEDP_OK;
 }
 

@@ -521,6 +521,17 @@ int pedp_icp_graph_captures(pedp_ctx_t ctx, int64_t *captures);
  * or the ICP workspace returns PEDP_ERR_BAD_ARG while a registration is pending. */
 int pedp_icp_last_serial_path(pedp_ctx_t ctx, int64_t *wide_closes, int64_t *bracket);
 
+/* Passes of the last single registration collected on `ctx` that were closed at the head of the next launch: a steady
+ * pass of a fused registration ends with its partial sums, and every workgroup of the next launch sums them, solves
+ * and updates the pose before it transforms its chunk -- no ticket, no sign-off, no state handed over inside a launch.
+ * Rebuild passes and the last pass close in their own launch: passes - rebuild passes - 1 here.  0 with
+ * PEDP_ICP_HEAD_CLOSE=0, with PEDP_ICP_SERIAL_CLOSE=1 or PEDP_ICP_COPY_BRACKET=1, for batches and sharded registrations.
+ * rebuilds (may be null): rebuilds of the live chunk set that registration asked for after pass 0 (fused path).
+ * launches (may be null): passes the last single registration enqueued on `ctx` -- max_iteration + 1, fewer where
+ * pedp_icp's early-exit look (every 8th pass) saw the registration done.
+ * Results do not change in any bit (tests/test_icp_head_close_gpu.py compares). */
+int pedp_icp_last_head_closed(pedp_ctx_t ctx, int64_t *head_closed, int64_t *rebuilds, int64_t *launches);
+
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
  * g[i * n_tgt + j] = |t'_j|^2 - 2 s'_i . t'_j exactly as the sweep's v_mfma_f32_16x16x32_bf16 produces it (same operand packing). */

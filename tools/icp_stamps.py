@@ -72,8 +72,22 @@ if hasattr(lib, "pedp_debug_icp_rt") and lib.pedp_debug_icp_rt(C.c_void_p(rt.cty
         e0 = r[on, 0].min()
         last = r[on, 4].max()
         us = lambda t: (t - e0) / 100.0
+        # The table is not cleared between registrations and holds 512 workgroups: rows of an earlier registration's rebuild
+        # pass (a larger grid) are told apart by age -- a launch is over within 50 us of its last entry -- and workgroup
+        # 512 (the service workgroup of a rebuild pass on a full grid) is never stamped.
+        on &= r[:, 0] >= r[on, 0].max() - 5000
+        e0 = r[on, 0].min()
+        last = r[on, 4].max()
+        in_launch = last > e0   # a pass left open takes no ticket and is closed by the next launch's head
         line = (f"pass {p:2d}: {on.sum():3d} workgroups; entry spread {us(r[on,0].max()):5.2f}; state read (median) {np.median(us(r[on,1])):5.2f}; "
-                f"chunks done median {np.median(us(r[on,2])):6.2f} max {us(r[on,2].max()):6.2f}; ticket back max {us(r[on,3].max()):6.2f}; closed {us(last):6.2f}")
+                f"chunks done median {np.median(us(r[on,2])):6.2f} max {us(r[on,2].max()):6.2f}; "
+                + (f"ticket back max {us(r[on,3].max()):6.2f}; closed {us(last):6.2f}" if in_launch else "left open"))
+        if not in_launch:
+            last = r[on, 2].max()
+        hc = on & (r[:, 7] > 0)
+        if hc.any():  # this launch began with the head close of the pass before
+            line += (f"; head close: loads back median {np.median(us(r[hc,5])):5.2f} max {us(r[hc,5].max()):5.2f}, sums done median {np.median(us(r[hc,6])):5.2f}, "
+                     f"U published median {np.median(us(r[hc,7])):5.2f} max {us(r[hc,7].max()):5.2f}")
         if prev_close is not None:
             line += f"; boundary (closed -> next entry) {(e0 - prev_close) / 100.0:5.2f}"
         prev_close = last
