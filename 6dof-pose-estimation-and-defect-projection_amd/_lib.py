@@ -163,6 +163,8 @@ PROTOTYPES = {
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "pedp_conv2d_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_mha_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_linear_f16": (C.c_int, [C.c_void_p] * 10),
+    "pedp_token_pool_f16": (C.c_int, [C.c_void_p] * 6),
     "pedp_cluster_poses": (C.c_int, [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, _P(C.c_int)]),
 }
@@ -371,6 +373,19 @@ class MhaParams(C.Structure):
                 ("k_ld", C.c_int32), ("v_ld", C.c_int32), ("o_ld", C.c_int32), ("scale", C.c_float)]
 
 
+class LinearParams(C.Structure):
+    """pedp_linear_params (include/pedp.h)."""
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("x_ld", C.c_int32), ("y_ld", C.c_int32),
+                ("res_ld", C.c_int32), ("epilogue", C.c_int32), ("pos_rows", C.c_int32), ("pos_period", C.c_int32),
+                ("pos_a", C.c_int32), ("eps", C.c_float)]
+
+
+class TokenPoolParams(C.Structure):
+    """pedp_token_pool_params (include/pedp.h)."""
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("E", C.c_int32), ("x_ld", C.c_int32), ("n_out", C.c_int32)]
+
+
+LINEAR_PLAIN, LINEAR_RELU, LINEAR_ADD_LN = 0, 1, 2
 TRANS_TRACKNET, TRANS_RAW = 0, 1
 ROT_AXIS_ANGLE, ROT_6D = 0, 1
 

@@ -32,6 +32,7 @@ SOURCES = {
     "pedp_estimator.hip": [],
     "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+    "pedp_linear.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_cluster.cpp": [],
 }
 HEADERS = ["pedp_internal.h", os.path.join("..", "..", "include", "pedp.h")]

@@ -20,6 +20,12 @@ the refiner's two encoder layers and of the scorer's `att` and `att_cross` runs 
 two projection GEMMs around the fused kernel, and no S x S weights are formed.  The default is heads='torch', the stock
 modules; in every other case they run whatever `heads` says.
 
+The heads' linear layers.  With linears='hip' together with heads='hip', under the same conditions, the
+projections, the feed-forward, both LayerNorms, the position table's add and the final mean and Linear run through
+linear.linear, linear.linear_add_norm and linear.token_pool on kept float16 buffers: a refiner head is six launches, and
+neither F.linear nor F.layer_norm is called from the heads.  The packed float16 weights live with the packed
+convolutions.  The default is linears='torch'.
+
 The stride-2 layers.  With strided='hip', under the same conditions, the three convolutions that halve
 the resolution run through conv.conv_stem and conv.conv_strided: the 7x7 stem reads A and B as they arrive (no cat, no
 NCHW intermediate, no conversion pass) and the forward is channels-last float16 on kept buffers from the crops to the
@@ -33,10 +39,12 @@ import torch.nn as nn
 
 from . import attention as _attn
 from . import conv as _conv
+from . import linear as _lin
 
 _BACKENDS = ("auto", "hip", "torch")
 _HEADS = ("torch", "hip")
 _STRIDED = ("torch", "hip")
+_LINEARS = ("torch", "hip")
 
 # backend 'auto': which path a block convolution of this many channels takes -- the kernel where tools/networks_time.py
 # finds it not slower than F.conv2d on the same channels-last float16 tensors, torch otherwise.
@@ -139,13 +147,16 @@ class _PairNet(nn.Module):
 
     _enc_names = ("", "")
 
-    def _init_backend(self, backend, heads="torch", strided="torch"):
-        # id(conv) -> PackedConv3x3 | PackedConv | None (None: a block layer the kernel does not take, kept on torch)
+    def _init_backend(self, backend, heads="torch", strided="torch", linears="torch"):
+        # id(conv) -> PackedConv3x3 | PackedConv | None (None: a block layer the kernel does not take, kept on torch);
+        # id(a head's module) -> its packed linears (linear.pack_*)
         self._packed = {}
         self._buffers_nhwc = {}
+        self._buffers_tok = {}
         self.set_backend(backend)
         self.set_heads(heads)
         self.set_strided(strided)
+        self.set_linears(linears)
 
     def set_backend(self, backend):
         """'hip': every block convolution through the kernel; 'torch': none; 'auto': per layer by the measured table."""
@@ -170,12 +181,50 @@ class _PairNet(nn.Module):
         self.strided = strided
         return self
 
+    def set_linears(self, linears):
+        """'hip': with heads='hip', the heads' linear layers, LayerNorms and means through linear.linear, linear_add_norm
+        and token_pool (eval, GPU, float16 autocast); 'torch': the stock modules."""
+        if linears not in _LINEARS:
+            raise ValueError(f"linears must be one of {_LINEARS}, got {linears!r}")
+        self.linears = linears
+        return self
+
     def _heads_fused(self, x):
         return self.heads == "hip" and not self.training and x.is_cuda and _fp16_autocast()
+
+    def _linears_fused(self, x):
+        return self.linears == "hip" and self._heads_fused(x)
 
     def drop_packed(self):
         self._packed = {}
         self._buffers_nhwc = {}
+        self._buffers_tok = {}
+
+    def _pack_head(self, module, pack):
+        key = id(module)
+        if key not in self._packed:
+            self._packed[key] = pack(module)
+        return self._packed[key]
+
+    def _tokens(self, tok, names=("qkv", "a", "y")):
+        """The tokens of `encode` as contiguous float16 and the kept buffers `names` of the heads at this batch and length:
+        'qkv' bs x S x 1536, 'a' and 'y' bs x S x 512."""
+        bs, s, e = (int(v) for v in tok.shape)
+        key = (tok.device, bs, s)
+        buf = self._buffers_tok.get(key)
+        if buf is None:
+            if len(self._buffers_tok) >= 4:
+                self._buffers_tok.clear()
+            with torch.inference_mode(False):
+                buf = self._buffers_tok[key] = {n: torch.empty((bs, s, 3 * e if n == "qkv" else e), dtype=torch.float16,
+                                                               device=tok.device) for n in names}
+        if tok.dtype != torch.float16 or not tok.is_contiguous():      # the torch encoder's channels-first result
+            if "tok" not in buf:
+                with torch.inference_mode(False):
+                    buf["tok"] = torch.empty((bs, s, e), dtype=torch.float16, device=tok.device)
+            buf["tok"].copy_(tok)
+            tok = buf["tok"]
+        return tok, buf
 
     def train(self, mode=True):
         self.drop_packed()
@@ -312,7 +361,7 @@ class RefineNet(_PairNet):
 
     _enc_names = ("encodeA", "encodeAB")
 
-    def __init__(self, cfg=None, c_in=None, n_view=1, backend="auto", heads="torch", strided="torch"):
+    def __init__(self, cfg=None, c_in=None, n_view=1, backend="auto", heads="torch", strided="torch", linears="torch"):
         super().__init__()
         self.cfg = cfg
         norm = bool(_get(cfg, "use_BN", False))
@@ -327,10 +376,20 @@ class RefineNet(_PairNet):
                                         nn.Linear(512, 3))
         self.rot_head = nn.Sequential(nn.TransformerEncoderLayer(d_model=512, nhead=4, dim_feedforward=512, batch_first=True),
                                       nn.Linear(512, 3 if rot_rep == "axis_angle" else 6))
-        self._init_backend(backend, heads, strided)
+        self._init_backend(backend, heads, strided, linears)
+
+    def _head_fused(self, head, tok, buf):
+        """A head on the raw tokens: the encoder layer in five launches, then the mean and the final Linear in one."""
+        y = _lin.encoder_layer_fused(head[0], tok, self._pack_head(head[0], _lin.pack_encoder_layer), self.pos_embed.pe,
+                                     tok.shape[1], qkv=buf["qkv"], attn=buf["a"], out=buf["y"])
+        return _lin.token_pool(y, len(tok), self._pack_head(head[1], _lin.pack_f32))
 
     def forward(self, A, B):
-        ab = self.pos_embed(self.encode(A, B))
+        tok = self.encode(A, B)
+        if self._linears_fused(tok):
+            tok, buf = self._tokens(tok)
+            return {"trans": self._head_fused(self.trans_head, tok, buf), "rot": self._head_fused(self.rot_head, tok, buf)}
+        ab = self.pos_embed(tok)
         if self._heads_fused(ab):
             trans = self.trans_head[1](_attn.encoder_layer(self.trans_head[0], ab))
             rot = self.rot_head[1](_attn.encoder_layer(self.rot_head[0], ab))
@@ -343,7 +402,7 @@ class ScoreNetMultiPair(_PairNet):
 
     _enc_names = ("encoderA", "encoderAB")
 
-    def __init__(self, cfg=None, c_in=None, backend="auto", heads="torch", strided="torch"):
+    def __init__(self, cfg=None, c_in=None, backend="auto", heads="torch", strided="torch", linears="torch"):
         super().__init__()
         self.cfg = cfg
         norm = bool(_get(cfg, "use_BN", False))
@@ -354,7 +413,7 @@ class ScoreNetMultiPair(_PairNet):
         self.att_cross = nn.MultiheadAttention(embed_dim=512, num_heads=4, bias=True, batch_first=True)
         self.pos_embed = _PositionTable(512, 400)
         self.linear = nn.Linear(512, 1)
-        self._init_backend(backend, heads, strided)
+        self._init_backend(backend, heads, strided, linears)
 
     def _attend(self, mha, x):
         if self._heads_fused(x):
@@ -363,13 +422,21 @@ class ScoreNetMultiPair(_PairNet):
 
     def extract_feat(self, A, B):
         """A, B: (B*L) x C x H x W -> one 512-vector per pair."""
-        ab = self.pos_embed(self.encode(A, B))
+        tok = self.encode(A, B)
+        if self._linears_fused(tok):
+            tok, buf = self._tokens(tok, ("qkv", "a"))
+            return _lin.attention_pooled_fused(self.att, tok, self._pack_head(self.att, _lin.pack_attention), self.pos_embed.pe,
+                                               tok.shape[1], qkv=buf["qkv"], attn=buf["a"])
+        ab = self.pos_embed(tok)
         ab = self._attend(self.att, ab)
         return ab.mean(dim=1).reshape(len(A), -1)
 
     def forward(self, A, B, L):
         bs = A.shape[0] // L
         x = self.extract_feat(A, B).reshape(bs, L, -1)
+        if self._linears_fused(x):
+            o = _lin.self_attention_fused(self.att_cross, x, self._pack_head(self.att_cross, _lin.pack_attention))
+            return {"score_logit": _lin.token_pool(o, bs * L, self._pack_head(self.linear, _lin.pack_f32)).reshape(bs, L)}
         x = self._attend(self.att_cross, x)
         return {"score_logit": self.linear(x).reshape(bs, L)}
 
@@ -384,12 +451,12 @@ def _load(net, path_or_state, device):
     return net.to(device).eval()
 
 
-def load_refiner(path_or_state, cfg, backend="auto", device="cuda", heads="torch", strided="torch"):
+def load_refiner(path_or_state, cfg, backend="auto", device="cuda", heads="torch", strided="torch", linears="torch"):
     """RefineNet(cfg) with a checkpoint (a path, a state dict, or {'model': state dict}) loaded strictly, on the GPU in
     eval mode: `PoseRefinePredictor(model=load_refiner(path, cfg), cfg=cfg)`."""
-    return _load(RefineNet(cfg, backend=backend, heads=heads, strided=strided), path_or_state, device)
+    return _load(RefineNet(cfg, backend=backend, heads=heads, strided=strided, linears=linears), path_or_state, device)
 
 
-def load_scorer(path_or_state, cfg, backend="auto", device="cuda", heads="torch", strided="torch"):
+def load_scorer(path_or_state, cfg, backend="auto", device="cuda", heads="torch", strided="torch", linears="torch"):
     """ScoreNetMultiPair(cfg) the same way: `ScorePredictor(model=load_scorer(path, cfg), cfg=cfg)`."""
-    return _load(ScoreNetMultiPair(cfg, backend=backend, heads=heads, strided=strided), path_or_state, device)
+    return _load(ScoreNetMultiPair(cfg, backend=backend, heads=heads, strided=strided, linears=linears), path_or_state, device)

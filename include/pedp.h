@@ -793,6 +793,50 @@ typedef struct pedp_mha_params {
  * input's (from its first element to its last), PEDP_ERR_BAD_ARG otherwise.  Rows >= S of no operand are touched. */
 int pedp_mha_f16(pedp_ctx_t ctx, const pedp_mha_params *prm, const void *q, const void *k, const void *v, void *o);
 
+/* ---------------------------------------------------------------- linear layers of the networks' heads
+ * The contract is DESIGN.md s4.14: Y[M x N] = epilogue(X[M x K] W^T + bias) with float16 X (row stride x_ld, read in
+ * place) and W (N x K row-major, `nn.Linear.weight` as stored), float32 bias (may be null), float32 accumulation on the
+ * matrix cores, the epilogue in float32 and one rounding to float16.  K is not split and nothing is added atomically:
+ * two calls give the same bits.  Device memory only, on the context's stream, no host wait. */
+#define PEDP_LINEAR_PLAIN 0  /* y = acc + bias */
+#define PEDP_LINEAR_RELU 1   /* y = max(acc + bias, 0) */
+#define PEDP_LINEAR_ADD_LN 2 /* y = LayerNorm(res + (acc + bias)) * gamma + beta over the whole row; N == 512 only */
+typedef struct pedp_linear_params {
+    int32_t M, N, K;           /* M >= 1; N and K multiples of 64 (K <= 8192) */
+    int32_t x_ld, y_ld;        /* elements from row r to row r + 1 (multiples of 8, at least K and N) */
+    int32_t res_ld;            /* ADD_LN: the same for res */
+    int32_t epilogue;          /* PEDP_LINEAR_* */
+    int32_t pos_rows;          /* rows of the position table */
+    int32_t pos_period;        /* S: row r takes table row r % S (1 <= S <= pos_rows) */
+    int32_t pos_a;             /* ADD_LN: nonzero adds the table to X as well as to res (then K == N) */
+    float eps;                 /* ADD_LN: of the variance, `nn.LayerNorm.eps` */
+} pedp_linear_params;
+
+/* Replaces `F.linear` of the heads' projections and feed-forward, and with ADD_LN the `norm(x + linear(...))` that follows
+ * it in a post-norm nn.TransformerEncoderLayer.  pos, when not null, is a float32 table pos_rows x K: row r of the X
+ * operand is half(float(x[r]) + pos[r % S]), formed on the way into the product and never written to memory (the
+ * `tokens + pe` of a _PositionTable).  In ADD_LN pos (pos_rows x N) is added in float32 to the residual row, and to X
+ * only if pos_a is set; res is float16 with row stride res_ld, gamma and beta (may be null) are float32, mean and biased
+ * variance are float32 sums over all N columns.  Every array is 16-byte aligned.  y may not overlap an input, except
+ * that ADD_LN takes y == res with y_ld == res_ld (each element is read and then written by the same lane).  Rows >= M
+ * of no array are touched.  Anything else is PEDP_ERR_BAD_ARG before the context or the device is used. */
+int pedp_linear_f16(pedp_ctx_t ctx, const pedp_linear_params *prm, const void *x, const void *w, const float *bias,
+                    const void *res, const float *pos, const float *gamma, const float *beta, void *y);
+
+typedef struct pedp_token_pool_params {
+    int32_t B, S;              /* groups, consecutive rows per group */
+    int32_t E;                 /* channels: 512 only */
+    int32_t x_ld;              /* elements from row r to row r + 1 (a multiple of 8, at least E) */
+    int32_t n_out;             /* rows of w (1 .. 8); 0 without w */
+} pedp_token_pool_params;
+
+/* The float32 mean over each group's S rows of x (float16), in a fixed order.  w == null: out is B x E float16, the
+ * `.mean(1)` of score_network.py:74.  Otherwise out is B x n_out float16, mean w^T + bias in float32 rounded once: a
+ * Linear and the mean commute, so this is `Linear(512, n)(x).mean(1)` of refine_network.py:90-91, and with S = 1 the
+ * Linear itself (score_network.py:88).  w (n_out x E) and bias (may be null) are float32; x, w, bias 16-byte aligned. */
+int pedp_token_pool_f16(pedp_ctx_t ctx, const pedp_token_pool_params *prm, const void *x, const float *w, const float *bias,
+                        void *out);
+
 /* ---------------------------------------------------------------- cluster_poses
  * Replaces mycpp.cluster_poses (mycpp/src/app/pybind_api.cpp:24-68; caller
  * estimater.py:118).  Host only.  poses: n x 16 float32 row-major, syms: s x 16.

@@ -23,6 +23,12 @@
     strided_first   the first forward's wall time in a fresh process per `strided` value (backend 'hip'): with 'hip' no
                 convolution of the encoders goes to torch's convolution library, whose search for kernels the first
                 forward otherwise pays
+    linears     the heads' linear layers at M = 100,800 (252 x 400 tokens) and M = 252, K = 512, on gaussian float16 data:
+                linear.linear per epilogue (N = 1536 plain and with the position table, N = 512 plain and with ReLU) and
+                linear.linear_add_norm against the torch ops they replace as autocast runs them (F.linear on float16; the
+                table's add, the residual add and F.layer_norm in float32, cast back to float16), linear.token_pool against
+                Linear + mean; then one refiner and one scorer forward at 252 pairs with linears 'torch' against 'hip'
+                (backend 'hip', strided 'hip', heads 'hip'), taking turns in one loop
     estimator   register (252 hypotheses, 5 iterations) and track_one (2 iterations) at 576 x 640 around the real
                 architectures, as tools/estimator_time.py times them around its stand-ins
 
@@ -47,7 +53,7 @@ sys.path.insert(0, ROOT)
 PAIRS, CROP = 252, 160
 SHAPES = [(2 * PAIRS, 40, 40, 128), (PAIRS, 40, 40, 256), (PAIRS, 20, 20, 512)]
 PEAK_F16_TFLOPS = 2500.0   # dense float16 MFMA peak of the MI355X
-STEPS = [("layers", 300), ("heads", 300), ("forward", 420), ("first torch", 300), ("first hip", 300), ("strided", 420),
+STEPS = [("layers", 300), ("heads", 300), ("linears", 420), ("forward", 420), ("first torch", 300), ("first hip", 300), ("strided", 420),
          ("strided_first torch", 300), ("strided_first hip", 300), ("estimator", 420)]
 CFG = {"use_BN": True, "c_in": 6, "rot_rep": "axis_angle", "input_resize": (CROP, CROP), "trans_normalizer": [0.02, 0.02, 0.05],
        "rot_normalizer": 0.35}
@@ -164,11 +170,71 @@ def heads():
     return out
 
 
-def _nets(backend, strided="torch"):
+def _nets(backend, strided="torch", heads="torch"):
     from pedp_hip import networks
 
-    return (networks.RefineNet(CFG, backend=backend, strided=strided).cuda().eval(),
-            networks.ScoreNetMultiPair(CFG, backend=backend, strided=strided).cuda().eval())
+    return (networks.RefineNet(CFG, backend=backend, strided=strided, heads=heads).cuda().eval(),
+            networks.ScoreNetMultiPair(CFG, backend=backend, strided=strided, heads=heads).cuda().eval())
+
+
+def linears():
+    import torch
+    import torch.nn.functional as F
+    from pedp_hip import linear as L
+    from pedp_hip.networks import _PositionTable
+
+    E, S = 512, 400
+    out = {"kernel": {}, "forward": {}}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    pe = _PositionTable(E, S).cuda().pe[0]
+    for M in (PAIRS * S, PAIRS):
+        x = torch.randn((M, E), device="cuda", generator=g).half()
+        res = torch.randn((M, E), device="cuda", generator=g).half()
+        res32 = res.float()
+        lin3, lin1, norm = torch.nn.Linear(E, 3 * E).cuda(), torch.nn.Linear(E, E).cuda(), torch.nn.LayerNorm(E).cuda()
+        p3, p1 = L.pack_linear(lin3), L.pack_linear(lin1)
+        w3, b3, w1, b1 = (t.detach().half() for t in (lin3.weight, lin3.bias, lin1.weight, lin1.bias))
+        y3 = torch.empty((M, 3 * E), dtype=torch.float16, device="cuda")
+        y1 = torch.empty((M, E), dtype=torch.float16, device="cuda")
+        pairs = {
+            "plain_n1536": (lambda: L.linear(x, p3, out=y3), lambda: F.linear(x, w3, b3), 3 * E),
+            "plain_n512": (lambda: L.linear(x, p1, out=y1), lambda: F.linear(x, w1, b1), E),
+            "relu_n512": (lambda: L.linear(x, p1, relu=True, out=y1), lambda: torch.relu(F.linear(x, w1, b1)), E),
+            "add_ln_n512": (lambda: L.linear_add_norm(x, p1, res, norm, out=y1),
+                            lambda: F.layer_norm(res32 + F.linear(x, w1, b1), (E,), norm.weight, norm.bias, norm.eps).half(), E)}
+        if M % S == 0:
+            x3 = x.view(-1, S, E)
+            pairs["plain_pos_n1536"] = (lambda: L.linear(x, p3, pos=pe, period=S, out=y3),
+                                        lambda: F.linear((x3 + pe).half(), w3, b3), 3 * E)
+            small = torch.nn.Linear(E, 3).cuda()
+            ps, ws, bs = L.pack_f32(small), small.weight.detach().half(), small.bias.detach().half()
+            pairs["token_pool_n3"] = (lambda: L.token_pool(x, M // S, ps), lambda: F.linear(x3, ws, bs).mean(dim=1), 0)
+        out["kernel"][f"M{M}"] = {}
+        for name, (kernel, stock, n) in pairs.items():
+            with torch.inference_mode():
+                k, t = _event_ms([kernel, stock], 20)
+            row = {"kernel": k, "torch": t, "kernel_over_torch": k["median_ms"] / t["median_ms"]}
+            if n:
+                flop = 2.0 * M * n * E
+                row.update(gflop=flop / 1e9, kernel_tflops=flop / (k["median_ms"] * 1e-3) / 1e12,
+                           torch_tflops=flop / (t["median_ms"] * 1e-3) / 1e12)
+                row["kernel_fraction_of_f16_peak"] = row["kernel_tflops"] / PEAK_F16_TFLOPS
+            out["kernel"][f"M{M}"][name] = row
+        del x, res, res32, y3, y1
+    A, B = _inputs()
+    rn, sn = _nets("hip", "hip", "hip")
+    refine, score = _forward_fns(rn, sn, A, B)
+
+    def with_linears(net, value, fn):
+        def run():
+            net.set_linears(value)
+            return fn()
+        return run
+
+    for name, net, fn in (("refiner", rn, refine), ("scorer", sn, score)):
+        t, h = _event_ms([with_linears(net, v, fn) for v in ("torch", "hip")], 10, warm=2)
+        out["forward"][name] = {"torch": t, "hip": h, "hip_over_torch": h["median_ms"] / t["median_ms"]}
+    return out
 
 
 def strided():
@@ -420,9 +486,9 @@ if __name__ == "__main__":
         else:
             import torch
 
-            res = {"layers": layers, "heads": heads, "forward": forward, "estimator": estimator, "strided": strided,
+            res = {"layers": layers, "heads": heads, "linears": linears, "forward": forward, "estimator": estimator, "strided": strided,
                    "strided_first": lambda: first("hip", sys.argv[3])}.get(sys.argv[2], lambda: first(sys.argv[3]))()
-            if sys.argv[2] in ("layers", "heads", "strided"):
+            if sys.argv[2] in ("layers", "heads", "linears", "strided"):
                 res["device"] = torch.cuda.get_device_name(0)
             print(json.dumps(res))
     else:
