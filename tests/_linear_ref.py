@@ -27,6 +27,29 @@ def inputs(M, K, N, seed=0, S=None, x_ld=None):
     return d
 
 
+def integer_inputs(M, K, N, seed=0):
+    """Operands whose product float32 holds exactly in any order of the sums and float16 holds exactly as a result: x with
+    integers -2 .. 2, w with -1, 0, 1, no bias.  Every partial sum is an integer of at most 2 K < 2^24."""
+    rng = np.random.default_rng(seed)
+    return {"x": rng.integers(-2, 3, (M, K)).astype(np.float16), "w": rng.integers(-1, 2, (N, K)).astype(np.float16), "bias": None}
+
+
+def sparse_inputs(M, K, N, seed=0, S=None, every=32):
+    """inputs() with one entry of x kept in every `every` columns (at a place drawn per row and group) and zeros elsewhere,
+    and w ~ N(0, 0.15^2 / (K / every)): every K tile still adds to the product, its standard deviation is 0.15 next to the
+    residual's 1, and sum_k |x| |w|, the term the bound's (K + 3) 2^-24 multiplies, is that of a product K / every long.
+    For a large K, where the bound on dense operands is far above what a kernel with a designed fault does."""
+    d = inputs(M, K, N, seed, S)
+    rng = np.random.default_rng(seed + 1)
+    groups = K // every
+    at = rng.integers(0, every, (M, groups)) + every * np.arange(groups)[None]
+    keep = np.zeros((M, K), bool)
+    keep[np.arange(M)[:, None], at] = True
+    d["x"] = np.where(keep, d["x"], np.float16(0))
+    d["w"] = (d["w"].astype(np.float32) * (0.1 * np.sqrt(every))).astype(np.float16)
+    return d
+
+
 def operand(x, pos=None, S=None, no_wrap=False):
     """The A operand as float16: x, or half(float32(x) + pos[r % S]) (no_wrap: pos[r], the designed fault)."""
     x = np.asarray(x, np.float16)
@@ -80,14 +103,18 @@ def reference(x, w, bias, epilogue, res=None, pos=None, S=None, gamma=None, beta
 
 
 def emulate(x, w, bias, epilogue, res=None, pos=None, S=None, gamma=None, beta=None, eps=EPS, pos_a=True, drop_last_k_block=False,
-            no_bias=False, res_shift=False, pos_no_wrap=False, stat_cols=None):
+            no_bias=False, res_shift=False, pos_no_wrap=False, stat_cols=None, last_tile_first_weights=False):
     """The kernel's arithmetic in numpy -> float16.  Faults: drop_last_k_block leaves the last 64 of K out; no_bias; res_shift
     takes residual row r + 1 for row r; pos_no_wrap takes pos[r] for pos[r % S]; stat_cols = n takes mean and variance over
-    the first n columns only."""
+    the first n columns only; last_tile_first_weights computes the last tile of 128 columns with the first tile's rows of w
+    (a column tile's offset left out of the W rows; PLAIN / RELU, N > 128)."""
     K = x.shape[1]
     ln = epilogue == ADD_LN
     xa = operand(x, pos if (not ln or pos_a) else None, S, pos_no_wrap).astype(np.float32)
     w32 = np.asarray(w, np.float16).astype(np.float32)
+    if last_tile_first_weights:
+        n0 = (len(w32) - 1) // 128 * 128
+        w32 = np.concatenate([w32[:n0], w32[:len(w32) - n0]])
     acc = np.zeros((len(xa), len(w32)), np.float32)
     for k in range(0, K - 64 if drop_last_k_block else K, 32):          # one MFMA step: 32 products added to the accumulator
         acc = acc + (xa[:, k:k + 32] @ w32[:, k:k + 32].T).astype(np.float32)

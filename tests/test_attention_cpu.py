@@ -142,6 +142,57 @@ def test_each_designed_fault_exceeds_the_bound(S):
         assert ar.used_share(ar.emulate(q, ks, v, H, skip_rescale_at=key // ar.BK), o_ref, bound) > 10   # a skipped rescale
 
 
+@pytest.mark.parametrize("B,S,H", [(1, 129, 5), (1, 1025, 2), (1, 4096, 1)])
+def test_emulation_on_the_new_shapes_uses_a_part_of_the_bound(B, S, H):
+    """A second query tile with one live row, and 17 and 64 key tiles; the GPU tests' inputs (seed S + 7 B + H)."""
+    q, k, v = ar.gaussian_qkv(B, S, H, seed=S + 7 * B + H)
+    o_ref, bound = ar.reference(q, k, v, H)
+    share = ar.used_share(ar.emulate(q, k, v, H), o_ref, bound)
+    print(f"{B} x {S} x {H}: the emulation uses {share:.3f} of the bound")
+    assert 0.05 < share < 1
+
+
+@pytest.mark.parametrize("S,B,H", [(1025, 1, 2), (4096, 1, 1)])
+def test_faults_at_the_last_of_many_tiles_exceed_the_bound(S, B, H):
+    """The spike at the last key, as tests/test_attention_gpu.py places it: the maximum jumps in the last of 17 and 64 tiles."""
+    key = S - 1
+    q, k, v = ar.gaussian_qkv(B, S, H, seed=200 + key)
+    ks = ar.spike(q, k, H, S // 3, key)
+    o_ref, bound = ar.reference(q, ks, v, H)
+    share = ar.used_share(ar.emulate(q, ks, v, H), o_ref, bound)
+    skipped = ar.used_share(ar.emulate(q, ks, v, H, skip_rescale_at=key // ar.BK), o_ref, bound)
+    dropped = ar.used_share(ar.emulate(q, ks, v, H, drop_last_key=True), o_ref, bound)
+    print(f"S = {S}, spike at the last key: the emulation uses {share:.3f} of the bound, a skipped rescale at the last tile is "
+          f"{skipped:.0f} times the bound, a dropped last key {dropped:.0f} times")
+    assert share < 1 and skipped > 10 and dropped > 10
+
+
+@pytest.mark.parametrize("scale", [0.0, -1.0 / np.sqrt(128), 1.0], ids=["zero", "negative", "one"])
+def test_scales_zero_negative_and_one(scale):
+    """At scale 0 every row is the mean of the values: the fault that tells is a key too few; at the others also a skipped
+    rescale (the maximum moves in the second and third tile of 129 keys for some row)."""
+    B, S, H = 2, 129, 2
+    q, k, v = ar.gaussian_qkv(B, S, H, seed=3)
+    o_ref, bound = ar.reference(q, k, v, H, scale=scale)
+    share = ar.used_share(ar.emulate(q, k, v, H, scale=scale), o_ref, bound)
+    dropped = ar.used_share(ar.emulate(q, k, v, H, scale=scale, drop_last_key=True), o_ref, bound)
+    print(f"scale {scale:.4f}: the emulation uses {share:.3f} of the bound, a dropped last key is {dropped:.0f} times the bound")
+    assert share < 1 and dropped > 10
+    if scale:
+        assert ar.used_share(ar.emulate(q, k, v, H, scale=scale, skip_rescale_at=1), o_ref, bound) > 10
+
+
+def test_leak_at_129_keys_exceeds_the_bound():
+    B, S, H = 3, 129, 4
+    q, k, v = ar.gaussian_qkv(B, S, H, seed=100 + S)
+    loud_k, loud_v = k.copy(), v.copy()
+    loud_k[1] = (k[1].astype(np.float32) * 8).astype(np.float16)
+    loud_v[1] = 300.0
+    o_ref, bound = ar.reference(q, loud_k, loud_v, H)
+    assert ar.used_share(ar.emulate(q, loud_k, loud_v, H), o_ref, bound) < 1
+    assert ar.used_share(ar.emulate(q, loud_k, loud_v, H, leak_keys=1)[:1], o_ref[:1], bound[:1]) > 10
+
+
 # ---------------------------------------------------------------- the networks' switch
 
 def _net(kind, **kw):

@@ -3,7 +3,8 @@
 Every comparison is of the full tensor against the float64 attention of the float16-rounded inputs, within
 |o - o_ref| <= (2^-11 + 4 E_i + (S + 4) 2^-24) A + S 2^-25 max_j |v_jd| + 2^-11 |o_ref| + 2^-24 (tests/_attn_ref.py: reference).
 The shapes cover one row, fewer rows than a 16-row block, the 64-key tile and the 128-row workgroup with and without a
-tail, and the networks' 252 and 400 tokens."""
+tail, the networks' 252 and 400 tokens, a second query tile with one live row (129), whole numbers of key tiles (128, 192),
+17 and 64 key tiles (1025 and 4096, the most the entry point takes), and a head count that is no power of two (5)."""
 import copy
 
 import numpy as np
@@ -15,8 +16,14 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-SHAPES = [(1, 1, 1), (2, 3, 4), (3, 16, 4), (2, 17, 4), (2, 63, 2), (1, 64, 4), (2, 65, 4), (2, 252, 4), (2, 400, 4)]
+SHAPES = [(1, 1, 1), (2, 3, 4), (3, 16, 4), (2, 17, 4), (2, 63, 2), (1, 64, 4), (2, 65, 4), (2, 252, 4), (2, 400, 4),
+          (2, 128, 1), (1, 129, 5), (1, 191, 2), (1, 192, 1), (1, 1025, 2), (1, 4096, 1)]
 _CACHE = {}
+
+
+def _batch_and_heads(S):
+    """B, H of the tests that take S alone: 2 x 4 up to the networks' sizes, fewer beyond to keep the float64 reference quick."""
+    return (2, 4) if S <= 400 else (1, 2) if S <= 1025 else (1, 1)
 
 
 def _case(B, S, H):
@@ -79,9 +86,21 @@ def test_scale_argument():
     _check(mha_core(_packed(q, k, v), H, scale=0.05).cpu().numpy(), o_ref, bound, "scale 0.05")
 
 
-@pytest.mark.parametrize("S", [17, 65, 252, 400])
+@pytest.mark.parametrize("scale", [0.0, -1.0 / np.sqrt(128), 1.0], ids=["zero", "negative", "one"])
+def test_scale_zero_negative_and_one(scale):
+    """Scale 0 makes every row the mean of the values over exactly S keys (a tail key let in, or a live one masked, moves it),
+    a negative scale turns the order of the scores round, and scale 1 gives scores of some hundreds in float32."""
+    from pedp_hip.attention import mha_core
+
+    B, S, H = 2, 129, 2
+    q, k, v = ar.gaussian_qkv(B, S, H, seed=3)
+    o_ref, bound = ar.reference(q, k, v, H, scale=scale)
+    _check(mha_core(_packed(q, k, v), H, scale=scale).cpu().numpy(), o_ref, bound, f"scale {scale:.4f} at {B} x {S} x {H}")
+
+
+@pytest.mark.parametrize("S", [17, 65, 252, 400, 1025, 4096])
 def test_dominant_last_key(S):
-    B, H = 2, 4
+    B, H = _batch_and_heads(S)
     q, k, v = ar.gaussian_qkv(B, S, H, seed=S)
     q, k = ar.dominate_last_key(q, k, H)
     o_ref, bound = ar.reference(q, k, v, H)
@@ -91,7 +110,7 @@ def test_dominant_last_key(S):
     assert np.abs(o.astype(np.float64) - v[:, -1:, :].astype(np.float64)).max() < 1e-2  # every row is the last key's value
 
 
-@pytest.mark.parametrize("S", [17, 65, 252])
+@pytest.mark.parametrize("S", [17, 65, 252, 129])
 def test_neighbouring_batch_and_head_do_not_leak(S):
     B, H = 3, 4
     q, k, v = ar.gaussian_qkv(B, S, H, seed=100 + S)
@@ -111,9 +130,11 @@ def test_neighbouring_batch_and_head_do_not_leak(S):
     assert ar.used_share(ar.emulate(q, loud_k, loud_v, H, leak_keys=1)[:1], o_ref[:1], bound[:1]) > 10
 
 
-@pytest.mark.parametrize("S,key", [(400, 5), (400, 200), (400, 399), (252, 130), (65, 64)])
+@pytest.mark.parametrize("S,key", [(400, 5), (400, 200), (400, 399), (252, 130), (65, 64), (1025, 1024), (4096, 4095)])
 def test_running_maximum_jumps_at_a_chosen_tile(S, key):
-    B, H, row = 2, 4, S // 3
+    """With the spike at the last key of S = 1025 and 4096 the maximum has been rescaled over 16 and 63 tiles before it
+    jumps in the last one: a tail tile of one key, and a full tile."""
+    (B, H), row = _batch_and_heads(S), S // 3
     q, k, v = ar.gaussian_qkv(B, S, H, seed=200 + key)
     for name, kk in (("spike", ar.spike(q, k, H, row, key)), ("no spike", k)):
         o_ref, bound = ar.reference(q, kk, v, H)

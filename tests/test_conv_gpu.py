@@ -4,7 +4,8 @@ back, b' and the residual.  Per element, with K = 9 * Cin and y the float64 pre-
     |y_kernel - y| <= (K + 4) * 2^-24 * (conv(|x|, |w'|) + |b'| + |res|) + 2^-11 * |y| + 2^-24
 
 the float32 accumulation bound for any summation order plus one rounding to float16; ReLU is 1-Lipschitz, so the bound
-holds after it unchanged.  One float64 reference per shape serves every variant of that shape."""
+holds after it unchanged.  One float64 reference per shape serves every variant of that shape.  The tap-map test needs no
+bound: one input element is 1, every weight is its own code, and each output element is one product or zero."""
 import ctypes as C
 import functools
 
@@ -83,6 +84,69 @@ def test_conv_with_batchnorm_folded_stays_within_the_float32_bound(shape):
         out = conv3x3(c["x"], c["packed"], residual=y, relu=relu, out=y)          # the residual is the destination
         assert out.data_ptr() == y.data_ptr()
         _check(y, c, True, relu, f"{shape} residual aliasing the output relu={relu}")
+
+
+NEW_CHANNELS = [(96, 32), (96, 224), (160, 96), (192, 128), (320, 64), (480, 480)]
+
+
+@pytest.mark.parametrize("pixels", [(3, 5, 7), (2, 9, 11)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("cin,cout", NEW_CHANNELS)
+def test_channel_counts_beside_the_networks(cin, cout, pixels):
+    """Cin = 96, 160 and 480: three, five and fifteen 32-channel steps per tap (conv_kernel<1, 1>); Cin = 192 and 320: an
+    odd number of 64-channel steps; Cout = 224 and 480: a partial channel tile behind full ones.  105 pixels are one tile
+    straddling three images, 198 are two tiles."""
+    from pedp_hip.conv import conv3x3
+
+    c = _case(*pixels, cin, cout, True)
+    what = f"{pixels} {cin} -> {cout}"
+    for relu in (True, False):
+        _check(conv3x3(c["x"], c["packed"], relu=relu), c, False, relu, f"{what} relu={relu}")
+        _check(conv3x3(c["x"], c["packed"], residual=c["res"], relu=relu), c, True, relu, f"{what} residual relu={relu}")
+        y = c["res"].clone()
+        out = conv3x3(c["x"], c["packed"], residual=y, relu=relu, out=y)          # the residual is the destination
+        assert out.data_ptr() == y.data_ptr()
+        _check(y, c, True, relu, f"{what} residual aliasing the output relu={relu}")
+
+
+@pytest.mark.parametrize("pixels", [(3, 5, 7), (2, 9, 11)], ids=lambda s: "x".join(map(str, s)))
+def test_partial_channel_tile_into_a_destination_with_its_own_stride_and_offset(pixels):
+    """96 -> 224 channels: the second channel tile holds 96 of 128; the channels on both sides of the slice stay."""
+    from pedp_hip.conv import conv3x3
+
+    c = _case(*pixels, 96, 224, True)
+    n, h, w = pixels
+    dense = conv3x3(c["x"], c["packed"], residual=c["res"], relu=True)
+    _check(dense, c, True, True, f"{pixels} 96 -> 224 dense")
+    pattern = (torch.arange(n * h * w * 480, device="cuda") % 251).half().reshape(n, h, w, 480)
+    for c0 in (32, 256):
+        out = pattern.clone()
+        got = conv3x3(c["x"], c["packed"], residual=c["res"], relu=True, out=out, out_c0=c0)
+        assert got.data_ptr() == out[..., c0:].data_ptr() and tuple(got.shape) == (n, h, w, 224)
+        assert torch.equal(out[..., c0:c0 + 224], dense), f"y_c0 = {c0} differs from the dense call"
+        assert torch.equal(out[..., :c0], pattern[..., :c0]) and torch.equal(out[..., c0 + 224:], pattern[..., c0 + 224:]), \
+            f"channels outside {c0} .. {c0 + 224} were written"
+
+
+@pytest.mark.parametrize("cin,cout,as_bits", [(32, 32, False), (96, 160, True)], ids=["32", "96"])
+def test_tap_map_is_exact(cin, cout, as_bits):
+    """Stride 1 through pack_conv3x3: a 1 at one input element and coded weights give each output element as one product
+    or zero, exactly.  32 channels are one 32-channel K step per tap; 96 are three, with the 1 at channels 95 and 48 in the
+    third and the second step (6912 codes, as float16 bit patterns): a 32-channel path that left the channel step out
+    of its offset would return the codes of channels 31 and 16 there.  160 output channels end in a tile of 32 behind a
+    full one.  77 pixels per image: the 231 pixels fill two tiles, the first holds two images' ends."""
+    from test_conv_strided_gpu import _coded_layer
+
+    from pedp_hip.conv import conv3x3
+
+    packed, w64 = _coded_layer(cout, cin, 3, as_bits, stride=1)
+    n, h, w = 3, 7, 11
+    for img, ci, y, x in ((0, 0, 0, 0), (2, cin - 1, 6, 10), (1, 7, 0, 5), (1, cin // 2, 3, 4), (1, 3, 6, 10), (2, 1, 2, 0)):
+        src = torch.zeros((n, h, w, cin), dtype=torch.float16)
+        src[img, y, x, ci] = 1.0
+        want = F.conv2d(src.double().permute(0, 3, 1, 2), w64, None, 1, 1).permute(0, 2, 3, 1)
+        got = conv3x3(src.cuda(), packed, relu=False).double().cpu()
+        assert int((want != 0).sum()) >= 4 * cout
+        assert torch.equal(got, want), f"a 1 at image {img}, channel {ci}, ({y}, {x}): {int((got != want).sum())} elements differ"
 
 
 def test_the_fold_is_the_float32_fold():

@@ -120,6 +120,21 @@ def test_strided_3x3_stays_within_the_float32_bound(shape):
         _check(y, c, relu, f"3x3/2 {shape} relu={relu}")
 
 
+NEW_CHANNELS = [(96, 32), (96, 224), (160, 96), (192, 128), (320, 64), (480, 480)]
+
+
+@pytest.mark.parametrize("pixels", [(3, 5, 7), (2, 9, 11)], ids=_ids)
+@pytest.mark.parametrize("cin,cout", NEW_CHANNELS)
+def test_strided_3x3_over_channel_counts_beside_the_networks(cin, cout, pixels):
+    """Cin = 96, 160 and 480: three, five and fifteen 32-channel steps per tap (conv_kernel<1, 2>); Cin = 192 and 320: an
+    odd number of 64-channel steps; Cout = 224 and 480: a partial channel tile behind full ones."""
+    from pedp_hip.conv import conv_strided
+
+    c = _down_case(*pixels, cin, cout)
+    for relu in (True, False):
+        _check(conv_strided(c["x"], c["packed"], relu=relu), c, relu, f"3x3/2 {pixels} {cin} -> {cout} relu={relu}")
+
+
 def test_strided_3x3_without_batchnorm_and_the_fold():
     from pedp_hip.conv import conv_strided
 
@@ -202,15 +217,16 @@ def _coded_weights(cout, cin, k, as_bits):
     return (v + (v >= 0)).to(torch.float16)
 
 
-def _coded_layer(cout, cin, k, as_bits):
-    from pedp_hip.conv import pack_conv
+def _coded_layer(cout, cin, k, as_bits, stride=2):
+    """The packed layer with _coded_weights and no bias (stride 1: conv3x3's form, through pack_conv3x3), and the weights."""
+    from pedp_hip.conv import pack_conv, pack_conv3x3
 
-    conv = torch.nn.Conv2d(cin, cout, k, 2, (k - 1) // 2, bias=True)
+    conv = torch.nn.Conv2d(cin, cout, k, stride, (k - 1) // 2, bias=True)
     w = _coded_weights(cout, cin, k, as_bits)
     with torch.no_grad():
         conv.weight.copy_(w.float())
         conv.bias.zero_()
-    packed = pack_conv(conv.cuda())
+    packed = (pack_conv if stride == 2 else pack_conv3x3)(conv.cuda())
     assert torch.equal(packed.weight_oihw().cpu(), w) and len(torch.unique(w[:8])) == 8 * cin * k * k
     return packed, w.double()
 
@@ -230,10 +246,12 @@ def test_stem_tap_map_is_exact(dtype):
         assert torch.equal(got, want), f"a 1 at image {img}, channel {ci}, ({y}, {x}): {int((got != want).sum())} elements differ"
 
 
-@pytest.mark.parametrize("cin,cout,as_bits", [(32, 32, False), (64, 128, True)], ids=["32", "64"])
+@pytest.mark.parametrize("cin,cout,as_bits", [(32, 32, False), (64, 128, True), (96, 160, True)], ids=["32", "64", "96"])
 def test_strided_3x3_tap_map_is_exact(cin, cout, as_bits):
     """32 channels take the kernel's 32-channel K step with integer codes; 64 channels (4608 codes, more than the integers
-    float16 holds exactly) take the 64-channel step the networks' layers use, with bit-pattern codes."""
+    float16 holds exactly) take the 64-channel step the networks' layers use, with bit-pattern codes; 96 channels (6912
+    codes) take three 32-channel steps per tap, the ones at channels 95 and 48 in the third and the second, and 160 output
+    channels end in a tile of 32 behind a full one."""
     from pedp_hip.conv import conv_strided
 
     packed, w64 = _coded_layer(cout, cin, 3, as_bits)
@@ -267,6 +285,25 @@ def test_destination_with_its_own_channel_stride_and_offset():
             assert torch.equal(out[..., c0:c0 + cout], dense), f"{what}: y_c0 = {c0} differs from the dense call"
             assert torch.equal(out[..., :c0], pattern[..., :c0]) and torch.equal(out[..., c0 + cout:], pattern[..., c0 + cout:]), \
                 f"{what}: channels outside {c0} .. {c0 + cout} were written"
+
+
+@pytest.mark.parametrize("pixels", [(3, 5, 7), (2, 9, 11)], ids=_ids)
+def test_partial_channel_tile_into_a_destination_with_its_own_stride_and_offset(pixels):
+    """96 -> 224 channels: the second channel tile holds 96 of 128; the channels on both sides of the slice stay."""
+    from pedp_hip.conv import conv_strided
+
+    c = _down_case(*pixels, 96, 224)
+    dense = conv_strided(c["x"], c["packed"], relu=False)
+    _check(dense, c, False, f"3x3/2 {pixels} 96 -> 224")
+    n, oh, ow, cout = dense.shape
+    pattern = (torch.arange(n * oh * ow * (2 * cout + 32), device="cuda") % 251).half().reshape(n, oh, ow, 2 * cout + 32)
+    for c0 in (32, cout + 32):
+        out = pattern.clone()
+        got = conv_strided(c["x"], c["packed"], relu=False, out=out, out_c0=c0)
+        assert got.data_ptr() == out[..., c0:].data_ptr()
+        assert torch.equal(out[..., c0:c0 + cout], dense), f"y_c0 = {c0} differs from the dense call"
+        assert torch.equal(out[..., :c0], pattern[..., :c0]) and torch.equal(out[..., c0 + cout:], pattern[..., c0 + cout:]), \
+            f"channels outside {c0} .. {c0 + cout} were written"
 
 
 def test_two_calls_give_identical_bits():

@@ -56,6 +56,125 @@ def test_each_designed_fault_of_the_product_exceeds_the_bound(epilogue):
         assert lr.used_share(lr.emulate(**a, pos_no_wrap=True), y_ref, bound) > 10
 
 
+# the shapes tests/test_linear_gpu.py adds: (M, K, N), the faults that shape is there for
+_TILE, _K, _BIAS = "last_tile_first_weights", "drop_last_k_block", "no_bias"
+NEW_PRODUCTS = {(130, 64, 192): (_TILE, _BIAS), (130, 192, 320): (_TILE, _K), (17, 128, 192): (_TILE, _K), (5, 64, 2112): (_TILE, _BIAS),
+                (128, 128, 128): (_K, _BIAS), (256, 64, 64): (_BIAS,), (127, 64, 64): (_BIAS,), (129, 64, 64): (_BIAS,)}
+
+
+@pytest.mark.parametrize("epilogue", [lr.PLAIN, lr.RELU])
+@pytest.mark.parametrize("shape", list(NEW_PRODUCTS), ids=lambda v: "x".join(map(str, v)))
+def test_new_product_shapes_tell_their_faults_from_the_bound(shape, epilogue):
+    M, K, N = shape
+    faults = NEW_PRODUCTS[shape]
+    d = lr.inputs(M, K, N, seed=M + K + N)
+    a = _args(d, epilogue)
+    y_ref, bound = lr.reference(**a)
+    share = lr.used_share(lr.emulate(**a), y_ref, bound)
+    print(f"{NAMES[epilogue]} {M} x {K} -> {N}: the emulation uses {share:.3f} of the bound")
+    assert share < 1
+    for fault in faults:
+        share = lr.used_share(lr.emulate(**a, **{fault: True}), y_ref, bound)
+        print(f"{NAMES[epilogue]} {M} x {K} -> {N}: {fault} is {share:.0f} times the bound")
+        assert share > 10, fault
+
+
+@pytest.mark.parametrize("K", [128, 192, 1024])
+@pytest.mark.parametrize("M", [63, 64, 128])
+def test_new_add_norm_shapes_tell_their_faults_from_the_bound(M, K):
+    d = lr.inputs(M, K, 512, seed=M + K)
+    a = _args(d, lr.ADD_LN)
+    y_ref, bound = lr.reference(**a)
+    share = lr.used_share(lr.emulate(**a), y_ref, bound)
+    print(f"ADD_LN {M} x {K}: the emulation uses {share:.3f} of the bound")
+    assert share < 1
+    for fault in ("drop_last_k_block", "no_bias", "res_shift"):
+        share = lr.used_share(lr.emulate(**a, **{fault: True}), y_ref, bound)
+        print(f"ADD_LN {M} x {K}: {fault} is {share:.0f} times the bound")
+        assert share > 10, fault
+
+
+def test_integer_operands_make_the_longest_product_exact():
+    """K = 8192 for PLAIN and RELU: on gaussian operands the emulation uses a few hundredths of the bound, which tells
+    little; on integer_inputs the result is the integer product bit for bit and a dropped K block changes most of it."""
+    d = lr.inputs(33, 8192, 192, seed=0)
+    y_ref, bound = lr.reference(**_args(d, lr.PLAIN))
+    loose = lr.used_share(lr.emulate(**_args(d, lr.PLAIN)), y_ref, bound)
+    print(f"PLAIN 33 x 8192 -> 192 on gaussian operands: the emulation uses {loose:.3f} of the bound")
+    assert loose < 0.1
+    for N in (192, 64):
+        d = lr.integer_inputs(33, 8192, N, seed=0)
+        y = d["x"].astype(np.float64) @ d["w"].astype(np.float64).T
+        assert np.abs(y).max() <= 2048                                    # float16 holds every integer up to 2048
+        for epilogue in (lr.PLAIN, lr.RELU):
+            want = np.maximum(y, 0) if epilogue == lr.RELU else y
+            assert np.array_equal(lr.emulate(d["x"], d["w"], None, epilogue).astype(np.float64), want)
+        changed = float((lr.emulate(d["x"], d["w"], None, lr.PLAIN, drop_last_k_block=True).astype(np.float64) != y).mean())
+        print(f"33 x 8192 -> {N}: max |y| {np.abs(y).max():.0f}, a dropped K block changes {changed:.2f} of the elements")
+        assert changed > 0.9
+
+
+@pytest.mark.parametrize("S", [None, 24])
+def test_sparse_operands_keep_every_fault_of_the_longest_add_norm_outside_the_bound(S):
+    """ADD_LN at K = 8192: on gaussian operands drop_last_k_block is only 4.8 times the bound; on sparse_inputs every fault
+    is more than 10 times outside."""
+    d = lr.sparse_inputs(33, 8192, 512, seed=3, S=S)
+    assert all((row.reshape(-1, 32) != 0).sum(1).max() <= 1 for row in d["x"]) and (d["x"] != 0).sum() > 33 * 250
+    a = _args(d, lr.ADD_LN, S, pos_a=False)
+    y_ref, bound = lr.reference(**a)
+    share = lr.used_share(lr.emulate(**a), y_ref, bound)
+    print(f"ADD_LN 33 x 8192, sparse x, S = {S}: the emulation uses {share:.3f} of the bound")
+    assert share < 1
+    for kw in [dict(drop_last_k_block=True), dict(no_bias=True), dict(res_shift=True), dict(stat_cols=448)] + \
+            ([dict(pos_no_wrap=True)] if S else []):
+        share = lr.used_share(lr.emulate(**a, **kw), y_ref, bound)
+        print(f"ADD_LN 33 x 8192, sparse x, S = {S}: {kw} is {share:.1f} times the bound")
+        assert share > 10, kw
+
+
+def test_an_operand_that_is_left_out_must_not_be_added():
+    """bias = None and beta = None at (65, 128, 512): a kernel that adds the bias or the beta it was not given."""
+    d = lr.inputs(65, 128, 512, seed=21)
+    for epilogue in (lr.PLAIN, lr.RELU, lr.ADD_LN):
+        without = _args(dict(d, bias=None), epilogue)
+        y_ref, bound = lr.reference(**without)
+        assert lr.used_share(lr.emulate(**without), y_ref, bound) < 1
+        share = lr.used_share(lr.emulate(**_args(d, epilogue)), y_ref, bound)
+        print(f"{NAMES[epilogue]}: a bias added anyway is {share:.0f} times the bound")
+        assert share > 10
+    without = _args(dict(d, beta=None), lr.ADD_LN)
+    y_ref, bound = lr.reference(**without)
+    assert lr.used_share(lr.emulate(**without), y_ref, bound) < 1
+    share = lr.used_share(lr.emulate(**_args(d, lr.ADD_LN)), y_ref, bound)
+    print(f"ADD_LN: a beta added anyway is {share:.0f} times the bound")
+    assert share > 10
+
+
+@pytest.mark.parametrize("epilogue", [lr.PLAIN, lr.RELU, lr.ADD_LN])
+@pytest.mark.parametrize("M,S", [(130, 1), (130, 48), (40, 64)])
+def test_new_table_periods(M, S, epilogue):
+    """Period 1 and a period that does not divide M tell pos[r] from pos[r % S]; a period above M cannot (no row wraps)
+    and is there for the entry point's pos_rows >= period path alone."""
+    K, N = (128, 512) if epilogue == lr.ADD_LN else (128, 192)
+    d = lr.inputs(M, K, N, seed=M + S, S=S)
+    a = _args(d, epilogue, S, pos_a=epilogue != lr.ADD_LN)
+    y_ref, bound = lr.reference(**a)
+    assert lr.used_share(lr.emulate(**a), y_ref, bound) < 1
+    share = lr.used_share(lr.emulate(**a, pos_no_wrap=True), y_ref, bound)
+    print(f"{NAMES[epilogue]} {M} rows, period {S}: pos_no_wrap is {share:.1f} times the bound")
+    assert share > 10 if S < M else share < 1
+
+
+@pytest.mark.parametrize("B,S,n_out", [(3, 5, 8), (2, 7, None), (2, 401, 8), (4, 2, 3)])
+def test_pool_emulation_and_its_fault_on_unequal_row_phases(B, S, n_out):
+    d = lr.pool_inputs(B, S, n_out, seed=S + B, loud_next=True)
+    ref, bound = lr.pool_reference(d["x"], B, S, d["w"], d["bias"])
+    share = lr.used_share(lr.pool_emulate(d["x"], B, S, d["w"], d["bias"]), ref, bound)
+    print(f"pool {B} x {S}, n_out {n_out}: {share:.3f} of the bound")
+    assert share < 1
+    assert lr.used_share(lr.pool_emulate(d["x"], B, S, d["w"], d["bias"], leak=True)[:1], ref[:1], bound[:1]) > 10
+
+
 def test_bound_holds_on_loud_and_flat_rows():
     d = lr.inputs(65, 512, 512, seed=11)
     for name, dd in (("loud", lr.loud_row(d, 3)), ("flat", lr.flat_row(d, 5))):
