@@ -155,6 +155,8 @@ PROTOTYPES = {
     "pedp_pose_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     "pedp_max_pair_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_double)]),
+    "pedp_pose_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pedp_mask_depth_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
@@ -388,6 +390,7 @@ class TokenPoolParams(C.Structure):
 LINEAR_PLAIN, LINEAR_RELU, LINEAR_ADD_LN = 0, 1, 2
 TRANS_TRACKNET, TRANS_RAW = 0, 1
 ROT_AXIS_ANGLE, ROT_6D = 0, 1
+ERR_ADD, ERR_ADDS = 0, 1      # pedp_pose_errors' kind
 
 
 class MaskDepthStats(C.Structure):

@@ -30,6 +30,7 @@ SOURCES = {
     "pedp_crop.hip": [],
     "pedp_pose.hip": [],
     "pedp_estimator.hip": [],
+    "pedp_metrics.hip": [],
     "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_linear.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

@@ -7,7 +7,8 @@ renderer (`nvdiffrast_render`, `make_mesh_tensors` and the `dr` stand-in for `nv
 (`make_crop_data_batch`, `make_score_crop_data_batch` and the `kornia` stand-in with `warp_perspective`), and the pose
 arithmetic of its refinement loop (`pose_update`, `max_pair_distance`), and the estimator with the two predictors'
 loops (`FoundationPose`, `PoseRefinePredictor`, `ScorePredictor`, estimator.py), and the two networks with their
-checkpoint loaders (`RefineNet`, `ScoreNetMultiPair`, `load_refiner`, `load_scorer`, networks.py); the Dash app, sensor
+checkpoint loaders (`RefineNet`, `ScoreNetMultiPair`, `load_refiner`, `load_scorer`, networks.py), and the evaluation
+metrics (`add_err`, `adds_err`, their batch forms, `compute_auc_sklearn`, `symmetry_tfs_from_info`, metrics.py); the Dash app, sensor
 code and the networks' weights stay the reference's own.
 """
 import numpy as np
@@ -51,6 +52,8 @@ from .crop import (BatchPoseData, compute_crop_window_tf_batch, kornia, make_cro
 from .pose import max_pair_distance, pose_update  # noqa: E402,F401  (predict_pose_refine.py:195-231, Utils.py:559-574)
 from .estimator import (FoundationPose, PoseRefinePredictor, ScorePredictor, compute_mesh_diameter,  # noqa: E402,F401
                         euler_matrix, guess_translation, mask_depth_stats, sample_views_icosphere, set_seed)
+from .metrics import (add_err, add_err_batch, adds_err, adds_err_batch, compute_auc_sklearn,  # noqa: E402,F401  (Utils.py:232-266, :806-834)
+                      symmetry_tfs_from_info)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
 
@@ -83,4 +86,5 @@ __all__ = [
     "FoundationPose", "PoseRefinePredictor", "ScorePredictor", "guess_translation", "mask_depth_stats", "set_seed",
     "sample_views_icosphere", "euler_matrix", "compute_mesh_diameter",
     "RefineNet", "ScoreNetMultiPair", "load_refiner", "load_scorer",
+    "add_err", "adds_err", "add_err_batch", "adds_err_batch", "compute_auc_sklearn", "symmetry_tfs_from_info",
 ]

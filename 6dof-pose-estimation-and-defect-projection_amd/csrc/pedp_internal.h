@@ -167,6 +167,8 @@ struct pedp_ctx_s {
     void *stage[2] = {nullptr, nullptr};  // pinned staging buffers of pedp_upload [0] / pedp_download [1], grown on demand
     size_t stage_cap[2] = {0, 0};
     bool stage_busy = false;              // an upload's DMA may still be reading stage[0]
+    pedp_scratch metrics_ws; // pose errors: the partial sums of one slab of poses (pedp_metrics.hip)
+    pedp_scratch metrics_io; // pose errors: inputs and outputs of host-memory calls
 };
 
 // Triangle record: 12 floats (48 B, 16-B aligned so a wave fetches it with scalar

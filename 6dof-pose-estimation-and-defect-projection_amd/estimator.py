@@ -399,7 +399,8 @@ class FoundationPose:
                              "networks); this package holds no weights to build them from")
         if debug >= 2:
             raise NotImplementedError("debug >= 2 writes point clouds and images with open3d / cv2 / imageio")
-        self.gt_pose = None
+        self.gt_pose = None     # a pose of the mesh as given (what register returns): switches the ADD lines of register on
+        self.add_errs = None    # register's last ADD errors in the order of self.poses (only with gt_pose)
         self.ignore_normal_flip = True
         self.debug = debug
         self.debug_dir = debug_dir
@@ -494,6 +495,8 @@ class FoundationPose:
         self.ob_id = ob_id
         self.ob_mask = ob_mask
         poses = self._hypotheses(center)
+        if self.gt_pose is not None:
+            logging.info(f"after viewpoint, add_errs min:{self.compute_add_err_to_gt_pose(poses).min()}")
         xyz_map = depth2xyzmap(depth, K)
         poses, _ = self.refiner.predict(mesh=self.mesh, mesh_tensors=self.mesh_tensors, rgb=rgb, depth=depth, K=K, ob_in_cams=poses,
                                         normal_map=None, xyz_map=xyz_map, glctx=self.glctx, mesh_diameter=self.diameter,
@@ -502,6 +505,10 @@ class FoundationPose:
                                         mesh_tensors=self.mesh_tensors, glctx=self.glctx, mesh_diameter=self.diameter,
                                         get_vis=False)
         ids = torch.as_tensor(scores).argsort(descending=True, stable=True)   # (the reference's sort leaves ties open)
+        if self.gt_pose is not None:
+            add_errs = self.compute_add_err_to_gt_pose(poses)
+            logging.info(f"final, add_errs min:{add_errs.min()}")
+            self.add_errs = add_errs[ids]
         scores = scores[ids]
         poses = poses[ids]
         best_pose = poses[0] @ self.get_tf_to_centered_mesh()
@@ -512,9 +519,22 @@ class FoundationPose:
         return best_pose.data.cpu().numpy()
 
     def compute_add_err_to_gt_pose(self, poses):
+        """The ADD error (metres, float32 CUDA tensor, no host wait) of every pose of the centred mesh against
+        self.gt_pose, minimised over self.symmetry_tfs; -1 for every pose while gt_pose is None (the reference's stub).
+        gt_pose is a pose of the mesh as given: the ground truth of the centred mesh is gt_pose @ inv(tf_to_center),
+        formed in float64 and rounded once to float32, the precision of the estimator's poses, so that a pose equal to
+        it has the error 0.  The points are self.pts."""
         import torch
 
-        return -torch.ones(len(poses), device="cuda", dtype=torch.float)
+        if self.gt_pose is None:
+            return -torch.ones(len(poses), device="cuda", dtype=torch.float)
+        from .metrics import add_err_batch
+
+        back = np.eye(4)
+        back[:3, 3] = np.asarray(self.model_center, np.float32)       # inv(tf_to_center), exactly
+        gt = (np.asarray(_host(self.gt_pose), np.float64).reshape(4, 4) @ back).astype(np.float32)
+        poses = torch.as_tensor(poses, device="cuda", dtype=torch.float).reshape(-1, 4, 4)
+        return add_err_batch(poses, gt, self.pts, symmetry_tfs=self.symmetry_tfs).float()
 
     def track_one(self, rgb, depth, K, iteration, extra={}):
         """The next frame's pose (4 x 4 numpy) from the last one: the depth filters, the refiner on pose_last, which

@@ -692,6 +692,34 @@ int pedp_pose_update(pedp_ctx_t ctx, const pedp_pose_update_params *prm, int B, 
  * memory; the call returns once it is written. */
 int pedp_max_pair_distance(pedp_ctx_t ctx, const double *pts, int64_t n, int mem, double *out);
 
+/* ---------------------------------------------------------------- pose errors (add_err, adds_err)
+ * ADD and ADD-S of B predicted poses against a ground truth (Utils.py:232-253), one float64 per pose.  The contract is
+ * DESIGN.md s4.15:
+ *   arithmetic   float64, no contraction, every sum in the order written, no floating-point atomics: a rerun, another
+ *                batch size and another position in the batch give the same bits
+ *   transform    q_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k for a model point (x, y, z); the bottom row of a pose is not read
+ *   ADD          e = (1 / N) sum_i sqrt((dx^2 + dy^2) + dz^2), d = pred p_i - gt p_i
+ *   ADD-S        e = (1 / N) sum_i sqrt(min_j ((dx^2 + dy^2) + dz^2)), d = pred p_j - gt p_i: the nearest transformed
+ *                pred point of every transformed gt point (the reference's tree holds the pred points)
+ *   mean         the terms in chunks of 256 points, a chunk's sum in a fixed tree, the chunks' sums added in index order,
+ *                one division by N: the order depends on N alone (DESIGN.md states it, tests/_metrics_ref.py restates it)
+ *   symmetries   S > 0: the error of pose b is the minimum over s of e(pred_b . sym_s, gt), the 4 x 4 product's rows
+ *                0 .. 2 formed as ((P_i0 s_0j + P_i1 s_1j) + P_i2 s_2j) + P_i3 s_3j; S = 0 multiplies nothing, and S = 1
+ *                with the identity gives the same bits as S = 0
+ *   non-finite   a pose is NaN if a transformed coordinate it reads (pred or gt side, any symmetry) is not finite, which
+ *                every NaN / infinite entry of the pose, the ground truth, a symmetry or a point causes; the other poses
+ *                are not touched
+ * pts N x 3; preds B x 16 and gts G x 16 row-major 4 x 4, G = 1 (one ground truth for all) or G = B; sym S x 16 or null
+ * with S = 0; kind PEDP_ERR_ADD or PEDP_ERR_ADDS; out B doubles.  Every pointer is host or device memory by `mem`;
+ * PEDP_DEVICE only enqueues on the context's stream.  N = 0, N > 2^22, B > 65535, S > 65535 or G not in {1, B} is
+ * PEDP_ERR_BAD_ARG; B = 0 does nothing.  The partial sums live in a workspace of their own (64 MB at most unless
+ * one pose alone needs more: more poses go in slabs), so PEDP_DEVICE calls are allowed while a registration is pending on ctx (pedp_icp_begin); PEDP_HOST
+ * calls, which use the context's staging buffers and wait on its stream, are PEDP_ERR_BAD_ARG then. */
+enum { PEDP_ERR_ADD = 0, PEDP_ERR_ADDS = 1 };
+
+int pedp_pose_errors(pedp_ctx_t ctx, const double *pts, int64_t N, const double *preds, int B, const double *gts, int G,
+                     const double *sym, int S, int kind, int mem, double *out);
+
 /* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
  * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
  * The contract is DESIGN.md s4.11.  With pos = mask > 0, truthy = mask.astype(bool) (for a float32 mask they differ on
