@@ -7,6 +7,7 @@ so import it as `pedp_hip` (the small alias package at the repository root).
 Layout
   csrc/            HIP kernels + the C ABI (include/pedp.h) -> libpedp_hip.so
   _lib.py          ctypes binding; raises if the library or the GPU is missing
+  _bridge.py       the wrappers' torch / numpy plumbing: arrays on the call's side, launches on torch's stream
   geometry.py      PointCloud / TriangleMesh / RegistrationResult / PinholeCameraIntrinsic
                    holders with the attribute names the reference uses (Open3D duck types)
   registration.py  registration_icp, estimation/criteria classes, get_rotation_matrix_from_xyz

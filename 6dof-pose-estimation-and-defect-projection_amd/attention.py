@@ -14,7 +14,7 @@ import ctypes as C
 import math
 
 from . import _lib
-from .crop import _launch
+from ._bridge import launch, ptr
 
 HEAD_DIM = 128
 
@@ -57,9 +57,7 @@ def attention(q, k, v, num_heads, scale=None, out=None):
         raise _lib.PedpError(f"attention: out must be {(b, s, e)} on {q.device}")
     prm.o_ld = _rows(out, "out", e)
     prm.scale = 1.0 / math.sqrt(HEAD_DIM) if scale is None else float(scale)
-    _launch(q.device, "pedp_mha_f16", lambda lib, hd, mem: lib.pedp_mha_f16(
-        hd, C.byref(prm), C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()),
-        C.c_void_p(out.data_ptr())))
+    launch(q.device, "pedp_mha_f16", lambda lib, hd, mem: lib.pedp_mha_f16(hd, C.byref(prm), ptr(q), ptr(k), ptr(v), ptr(out)))
     return out
 
 
@@ -74,6 +72,20 @@ def mha_core(qkv, num_heads, scale=None, out=None):
     return attention(qkv[..., :e], qkv[..., e:2 * e], qkv[..., 2 * e:], num_heads, scale, out)
 
 
+def _check_mha(mha, who):
+    """The nn.MultiheadAttention the heads' kernels stand in for: anything else is refused in `who`'s name."""
+    if (not mha.batch_first or not mha._qkv_same_embed_dim or mha.bias_k is not None or mha.add_zero_attn
+            or mha.in_proj_weight is None):
+        raise _lib.PedpError(f"{who}: the module must be batch_first with one embed dim and no bias_k / zero attention")
+    if mha.training and mha.dropout > 0:
+        raise _lib.PedpError(f"{who}: dropout is not built")
+
+
+def _check_post_norm_relu(layer, who):
+    if layer.norm_first or getattr(layer, "activation_relu_or_gelu", 1) != 1:
+        raise _lib.PedpError(f"{who}: only the post-norm relu layer is decomposed")
+
+
 def self_attention(mha, x):
     """`mha(x, x, x, need_weights=False)[0]` of an nn.MultiheadAttention (batch_first, one embed dim for q, k, v, no bias_k /
     zero-attention, eval) on x: B x S x E on a GPU.  The two projections are torch's GEMMs in float16; between them runs
@@ -81,11 +93,7 @@ def self_attention(mha, x):
     import torch
     import torch.nn.functional as F
 
-    if (not mha.batch_first or not mha._qkv_same_embed_dim or mha.bias_k is not None or mha.add_zero_attn
-            or mha.in_proj_weight is None):
-        raise _lib.PedpError("self_attention: the module must be batch_first with one embed dim and no bias_k / zero attention")
-    if mha.training and mha.dropout > 0:
-        raise _lib.PedpError("self_attention: dropout is not built")
+    _check_mha(mha, "self_attention")
     if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16:
         cast = lambda t: t                       # autocast makes (and caches) the float16 weights itself
     else:
@@ -101,8 +109,7 @@ def encoder_layer(layer, x, attn=self_attention):
     with its signature."""
     import torch
 
-    if layer.norm_first or getattr(layer, "activation_relu_or_gelu", 1) != 1:
-        raise _lib.PedpError("encoder_layer: only the post-norm relu layer is decomposed")
+    _check_post_norm_relu(layer, "encoder_layer")
     y = layer.norm1(x + attn(layer.self_attn, x).to(x.dtype))
     return layer.norm2(y + layer.linear2(torch.relu(layer.linear1(y))).to(y.dtype))
 

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._bridge import wait_for_torch
 
 _SEED = 0
 
@@ -41,7 +42,7 @@ def voxel_down_sample(points, voxel_size, normals=None, ctx=None):
             raise _lib.PedpError(f"voxel_down_sample: the points are on cuda:{t.device.index}, the context on cuda:{ctx.device}")
         if t.dtype != torch.float64 or not t.is_contiguous():
             t = t.to(torch.float64).contiguous()              # (a float32 or strided tensor is copied on the device)
-        torch.cuda.current_stream(t.device).synchronize()     # the library reads the array on its own stream
+        wait_for_torch(t)
         out = np.empty((len(t), 3), np.float64)
         m = C.c_int64()
         _lib.check(_lib.load().pedp_voxel_down_sample_device_in(ctx._h, C.c_void_p(t.data_ptr()), len(t), float(voxel_size),
@@ -80,7 +81,7 @@ def preprocess_source_fused(points, voxel_size, plane_distance, plane_iterations
             raise _lib.PedpError(f"preprocess_source: the points are on cuda:{t.device.index}, the context on cuda:{ctx.device}")
         if t.dtype != torch.float64 or not t.is_contiguous():
             t = t.to(torch.float64).contiguous()
-        torch.cuda.current_stream(t.device).synchronize()     # the library reads the array on its own stream
+        wait_for_torch(t)
         n, ptr, on_dev, keep = len(t), C.c_void_p(t.data_ptr()), 1, t
     else:
         p = _pts(points)

@@ -17,7 +17,7 @@ not take raises.
 import ctypes as C
 
 from . import _lib
-from .crop import _launch
+from ._bridge import launch, ptr
 
 
 class PackedConv3x3:
@@ -44,36 +44,38 @@ def _f32(t):
     return None if t is None else t.detach().to(torch.float32).contiguous()
 
 
-def pack_conv3x3(conv, bn=None):
-    """Fold `bn` (BatchNorm2d in eval mode, or None) into `conv` (Conv2d on a GPU) in float32 and pack (pedp_conv3x3_pack)."""
+def _pack(who, conv, bn, k):
+    """Fold `bn` into `conv` in float32 and pack through `who`'s entry point: the packed weights, the bias, Cin, Cout."""
     import torch
 
-    if not supported(conv):
-        raise _lib.PedpError(f"pack_conv3x3: {conv} is not a stride-1, pad-1 3x3 convolution with channels in 32 .. 512 by 32")
     w = _f32(conv.weight)
     if not w.is_cuda:
-        raise _lib.PedpError("pack_conv3x3: the module must be on a GPU")
+        raise _lib.PedpError(f"{who}: the module must be on a GPU")
     dev, cin, cout = w.device, conv.in_channels, conv.out_channels
     b = _f32(conv.bias)
     g = be = mu = var = None
     eps = 0.0
     if bn is not None:
         if bn.running_mean is None or bn.running_var is None:
-            raise _lib.PedpError("pack_conv3x3: a BatchNorm2d without running statistics cannot be folded")
+            raise _lib.PedpError(f"{who}: a BatchNorm2d without running statistics cannot be folded")
         ones = torch.ones(cout, dtype=torch.float32, device=dev)
         g = _f32(bn.weight) if bn.weight is not None else ones
         be = _f32(bn.bias) if bn.bias is not None else torch.zeros_like(ones)
         mu, var, eps = _f32(bn.running_mean), _f32(bn.running_var), float(bn.eps)
     with torch.inference_mode(False):
-        wp = torch.empty((cout, 9, cin), dtype=torch.float16, device=dev)
+        wp = torch.empty((cout, 9, cin) if k == 3 else (cout, STEM_K), dtype=torch.float16, device=dev)
         bp = torch.empty((cout,), dtype=torch.float32, device=dev)
+    fn_name, dims = ("pedp_conv3x3_pack", (cin, cout)) if who == "pack_conv3x3" else ("pedp_conv2d_pack", (cin, cout, k, k))
+    launch(dev, fn_name, lambda lib, hd, mem: getattr(lib, fn_name)(
+        hd, *dims, ptr(w), ptr(b), ptr(g), ptr(be), ptr(mu), ptr(var), eps, ptr(wp), ptr(bp)))
+    return wp, bp, cin, cout
 
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
 
-    _launch(dev, "pedp_conv3x3_pack", lambda lib, hd, mem: lib.pedp_conv3x3_pack(
-        hd, cin, cout, p(w), p(b), p(g), p(be), p(mu), p(var), eps, p(wp), p(bp)))
-    return PackedConv3x3(wp, bp, cin, cout)
+def pack_conv3x3(conv, bn=None):
+    """Fold `bn` (BatchNorm2d in eval mode, or None) into `conv` (Conv2d on a GPU) in float32 and pack (pedp_conv3x3_pack)."""
+    if not supported(conv):
+        raise _lib.PedpError(f"pack_conv3x3: {conv} is not a stride-1, pad-1 3x3 convolution with channels in 32 .. 512 by 32")
+    return PackedConv3x3(*_pack("pack_conv3x3", conv, bn, 3))
 
 
 def _pixel_stride(t, name):
@@ -95,32 +97,17 @@ def conv3x3(x_nhwc, packed, residual=None, relu=True, out=None, out_c0=0):
     import torch
 
     x = x_nhwc
-    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.is_contiguous()):
-        raise _lib.PedpError("conv3x3: x must be a contiguous N x H x W x Cin float16 CUDA tensor")
-    n, h, w, cin = (int(v) for v in x.shape)
-    if cin != packed.cin:
-        raise _lib.PedpError(f"conv3x3: x has {cin} channels, the weights take {packed.cin}")
-    cout = packed.cout
-    if out is None:
-        out, out_c0 = torch.empty((n, h, w, cout), dtype=torch.float16, device=x.device), 0
-    if not (out.is_cuda and out.dtype == torch.float16 and out.dim() == 4 and out.is_contiguous()
-            and tuple(out.shape[:3]) == (n, h, w)):
-        raise _lib.PedpError(f"conv3x3: out must be a contiguous {n} x {h} x {w} x ld float16 CUDA tensor")
-    y_ld, out_c0 = int(out.shape[3]), int(out_c0)
-    if out_c0 < 0 or out_c0 + cout > y_ld:
-        raise _lib.PedpError(f"conv3x3: channels {out_c0} .. {out_c0 + cout} do not fit a destination of {y_ld}")
+    n, h, w, out, y_ld, out_c0 = _operands("conv3x3", x, packed, out, out_c0, 1)
+    cin, cout = packed.cin, packed.cout
     prm = _lib.Conv3x3Params()
     prm.N, prm.H, prm.W, prm.Cin, prm.Cout = n, h, w, cin, cout
     prm.y_ld, prm.y_c0, prm.relu = y_ld, out_c0, int(bool(relu))
-    r_ptr = None
     if residual is not None:
         if not (residual.is_cuda and residual.dtype == torch.float16 and tuple(residual.shape) == (n, h, w, cout)):
             raise _lib.PedpError(f"conv3x3: residual must be {n} x {h} x {w} x {cout} float16 on the GPU")
         prm.res_ld, prm.res_c0 = _pixel_stride(residual, "residual"), 0
-        r_ptr = C.c_void_p(residual.data_ptr())
-    _launch(x.device, "pedp_conv3x3_f16", lambda lib, hd, mem: lib.pedp_conv3x3_f16(
-        hd, C.byref(prm), C.c_void_p(x.data_ptr()), C.c_void_p(packed.w.data_ptr()), C.c_void_p(packed.bias.data_ptr()),
-        r_ptr, C.c_void_p(out.data_ptr())))
+    launch(x.device, "pedp_conv3x3_f16", lambda lib, hd, mem: lib.pedp_conv3x3_f16(
+        hd, C.byref(prm), ptr(x), ptr(packed.w), ptr(packed.bias), ptr(residual), ptr(out)))
     return out[..., out_c0:out_c0 + cout]
 
 
@@ -164,35 +151,11 @@ def out_hw(h, w, conv):
 def pack_conv(conv, bn=None):
     """pack_conv3x3 for a stride-2 layer (pedp_conv2d_pack): `bn` (BatchNorm2d in eval mode, or None) folded into `conv`
     (Conv2d on a GPU) in float32."""
-    import torch
-
     if not supported_strided(conv):
         raise _lib.PedpError(f"pack_conv: {conv} is neither a 3x3 / stride 2 / padding 1 convolution with channels in "
                              "32 .. 512 by 32 nor a 7x7 / stride 2 / padding 3 one with at most 8 input channels")
-    w = _f32(conv.weight)
-    if not w.is_cuda:
-        raise _lib.PedpError("pack_conv: the module must be on a GPU")
-    dev, cin, cout, k = w.device, conv.in_channels, conv.out_channels, int(conv.kernel_size[0])
-    b = _f32(conv.bias)
-    g = be = mu = var = None
-    eps = 0.0
-    if bn is not None:
-        if bn.running_mean is None or bn.running_var is None:
-            raise _lib.PedpError("pack_conv: a BatchNorm2d without running statistics cannot be folded")
-        ones = torch.ones(cout, dtype=torch.float32, device=dev)
-        g = _f32(bn.weight) if bn.weight is not None else ones
-        be = _f32(bn.bias) if bn.bias is not None else torch.zeros_like(ones)
-        mu, var, eps = _f32(bn.running_mean), _f32(bn.running_var), float(bn.eps)
-    with torch.inference_mode(False):
-        wp = torch.empty((cout, 9, cin) if k == 3 else (cout, STEM_K), dtype=torch.float16, device=dev)
-        bp = torch.empty((cout,), dtype=torch.float32, device=dev)
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
-    _launch(dev, "pedp_conv2d_pack", lambda lib, hd, mem: lib.pedp_conv2d_pack(
-        hd, cin, cout, k, k, p(w), p(b), p(g), p(be), p(mu), p(var), eps, p(wp), p(bp)))
-    return PackedConv(wp, bp, cin, cout, k, 2, (k - 1) // 2)
+    k = int(conv.kernel_size[0])
+    return PackedConv(*_pack("pack_conv", conv, bn, k), k, 2, (k - 1) // 2)
 
 
 def _destination(who, out, out_c0, n, oh, ow, cout, dev):
@@ -209,32 +172,34 @@ def _destination(who, out, out_c0, n, oh, ow, cout, dev):
     return out, y_ld, out_c0
 
 
+def _operands(who, x, packed, out, out_c0, stride):
+    """conv3x3's and conv_strided's check of x, of its channel count and of the destination of a stride-`stride` layer on
+    it: (n, h, w, out, y_ld, out_c0)."""
+    import torch
+
+    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.is_contiguous()):
+        raise _lib.PedpError(f"{who}: x must be a contiguous N x H x W x Cin float16 CUDA tensor")
+    n, h, w, cin = (int(v) for v in x.shape)
+    if cin != packed.cin:
+        raise _lib.PedpError(f"{who}: x has {cin} channels, the weights take {packed.cin}")
+    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
+    return (n, h, w, *_destination(who, out, out_c0, n, oh, ow, packed.cout, x.device))
+
+
 def _conv2d(who, prm, packed, x, x2, residual, out):
     prm.Cin, prm.Cout, prm.KH, prm.KW, prm.stride, prm.pad = packed.cin, packed.cout, packed.k, packed.k, packed.stride, packed.pad
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
-    _launch(out.device, "pedp_conv2d_f16", lambda lib, hd, mem: lib.pedp_conv2d_f16(
-        hd, C.byref(prm), p(x), p(x2), p(packed.w), p(packed.bias), p(residual), p(out)))
+    launch(out.device, "pedp_conv2d_f16", lambda lib, hd, mem: lib.pedp_conv2d_f16(
+        hd, C.byref(prm), ptr(x), ptr(x2), ptr(packed.w), ptr(packed.bias), ptr(residual), ptr(out)))
 
 
 def conv_strided(x_nhwc, packed, relu=True, out=None, out_c0=0, residual=None):
     """x N x H x W x Cin float16, dense -> the N x OH x OW x Cout result of a packed 3x3 stride-2 layer (pedp_conv2d_f16);
     `out` and `out_c0` as in conv3x3.  The stride-2 layers add no residual: one is refused, like a stride-1 layer (that is
     conv3x3's)."""
-    import torch
-
     x = x_nhwc
     if not (isinstance(packed, PackedConv) and packed.k == 3):
         raise _lib.PedpError("conv_strided: the weights must come from pack_conv on a 3x3 stride-2 layer")
-    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.is_contiguous()):
-        raise _lib.PedpError("conv_strided: x must be a contiguous N x H x W x Cin float16 CUDA tensor")
-    n, h, w, cin = (int(v) for v in x.shape)
-    if cin != packed.cin:
-        raise _lib.PedpError(f"conv_strided: x has {cin} channels, the weights take {packed.cin}")
-    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    out, y_ld, out_c0 = _destination("conv_strided", out, out_c0, n, oh, ow, packed.cout, x.device)
+    n, h, w, out, y_ld, out_c0 = _operands("conv_strided", x, packed, out, out_c0, 2)
     prm = _lib.Conv2dParams()
     prm.N, prm.H, prm.W, prm.layout, prm.dtype, prm.N0 = n, h, w, _lib.NHWC, _lib.F16, n
     prm.y_ld, prm.y_c0, prm.relu = y_ld, out_c0, int(bool(relu))

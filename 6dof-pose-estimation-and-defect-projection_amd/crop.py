@@ -22,7 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .depth_filters import _is_torch, _stream_context
+from ._bridge import as_array, as_kind, device_of, empty, is_torch, launch, ptr, to_device
 from .render import nvdiffrast_render
 
 
@@ -40,69 +40,17 @@ class BatchPoseData:
         self.mesh_diameters, self.labels = mesh_diameters, labels
 
 
-# ---------------------------------------------------------------- dispatch
-
-def _launch(dev, fn_name, call):
-    """call(lib, ctx_handle, mem) on the device's context ordered with torch's current stream, or on host memory."""
-    lib = _lib.load()
-    if dev is None:
-        _lib.check(call(lib, _lib.default_context()._h, _lib.HOST), fn_name)
-        return
-    import torch
-
-    cur = torch.cuda.current_stream(dev)
-    ctx = _stream_context(dev.index or 0, cur.cuda_stream)
-    shared = ctx.stream_handle not in (None, 0) and ctx.stream_handle == cur.cuda_stream
-    if not shared:
-        cur.synchronize()  # the context runs on another stream: the inputs must be complete
-    _lib.check(call(lib, ctx._h, _lib.DEVICE), fn_name)
-    if not shared:
-        ctx.synchronize()  # ... and the outputs before torch touches them
-
-
-def _device_of(*xs):
-    return next((x.device for x in xs if _is_torch(x) and x.is_cuda), None)
-
-
-def _ptr(a):
-    if a is None:
-        return None
-    return C.c_void_p(a.data_ptr()) if _is_torch(a) else _lib._ptr(a)
-
-
-def _to_device(x, dev, u8_ok=False):
-    """x as a float32 (or, with u8_ok, uint8) tensor on `dev` without a host wait: device tensors stay where they are;
-    host arrays go through page-locked memory and a copy ordered on the current stream (a pageable copy would make
-    torch synchronise the stream)."""
-    import torch
-
-    def cast(t):
-        return t if t.dtype == torch.float32 or (u8_ok and t.dtype == torch.uint8) else t.float()
-
-    if _is_torch(x) and x.is_cuda:
-        return cast(x if x.device == dev else x.to(dev))
-    t = x.detach() if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
-    return cast(t).contiguous().pin_memory().to(dev, non_blocking=True)
-
-
-def _f32(x, dev):
-    """x as a contiguous float32 array on the call's side (torch on `dev`, numpy on the host)."""
-    if dev is not None:
-        return _to_device(x, dev).contiguous()
-    if _is_torch(x):
-        x = x.detach().cpu().numpy()
-    return np.ascontiguousarray(x, dtype=np.float32)
-
+# ---------------------------------------------------------------- image sources
 
 def _source(x, dev):
     """An image source as a uint8 / float32 array on the call's side, its strides kept (expanded and permuted views
     go through without a copy)."""
     if dev is not None:
-        t = _to_device(x, dev, u8_ok=True)
+        t = to_device(x, dev, u8_ok=True)
         if any(s < 0 for s in t.stride()):
             t = t.contiguous()
         return t
-    a = x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
+    a = x.detach().cpu().numpy() if is_torch(x) else np.asarray(x)
     if a.dtype not in (np.uint8, np.float32):
         a = a.astype(np.float32)
     if any(s < 0 or s % a.itemsize for s in a.strides):
@@ -111,7 +59,7 @@ def _source(x, dev):
 
 
 def _strides(a):
-    return tuple(a.stride()) if _is_torch(a) else tuple(s // a.itemsize for s in a.strides)
+    return tuple(a.stride()) if is_torch(a) else tuple(s // a.itemsize for s in a.strides)
 
 
 def _image(a, dims):
@@ -119,29 +67,12 @@ def _image(a, dims):
     st = dict(zip(dims, _strides(a)))
     ext = dict(zip(dims, (int(v) for v in a.shape)))
     im = _lib.Image()
-    im.data = _ptr(a).value if _ptr(a) is not None else None
-    u8 = (str(a.dtype) == "torch.uint8") if _is_torch(a) else a.dtype == np.uint8
+    im.data = ptr(a).value if ptr(a) is not None else None
+    u8 = (str(a.dtype) == "torch.uint8") if is_torch(a) else a.dtype == np.uint8
     im.dtype = _lib.U8 if u8 else _lib.F32
     im.N, im.C, im.H, im.W = (ext.get(k, 1) for k in "NCHW")
     im.sn, im.sc, im.sy, im.sx = (st.get(k, 0) for k in "NCHW")
     return im
-
-
-def _empty(dev, shape):
-    if dev is not None:
-        import torch
-
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-    return np.empty(shape, np.float32)
-
-
-def _as_kind(a, like):
-    """Host results come back as the kind of the caller's input (CPU tensor or numpy)."""
-    if _is_torch(a) or not _is_torch(like):
-        return a
-    import torch
-
-    return torch.from_numpy(a)
 
 
 def _dsize(dsize):
@@ -160,13 +91,13 @@ def warp_perspective(src, M, dsize, mode="bilinear", padding_mode="zeros", align
         raise NotImplementedError(f"warp_perspective: mode {mode!r}")
     if padding_mode != "zeros":
         raise NotImplementedError(f"warp_perspective: padding_mode {padding_mode!r}")
-    if (_is_torch(src) and src.requires_grad) or (_is_torch(M) and M.requires_grad):
+    if (is_torch(src) and src.requires_grad) or (is_torch(M) and M.requires_grad):
         raise NotImplementedError("warp_perspective: gradients are not supported")
     if len(getattr(src, "shape", ())) != 4:
         raise _lib.PedpError(f"warp_perspective: src must be N x C x H x W, got shape {tuple(getattr(src, 'shape', ()))}")
-    dev = _device_of(src, M)
+    dev = device_of(src, M)
     s = _source(src, dev)
-    m = _f32(M, dev)
+    m = as_array(M, dev)
     if m.ndim != 3 or tuple(m.shape[1:]) != (3, 3):
         raise _lib.PedpError(f"warp_perspective: M must be B x 3 x 3, got shape {tuple(m.shape)}")
     B = int(m.shape[0])
@@ -174,10 +105,10 @@ def warp_perspective(src, M, dsize, mode="bilinear", padding_mode="zeros", align
         raise _lib.PedpError(f"warp_perspective: {int(s.shape[0])} source images for {B} matrices")
     h, w = _dsize(dsize)
     im = _image(s, "NCHW")
-    out = _empty(dev, (B, int(s.shape[1]), h, w))
-    _launch(dev, "pedp_warp_perspective", lambda lib, hd, mem: lib.pedp_warp_perspective(
-        hd, C.byref(im), _ptr(m), B, h, w, 1 if mode == "nearest" else 0, int(bool(align_corners)), mem, _ptr(out)))
-    return _as_kind(out, src)
+    out = empty(dev, (B, int(s.shape[1]), h, w))
+    launch(dev, "pedp_warp_perspective", lambda lib, hd, mem: lib.pedp_warp_perspective(
+        hd, C.byref(im), ptr(m), B, h, w, 1 if mode == "nearest" else 0, int(bool(align_corners)), mem, ptr(out)))
+    return as_kind(out, src)
 
 
 class _Transform:
@@ -199,18 +130,18 @@ kornia = _Kornia()
 # ---------------------------------------------------------------- crop windows
 
 def _crop_window(poses, K, radius, out_w, out_h, corner, want_bbox):
-    dev = _device_of(poses)
-    p = _f32(poses, dev).reshape(-1, 16)
-    Kf = np.ascontiguousarray(np.asarray(K.detach().cpu().numpy() if _is_torch(K) else K, dtype=np.float64), dtype=np.float32)
+    dev = device_of(poses)
+    p = as_array(poses, dev).reshape(-1, 16)
+    Kf = np.ascontiguousarray(np.asarray(K.detach().cpu().numpy() if is_torch(K) else K, dtype=np.float64), dtype=np.float32)
     if Kf.size != 9:
         raise _lib.PedpError("K must be 3 x 3")
     B = int(p.shape[0])
-    tf = _empty(dev, (B, 3, 3))
-    bb = _empty(dev, (B, 4)) if want_bbox else None
-    _launch(dev, "pedp_crop_window", lambda lib, hd, mem: lib.pedp_crop_window(
-        hd, _ptr(p), B, _lib._ptr(Kf), float(np.float32(radius)), int(out_w), int(out_h), float(corner[0]), float(corner[1]), mem,
-        _ptr(tf), _ptr(bb)))
-    return _as_kind(tf, poses), (None if bb is None else _as_kind(bb, poses))
+    tf = empty(dev, (B, 3, 3))
+    bb = empty(dev, (B, 4)) if want_bbox else None
+    launch(dev, "pedp_crop_window", lambda lib, hd, mem: lib.pedp_crop_window(
+        hd, ptr(p), B, _lib._ptr(Kf), float(np.float32(radius)), int(out_w), int(out_h), float(corner[0]), float(corner[1]), mem,
+        ptr(tf), ptr(bb)))
+    return as_kind(tf, poses), (None if bb is None else as_kind(bb, poses))
 
 
 def compute_crop_window_tf_batch(pts=None, H=None, W=None, poses=None, K=None, crop_ratio=1.2, out_size=None, rgb=None,
@@ -250,8 +181,8 @@ def crop_pass(variant, tf_to_crops, poseA, K, mesh_diameter, rgb, rgb_r, xyz_r, 
     B, oh, ow = (int(v) for v in rgb_r.shape[:3])
     if tuple(xyz_r.shape) != (B, oh, ow, 3) or tuple(rgb_r.shape) != (B, oh, ow, 3):
         raise _lib.PedpError("rgb_r and xyz_r must be B x h x w x 3")
-    rgb_r, xyz_r = _f32(rgb_r, dev), _f32(xyz_r, dev)
-    tf, poseA = _f32(tf_to_crops, dev), _f32(poseA, dev)
+    rgb_r, xyz_r = as_array(rgb_r, dev), as_array(xyz_r, dev)
+    tf, poseA = as_array(tf_to_crops, dev), as_array(poseA, dev)
     if tuple(tf.shape) != (B, 3, 3) or tuple(poseA.shape) != (B, 4, 4):
         raise _lib.PedpError("tf_to_crops must be B x 3 x 3 and poseA B x 4 x 4")
     s_rgb = _source(rgb, dev)
@@ -278,7 +209,7 @@ def crop_pass(variant, tf_to_crops, poseA, K, mesh_diameter, rgb, rgb_r, xyz_r, 
             if normal_map is None:
                 raise _lib.PedpError("make_crop_data_batch: cfg['use_normal'] needs normal_map")
             frame("normal", normal_map, 3)
-    Kf = np.asarray(K.detach().cpu().numpy() if _is_torch(K) else K, dtype=np.float64).astype(np.float32).reshape(9)
+    Kf = np.asarray(K.detach().cpu().numpy() if is_torch(K) else K, dtype=np.float64).astype(np.float32).reshape(9)
     prm = _lib.CropParams()
     prm.variant, prm.normalize_xyz, prm.use_normal, prm.B = variant, int(bool(normalize_xyz)), int(use_normal), B
     prm.H, prm.W, prm.out_h, prm.out_w = H, W, oh, ow
@@ -297,14 +228,14 @@ def crop_pass(variant, tf_to_crops, poseA, K, mesh_diameter, rgb, rgb_r, xyz_r, 
         return C.byref(srcs[k]) if k in srcs else None
 
     if packed:
-        _launch(dev, "pedp_crop_batch_packed", lambda lib, hd, mem: lib.pedp_crop_batch_packed(
-            hd, C.byref(prm), _ptr(tf), _ptr(poseA), img("rgb"), img("xyz"), img("normal"), img("depth"), _ptr(rgb_r),
-            _ptr(xyz_r), mem, _ptr(out["A"]), _ptr(out["B"]), _ptr(out["normalB"]), _ptr(out["depthB"])))
+        launch(dev, "pedp_crop_batch_packed", lambda lib, hd, mem: lib.pedp_crop_batch_packed(
+            hd, C.byref(prm), ptr(tf), ptr(poseA), img("rgb"), img("xyz"), img("normal"), img("depth"), ptr(rgb_r),
+            ptr(xyz_r), mem, ptr(out["A"]), ptr(out["B"]), ptr(out["normalB"]), ptr(out["depthB"])))
         return out
-    _launch(dev, "pedp_crop_batch", lambda lib, hd, mem: lib.pedp_crop_batch(
-        hd, C.byref(prm), _ptr(tf), _ptr(poseA), img("rgb"), img("xyz"), img("normal"), img("depth"), _ptr(rgb_r),
-        _ptr(xyz_r), mem, _ptr(out["rgbA"]), _ptr(out["rgbB"]), _ptr(out["xyzA"]), _ptr(out["xyzB"]), _ptr(out["normalB"]),
-        _ptr(out["depthB"])))
+    launch(dev, "pedp_crop_batch", lambda lib, hd, mem: lib.pedp_crop_batch(
+        hd, C.byref(prm), ptr(tf), ptr(poseA), img("rgb"), img("xyz"), img("normal"), img("depth"), ptr(rgb_r),
+        ptr(xyz_r), mem, ptr(out["rgbA"]), ptr(out["rgbB"]), ptr(out["xyzA"]), ptr(out["xyzB"]), ptr(out["normalB"]),
+        ptr(out["depthB"])))
     return out
 
 
@@ -325,12 +256,12 @@ def _crop_batch(variant, render_size, ob_in_cams, mesh, rgb, depth, K, crop_rati
     dcfg = getattr(dataset, "cfg", None) if dataset is not None else None
     normalize = bool(_cfg(dcfg if dcfg is not None else cfg, "normalize_xyz", False))
     H, W = (int(v) for v in depth.shape[:2])
-    dev = _device_of(ob_in_cams, rgb, depth, xyz_map)
+    dev = device_of(ob_in_cams, rgb, depth, xyz_map)
     if dev is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    poseA = _to_device(ob_in_cams, dev).reshape(-1, 4, 4).contiguous()
+    poseA = to_device(ob_in_cams, dev).reshape(-1, 4, 4).contiguous()
     B = int(poseA.shape[0])
-    Kf = np.asarray(K.detach().cpu().numpy() if _is_torch(K) else K, dtype=np.float64).astype(np.float32).reshape(3, 3)
+    Kf = np.asarray(K.detach().cpu().numpy() if is_torch(K) else K, dtype=np.float64).astype(np.float32).reshape(3, 3)
 
     tf_to_crops, bbox2d = _crop_window(poseA, Kf, mesh_diameter * crop_ratio / 2, ow, oh, (ir[0] - 1, ir[1] - 1), True)
     extra = {}
@@ -347,7 +278,7 @@ def _crop_batch(variant, render_size, ob_in_cams, mesh, rgb, depth, K, crop_rati
     if use_normal and not scorer:  # the reference warps the crop-sized render like a full frame (predict_pose_refine.py:74)
         normalA = warp_perspective(normal_r.permute(0, 3, 1, 2), tf_to_crops, dsize=rs, mode="nearest", align_corners=False)
     mesh_diameters = torch.ones(B, dtype=torch.float32, device=dev) * mesh_diameter
-    Ks = _to_device(Kf, dev).reshape(1, 3, 3)
+    Ks = to_device(Kf, dev).reshape(1, 3, 3)
     if scorer:
         Ks = Ks.expand(B, 3, 3)
     cls = batch_cls or BatchPoseData

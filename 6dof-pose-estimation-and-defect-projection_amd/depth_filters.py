@@ -15,50 +15,25 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
+from ._bridge import device_of, empty, is_torch, launch, ptr, wait_for_torch
 
 
 def _run(fn_name, depth, out_shape_tail, call, ctx=None):
     """Dispatch one image-shaped call on host (numpy) or device (torch) memory."""
-    lib = _lib.load()
-    if _is_torch(depth):
+    if is_torch(depth) and not depth.is_cuda:
         import torch
 
-        if not depth.is_cuda:
-            return torch.from_numpy(_run(fn_name, depth.numpy(), out_shape_tail, call, ctx))
+        return torch.from_numpy(_run(fn_name, depth.numpy(), out_shape_tail, call, ctx))
+    dev = device_of(depth)
+    if dev is not None:
+        import torch
+
         d = depth.contiguous().to(torch.float32)
-        out = torch.empty(tuple(d.shape) + out_shape_tail, dtype=torch.float32, device=d.device)
-        cur = torch.cuda.current_stream(d.device)
-        if ctx is None:
-            ctx = _stream_context(d.device.index or 0, cur.cuda_stream)
-        shared = ctx.stream_handle not in (None, 0) and ctx.stream_handle == cur.cuda_stream
-        if not shared:
-            cur.synchronize()  # the context runs on another stream: the input must be complete
-        _lib.check(call(lib, ctx._h, C.c_void_p(d.data_ptr()), _lib.DEVICE, C.c_void_p(out.data_ptr()), d.shape), fn_name)
-        if not shared:
-            ctx.synchronize()  # ... and the output before torch touches it
-        return out
-    d = np.ascontiguousarray(depth, dtype=np.float32)
-    ctx = ctx or _lib.default_context()
-    out = np.empty(d.shape + out_shape_tail, np.float32)
-    _lib.check(call(lib, ctx._h, _lib._ptr(d), _lib.HOST, _lib._ptr(out), d.shape), fn_name)
+    else:
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+    out = empty(dev, tuple(d.shape) + out_shape_tail)
+    launch(dev, fn_name, lambda lib, h, mem: call(lib, h, ptr(d), mem, ptr(out), d.shape), ctx)
     return out
-
-
-_stream_ctx = {}
-
-
-def _stream_context(device, stream_handle):
-    """A context per (device, torch stream).  torch's default stream has handle 0, which the C
-    ABI reads as "own stream": such a context is not ordered with torch and _run synchronises
-    around the call instead."""
-    key = (device, stream_handle)
-    if key not in _stream_ctx:
-        _stream_ctx[key] = _lib.Context(device, stream=stream_handle or None)
-    return _stream_ctx[key]
 
 
 def _hw(shape):
@@ -89,9 +64,9 @@ def depth2xyzmap(depth, K, uvs=None, ctx=None):
         # map stays zero.  A listed pixel's value is the full map's, so the full map comes from the
         # device and the listed pixels are picked out of it.
         full = depth2xyzmap(depth, K, None, ctx)
-        on_device = _is_torch(full)
+        on_device = is_torch(full)
         arr = full.detach().cpu().numpy() if on_device else np.asarray(full)
-        uv = np.asarray(uvs.detach().cpu().numpy() if _is_torch(uvs) else uvs).round().astype(int)
+        uv = np.asarray(uvs.detach().cpu().numpy() if is_torch(uvs) else uvs).round().astype(int)
         out = np.zeros_like(arr)
         out[uv[:, 1], uv[:, 0]] = arr[uv[:, 1], uv[:, 0]]
         if on_device:
@@ -99,7 +74,7 @@ def depth2xyzmap(depth, K, uvs=None, ctx=None):
 
             return torch.from_numpy(out).to(full.device)
         return out
-    Kd = np.ascontiguousarray(np.asarray(K.detach().cpu().numpy() if _is_torch(K) else K), dtype=np.float64).reshape(3, 3)
+    Kd = np.ascontiguousarray(np.asarray(K.detach().cpu().numpy() if is_torch(K) else K), dtype=np.float64).reshape(3, 3)
 
     def call(lib, h, src, mem, dst, shape):
         H, W = _hw(shape)
@@ -108,7 +83,7 @@ def depth2xyzmap(depth, K, uvs=None, ctx=None):
 
 
 def depth2xyzmap_batch(depths, Ks, zfar, ctx=None):
-    Kf = np.ascontiguousarray(np.asarray(Ks.detach().cpu().numpy() if _is_torch(Ks) else Ks), dtype=np.float32)
+    Kf = np.ascontiguousarray(np.asarray(Ks.detach().cpu().numpy() if is_torch(Ks) else Ks), dtype=np.float32)
 
     def call(lib, h, src, mem, dst, shape):
         if len(shape) != 3:
@@ -131,9 +106,9 @@ def depth_to_scene(depth, K, erode_radius=2, bilateral_radius=2, depth_diff_thre
 
     ctx = ctx or _lib.default_context()
     dev = torch.device(f"cuda:{ctx.device}")
-    if _is_torch(depth):
+    if is_torch(depth):
         d_in = depth.to(dev, torch.float32).contiguous()
-        torch.cuda.current_stream(dev).synchronize()            # the library reads it on its own stream
+        wait_for_torch(d_in)
         H, W = _hw(d_in.shape)
         src, mem, keep = C.c_void_p(d_in.data_ptr()), _lib.DEVICE, d_in
     else:
@@ -147,10 +122,10 @@ def depth_to_scene(depth, K, erode_radius=2, bilateral_radius=2, depth_diff_thre
         buffers["xyz"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
         buffers["points"] = [torch.empty((H * W, 3), dtype=torch.float64, device=dev) for _ in range(2)]
         buffers["turn"] = 0
-        torch.cuda.current_stream(dev).synchronize()
+        wait_for_torch(buffers["depth"])
     buffers["turn"] ^= 1                                          # two point buffers in turn: a frame's cloud outlives the next call
     pts = buffers["points"][buffers["turn"]]
-    Kf = np.asarray(K.detach().cpu().numpy() if _is_torch(K) else K, dtype=np.float32).reshape(9)
+    Kf = np.asarray(K.detach().cpu().numpy() if is_torch(K) else K, dtype=np.float32).reshape(9)
     prm = _lib.DepthEntryParams(int(erode_radius), float(depth_diff_thres), float(ratio_thres), float(erode_zfar), int(bilateral_radius),
                                 float(bilateral_zfar), float(sigmaD), float(sigmaR), (C.c_float * 9)(*Kf.tolist()), float(xyz_zfar),
                                 float(z_min), float(scale))

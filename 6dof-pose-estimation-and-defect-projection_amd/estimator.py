@@ -23,8 +23,9 @@ import random
 import numpy as np
 
 from . import _lib, cloud_ops
-from .crop import _crop_batch, _device_of, _launch, _ptr, _source, _to_device
-from .depth_filters import _is_torch, bilateral_filter_depth, depth2xyzmap, depth2xyzmap_batch, erode_depth
+from ._bridge import device_of, is_torch, launch, ptr, to_device
+from .crop import _crop_batch, _source
+from .depth_filters import bilateral_filter_depth, depth2xyzmap, depth2xyzmap_batch, erode_depth
 from .pose import max_pair_distance, pose_update, update_params
 from .render import RasterizeCudaContext, make_mesh_tensors
 
@@ -32,7 +33,7 @@ from .render import RasterizeCudaContext, make_mesh_tensors
 # ---------------------------------------------------------------- mask / depth statistics
 
 def _host(x):
-    return x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
+    return x.detach().cpu().numpy() if is_torch(x) else np.asarray(x)
 
 
 def _dtype_name(x):
@@ -62,12 +63,12 @@ def mask_depth_stats(depth, mask):
     H, W = int(ds[0]), int(ds[1])
     if H <= 0 or W <= 0 or H * W > 4096 * 4096:
         raise _lib.PedpError(f"mask_depth_stats: {H} x {W} frame (1 to 4096 x 4096 pixels)")
-    dev = _device_of(depth, mask)
+    dev = device_of(depth, mask)
     if dev is not None:
         import torch
 
-        d = _to_device(depth, dev).contiguous()
-        m = mask if _is_torch(mask) else torch.from_numpy(np.ascontiguousarray(mask))
+        d = to_device(depth, dev).contiguous()
+        m = mask if is_torch(mask) else torch.from_numpy(np.ascontiguousarray(mask))
         if not m.is_cuda:
             m = m.contiguous().pin_memory().to(dev, non_blocking=True)
         m = (m if m.device == dev else m.to(dev)).contiguous()
@@ -77,8 +78,8 @@ def mask_depth_stats(depth, mask):
         m = np.ascontiguousarray(_host(mask))
         f32 = m.dtype == np.float32
     rec = _lib.MaskDepthStats()
-    _launch(dev, "pedp_mask_depth_stats", lambda lib, h, mem: lib.pedp_mask_depth_stats(
-        h, _ptr(d), _ptr(m), _lib.F32 if f32 else _lib.U8, H, W, mem, C.byref(rec)))
+    launch(dev, "pedp_mask_depth_stats", lambda lib, h, mem: lib.pedp_mask_depth_stats(
+        h, ptr(d), ptr(m), _lib.F32 if f32 else _lib.U8, H, W, mem, C.byref(rec)))
     out = {k: int(getattr(rec, k)) for k in ("n_pos", "n_valid", "n_med", "umin", "umax", "vmin", "vmax")}
     out["median"] = np.float32(rec.median)
     return out
@@ -292,7 +293,7 @@ def _no_vis(get_vis):
 def _frame_device(*xs):
     import torch
 
-    dev = _device_of(*xs)
+    dev = device_of(*xs)
     return dev if dev is not None else torch.device("cuda", torch.cuda.current_device())
 
 
@@ -330,8 +331,8 @@ class PoseRefinePredictor:
                             trans_normalizer=tn if isinstance(tn, (int, float)) else [float(v) for v in tn],
                             rot_normalizer=cfg["rot_normalizer"], mesh_diameter=mesh_diameter if mesh_diameter is not None else 1.0)
         with torch.inference_mode():
-            poses = _to_device(ob_in_cams, dev).reshape(-1, 4, 4).contiguous()
-            rgb_d, depth_d, xyz_d = _source(rgb, dev), _to_device(depth, dev), _to_device(xyz_map, dev)   # up once
+            poses = to_device(ob_in_cams, dev).reshape(-1, 4, 4).contiguous()
+            rgb_d, depth_d, xyz_d = _source(rgb, dev), to_device(depth, dev), to_device(xyz_map, dev)   # up once
             n = int(poses.shape[0])
             for _ in range(int(iteration)):
                 batch = _crop_batch(0, cfg["input_resize"], poses, mesh, rgb_d, depth_d, K, cfg["crop_ratio"], xyz_d, normal_map,
@@ -368,7 +369,7 @@ class ScorePredictor:
         if mesh_tensors is None:
             mesh_tensors = make_mesh_tensors(mesh)
         with torch.inference_mode():
-            poses = _to_device(ob_in_cams, dev).reshape(-1, 4, 4).contiguous()
+            poses = to_device(ob_in_cams, dev).reshape(-1, 4, 4).contiguous()
             batch = _crop_batch(1, cfg["input_resize"], poses, mesh, rgb, depth, K, cfg["crop_ratio"], None, None, mesh_diameter,
                                 cfg, glctx, mesh_tensors, None, None, packed=True)
             A, B = batch.A, batch.B
@@ -480,7 +481,7 @@ class FoundationPose:
         if self.glctx is None:
             self.glctx = glctx if glctx is not None else RasterizeCudaContext()
         dev = _frame_device(depth, rgb)
-        depth = _to_device(depth, dev)
+        depth = to_device(depth, dev)
         depth = erode_depth(depth, radius=2, device="cuda")
         depth = bilateral_filter_depth(depth, radius=2, device="cuda")
         rec = _stats(depth, ob_mask)
@@ -543,7 +544,7 @@ class FoundationPose:
 
         if self.pose_last is None:
             raise RuntimeError("track_one: initialise the pose with register first")
-        depth = torch.as_tensor(depth, device="cuda", dtype=torch.float) if not (_is_torch(depth) and depth.is_cuda) \
+        depth = torch.as_tensor(depth, device="cuda", dtype=torch.float) if not (is_torch(depth) and depth.is_cuda) \
             else depth.float()
         depth = erode_depth(depth, radius=2, device="cuda")
         depth = bilateral_filter_depth(depth, radius=2, device="cuda")

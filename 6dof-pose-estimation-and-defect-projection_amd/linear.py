@@ -15,8 +15,8 @@ fallback here: a shape, dtype or device the kernels do not take raises.
 import ctypes as C
 
 from . import _lib
-from .attention import mha_core
-from .crop import _launch
+from ._bridge import launch, ptr
+from .attention import _check_mha, _check_post_norm_relu, mha_core
 
 LN_N = 512
 POOL_E = 512
@@ -126,8 +126,7 @@ def _run(who, x, packed, epilogue, res, pos, period, norm, out, pos_on_x):
         prm.pos_a = int(bool(pos_on_x)) if pos is not None else 0
     else:
         pos, prm.pos_rows, prm.pos_period = _table(pos, period, packed.k, who)
-    ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-    _launch(x.device, "pedp_linear_f16", lambda lib, hd, mem: lib.pedp_linear_f16(
+    launch(x.device, "pedp_linear_f16", lambda lib, hd, mem: lib.pedp_linear_f16(
         hd, C.byref(prm), ptr(x), ptr(packed.weight), ptr(packed.bias), ptr(res), ptr(pos), ptr(gamma), ptr(beta), ptr(out)))
     return out
 
@@ -170,21 +169,12 @@ def token_pool(x, groups, packed=None, out=None):
     elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float16 and out.device == x.device and tuple(out.shape) == shape
               and out.is_contiguous()):
         raise _lib.PedpError(f"token_pool: out must be a contiguous {shape} float16 tensor on {x.device}")
-    ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-    _launch(x.device, "pedp_token_pool_f16", lambda lib, hd, mem: lib.pedp_token_pool_f16(hd, C.byref(prm), ptr(x), ptr(w), ptr(b),
-                                                                                           ptr(out)))
+    launch(x.device, "pedp_token_pool_f16", lambda lib, hd, mem: lib.pedp_token_pool_f16(
+        hd, C.byref(prm), ptr(x), ptr(w), ptr(b), ptr(out)))
     return out
 
 
 # ---------------------------------------------------------------- the heads' modules over the three kernels
-
-def _check_mha(mha, who):
-    if (not mha.batch_first or not mha._qkv_same_embed_dim or mha.bias_k is not None or mha.add_zero_attn
-            or mha.in_proj_weight is None):
-        raise _lib.PedpError(f"{who}: the module must be batch_first with one embed dim and no bias_k / zero attention")
-    if mha.training and mha.dropout > 0:
-        raise _lib.PedpError(f"{who}: dropout is not built")
-
 
 def pack_attention(mha):
     """{'in': ..., 'out': ...}: the packed projections of an nn.MultiheadAttention."""
@@ -220,8 +210,7 @@ def encoder_layer_fused(layer, x, packs, pos=None, period=None, qkv=None, attn=N
     """`layer(x + pos)` of an nn.TransformerEncoderLayer with torch's defaults (post-norm, relu, eval) on the raw tokens
     x: B x S x 512 float16, in five launches: in-projection with the table, mha_core, out-projection + add + norm1 (the table
     added to the residual), linear1 + relu (into `attn`), linear2 + add + norm2 (in place).  Returns `out`."""
-    if layer.norm_first or getattr(layer, "activation_relu_or_gelu", 1) != 1:
-        raise _lib.PedpError("encoder_layer_fused: only the post-norm relu layer is decomposed")
+    _check_post_norm_relu(layer, "encoder_layer_fused")
     _check_mha(layer.self_attn, "encoder_layer_fused")
     qkv = linear(x, packs["in"], pos=pos, period=period, out=qkv)
     o = mha_core(qkv, layer.self_attn.num_heads, out=attn)

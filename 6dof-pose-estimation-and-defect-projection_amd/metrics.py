@@ -14,43 +14,10 @@ non-finite inputs) is DESIGN.md s4.15.
 import numpy as np
 
 from . import _lib
-from .crop import _as_kind, _device_of, _launch, _ptr
-from .depth_filters import _is_torch
+from ._bridge import as_array, as_kind, check_out, device_of, empty, is_torch, launch, ptr
 
 MAX_POSES = 65535          # pedp_pose_errors' bounds
 MAX_POINTS = 1 << 22
-
-
-def _f64(x, dev):
-    """x as a contiguous float64 array on the call's side; float32 widens exactly.  On a device a host array goes up
-    through page-locked memory with a copy ordered on the current stream (no host wait)."""
-    if dev is None:
-        return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float64)
-    import torch
-
-    if _is_torch(x) and x.is_cuda:
-        return x.to(device=dev, dtype=torch.float64).contiguous()
-    t = x.detach() if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
-    return t.to(torch.float64).contiguous().pin_memory().to(dev, non_blocking=True)
-
-
-def _check_out(name, out, n, dev):
-    """The library writes n float64 values through out's pointer, on the inputs' side: anything else is refused."""
-    where = f"on {dev}" if dev is not None else "in host memory"
-    if _is_torch(out):
-        import torch
-
-        ok = (out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (n,)
-              and (out.device == dev if dev is not None else not out.is_cuda))
-        kind = f"{out.dtype} tensor of shape {tuple(out.shape)} on {out.device}{'' if out.is_contiguous() else ', strided'}"
-    else:
-        a = out if isinstance(out, np.ndarray) else None
-        ok = (dev is None and a is not None and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable
-              and a.shape == (n,))
-        kind = (f"{type(out).__name__}" if a is None else
-                f"{a.dtype} array of shape {a.shape}{'' if a.flags.c_contiguous else ', strided'}")
-    if not ok:
-        raise _lib.PedpError(f"{name}: out must be a C-contiguous float64 array of {n} values {where}, got a {kind}")
 
 
 def _errors(kind, name, preds, gts, model_pts, symmetry_tfs, out):
@@ -74,21 +41,17 @@ def _errors(kind, name, preds, gts, model_pts, symmetry_tfs, out):
         S = 1 if len(sshape) == 2 else sshape[0]
         if S > MAX_POSES:
             raise _lib.PedpError(f"{name}: at most {MAX_POSES} symmetries, got {S}")
-    dev = _device_of(preds, gts, model_pts, symmetry_tfs)
+    dev = device_of(preds, gts, model_pts, symmetry_tfs)
     if out is not None:
-        _check_out(name, out, B, dev)
-    elif dev is None:
-        out = np.empty(B, np.float64)
+        check_out(name, out, (B,), np.float64, dev, f"C-contiguous float64 array of {B} values")
     else:
-        import torch
-
-        out = torch.empty(B, dtype=torch.float64, device=dev)
+        out = empty(dev, B, np.float64)
     if B:
-        p, g, m = _f64(preds, dev), _f64(gts, dev), _f64(model_pts, dev)
-        s = _f64(symmetry_tfs, dev) if S else None
-        _launch(dev, "pedp_pose_errors", lambda lib, h, mem: lib.pedp_pose_errors(
-            h, _ptr(m), N, _ptr(p), B, _ptr(g), G, _ptr(s), S, kind, mem, _ptr(out)))
-    return _as_kind(out, preds)
+        p, g, m = (as_array(x, dev, np.float64) for x in (preds, gts, model_pts))
+        s = as_array(symmetry_tfs, dev, np.float64) if S else None
+        launch(dev, "pedp_pose_errors", lambda lib, h, mem: lib.pedp_pose_errors(
+            h, ptr(m), N, ptr(p), B, ptr(g), G, ptr(s), S, kind, mem, ptr(out)))
+    return as_kind(out, preds)
 
 
 def add_err_batch(preds, gts, model_pts, symmetry_tfs=None, out=None):
@@ -111,7 +74,7 @@ def _one(fn, name, pred, gt, model_pts):
     if tuple(pred.shape) != (4, 4) or tuple(gt.shape) != (4, 4):
         raise _lib.PedpError(f"{name}: pred and gt must be 4 x 4, got {tuple(pred.shape)} and {tuple(gt.shape)}")
     e = fn(pred.reshape(1, 4, 4), gt, model_pts)
-    return np.float64(e.cpu().numpy()[0] if _is_torch(e) else e[0])
+    return np.float64(e.cpu().numpy()[0] if is_torch(e) else e[0])
 
 
 def add_err(pred, gt, model_pts, symetry_tfs=None):

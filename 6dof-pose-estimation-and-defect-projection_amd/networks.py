@@ -137,6 +137,11 @@ def _pair_encoder(norm):
                          _BasicBlock(512, norm), _BasicBlock(512, norm))
 
 
+def _pack_block(conv, bn):
+    """A block convolution's packed form; None: a layer the kernel does not take, kept on torch."""
+    return _conv.pack_conv3x3(conv, bn) if _conv.supported(conv) else None
+
+
 def _fp16_autocast():
     return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.float16
 
@@ -158,36 +163,30 @@ class _PairNet(nn.Module):
         self.set_strided(strided)
         self.set_linears(linears)
 
+    def _set(self, name, value, allowed):
+        if value not in allowed:
+            raise ValueError(f"{name} must be one of {allowed}, got {value!r}")
+        setattr(self, name, value)
+        return self
+
     def set_backend(self, backend):
         """'hip': every block convolution through the kernel; 'torch': none; 'auto': per layer by the measured table."""
-        if backend not in _BACKENDS:
-            raise ValueError(f"backend must be one of {_BACKENDS}, got {backend!r}")
-        self.backend = backend
-        return self
+        return self._set("backend", backend, _BACKENDS)
 
     def set_heads(self, heads):
         """'hip': the heads' attention through attention.self_attention (eval, GPU, float16 autocast); 'torch': the stock
         modules."""
-        if heads not in _HEADS:
-            raise ValueError(f"heads must be one of {_HEADS}, got {heads!r}")
-        self.heads = heads
-        return self
+        return self._set("heads", heads, _HEADS)
 
     def set_strided(self, strided):
         """'hip': the three stride-2 convolutions through conv.conv_stem / conv.conv_strided (eval, GPU, float16
         autocast); 'torch': the stock modules."""
-        if strided not in _STRIDED:
-            raise ValueError(f"strided must be one of {_STRIDED}, got {strided!r}")
-        self.strided = strided
-        return self
+        return self._set("strided", strided, _STRIDED)
 
     def set_linears(self, linears):
         """'hip': with heads='hip', the heads' linear layers, LayerNorms and means through linear.linear, linear_add_norm
         and token_pool (eval, GPU, float16 autocast); 'torch': the stock modules."""
-        if linears not in _LINEARS:
-            raise ValueError(f"linears must be one of {_LINEARS}, got {linears!r}")
-        self.linears = linears
-        return self
+        return self._set("linears", linears, _LINEARS)
 
     def _heads_fused(self, x):
         return self.heads == "hip" and not self.training and x.is_cuda and _fp16_autocast()
@@ -200,24 +199,31 @@ class _PairNet(nn.Module):
         self._buffers_nhwc = {}
         self._buffers_tok = {}
 
-    def _pack_head(self, module, pack):
+    def _memo(self, module, pack, *args):
+        """self._packed's entry of `module`, made by pack(module, *args) on first use."""
         key = id(module)
         if key not in self._packed:
-            self._packed[key] = pack(module)
+            self._packed[key] = pack(module, *args)
         return self._packed[key]
+
+    @staticmethod
+    def _kept(cache, key, make):
+        """cache[key], allocated by make() outside inference mode on first use.  A tracker alternates between a few
+        batch sizes; do not hoard more: at four keys the cache is cleared."""
+        buf = cache.get(key)
+        if buf is None:
+            if len(cache) >= 4:
+                cache.clear()
+            with torch.inference_mode(False):
+                buf = cache[key] = make()
+        return buf
 
     def _tokens(self, tok, names=("qkv", "a", "y")):
         """The tokens of `encode` as contiguous float16 and the kept buffers `names` of the heads at this batch and length:
         'qkv' bs x S x 1536, 'a' and 'y' bs x S x 512."""
         bs, s, e = (int(v) for v in tok.shape)
-        key = (tok.device, bs, s)
-        buf = self._buffers_tok.get(key)
-        if buf is None:
-            if len(self._buffers_tok) >= 4:
-                self._buffers_tok.clear()
-            with torch.inference_mode(False):
-                buf = self._buffers_tok[key] = {n: torch.empty((bs, s, 3 * e if n == "qkv" else e), dtype=torch.float16,
-                                                               device=tok.device) for n in names}
+        buf = self._kept(self._buffers_tok, (tok.device, bs, s), lambda: {
+            n: torch.empty((bs, s, 3 * e if n == "qkv" else e), dtype=torch.float16, device=tok.device) for n in names})
         if tok.dtype != torch.float16 or not tok.is_contiguous():      # the torch encoder's channels-first result
             if "tok" not in buf:
                 with torch.inference_mode(False):
@@ -262,18 +268,11 @@ class _PairNet(nn.Module):
     def _pack(self, conv, bn):
         if not self._uses_kernel(conv.out_channels):
             return None
-        key = id(conv)
-        if key not in self._packed:
-            self._packed[key] = _conv.pack_conv3x3(conv, bn) if _conv.supported(conv) else None
-        return self._packed[key]
+        return self._memo(conv, _pack_block, bn)
 
     def _pack_strided(self, block):
         """The packed form of a stride-2 _ConvNormReLU; a layer the kernels do not take raises (conv.pack_conv)."""
-        conv = block.net[0]
-        key = id(conv)
-        if key not in self._packed:
-            self._packed[key] = _conv.pack_conv(conv, block.net[1] if isinstance(block.net[1], nn.BatchNorm2d) else None)
-        return self._packed[key]
+        return self._memo(block.net[0], _conv.pack_conv, block.net[1] if isinstance(block.net[1], nn.BatchNorm2d) else None)
 
     def _conv(self, x, conv, bn, residual=None, out=None, out_c0=0):
         """One block convolution with its norm, optional identity add and ReLU: x, residual N x H x W x C float16 ->
@@ -294,20 +293,17 @@ class _PairNet(nn.Module):
     def _scratch(self, dev, bs, h, w, strided_hw=None):
         """The buffers of a forward of `bs` pairs at h x w after the shared encoder's two stride-2 layers; with
         strided_hw = (h1, w1, h3, w3), the sizes after the stem and after the pair encoder's stride-2 layer, also theirs."""
-        key = (dev, bs, h, w, strided_hw)
-        buf = self._buffers_nhwc.get(key)
-        if buf is None:
-            if len(self._buffers_nhwc) >= 4:     # a tracker alternates between a few batch sizes; do not hoard more
-                self._buffers_nhwc.clear()
-            with torch.inference_mode(False):
-                def e(n, hh, ww, c):
-                    return torch.empty((n, hh, ww, c), dtype=torch.float16, device=dev)
-                buf = self._buffers_nhwc[key] = {"x": e(2 * bs, h, w, 128), "t": e(2 * bs, h, w, 128), "ab": e(bs, h, w, 256),
-                                                 "t2": e(bs, h, w, 256)}
-                if strided_hw is not None:
-                    h1, w1, h3, w3 = strided_hw
-                    buf.update({"s": e(2 * bs, h1, w1, 64), "y": e(bs, h3, w3, 512), "t3": e(bs, h3, w3, 512)})
-        return buf
+        def e(n, hh, ww, c):
+            return torch.empty((n, hh, ww, c), dtype=torch.float16, device=dev)
+
+        def make():
+            buf = {"x": e(2 * bs, h, w, 128), "t": e(2 * bs, h, w, 128), "ab": e(bs, h, w, 256), "t2": e(bs, h, w, 256)}
+            if strided_hw is not None:
+                h1, w1, h3, w3 = strided_hw
+                buf.update({"s": e(2 * bs, h1, w1, 64), "y": e(bs, h3, w3, 512), "t3": e(bs, h3, w3, 512)})
+            return buf
+
+        return self._kept(self._buffers_nhwc, (dev, bs, h, w, strided_hw), make)
 
     def _encode_fused(self, A, B):
         bs = len(A)
@@ -380,9 +376,9 @@ class RefineNet(_PairNet):
 
     def _head_fused(self, head, tok, buf):
         """A head on the raw tokens: the encoder layer in five launches, then the mean and the final Linear in one."""
-        y = _lin.encoder_layer_fused(head[0], tok, self._pack_head(head[0], _lin.pack_encoder_layer), self.pos_embed.pe,
+        y = _lin.encoder_layer_fused(head[0], tok, self._memo(head[0], _lin.pack_encoder_layer), self.pos_embed.pe,
                                      tok.shape[1], qkv=buf["qkv"], attn=buf["a"], out=buf["y"])
-        return _lin.token_pool(y, len(tok), self._pack_head(head[1], _lin.pack_f32))
+        return _lin.token_pool(y, len(tok), self._memo(head[1], _lin.pack_f32))
 
     def forward(self, A, B):
         tok = self.encode(A, B)
@@ -425,7 +421,7 @@ class ScoreNetMultiPair(_PairNet):
         tok = self.encode(A, B)
         if self._linears_fused(tok):
             tok, buf = self._tokens(tok, ("qkv", "a"))
-            return _lin.attention_pooled_fused(self.att, tok, self._pack_head(self.att, _lin.pack_attention), self.pos_embed.pe,
+            return _lin.attention_pooled_fused(self.att, tok, self._memo(self.att, _lin.pack_attention), self.pos_embed.pe,
                                                tok.shape[1], qkv=buf["qkv"], attn=buf["a"])
         ab = self.pos_embed(tok)
         ab = self._attend(self.att, ab)
@@ -435,8 +431,8 @@ class ScoreNetMultiPair(_PairNet):
         bs = A.shape[0] // L
         x = self.extract_feat(A, B).reshape(bs, L, -1)
         if self._linears_fused(x):
-            o = _lin.self_attention_fused(self.att_cross, x, self._pack_head(self.att_cross, _lin.pack_attention))
-            return {"score_logit": _lin.token_pool(o, bs * L, self._pack_head(self.linear, _lin.pack_f32)).reshape(bs, L)}
+            o = _lin.self_attention_fused(self.att_cross, x, self._memo(self.att_cross, _lin.pack_attention))
+            return {"score_logit": _lin.token_pool(o, bs * L, self._memo(self.linear, _lin.pack_f32)).reshape(bs, L)}
         x = self._attend(self.att_cross, x)
         return {"score_logit": self.linear(x).reshape(bs, L)}
 

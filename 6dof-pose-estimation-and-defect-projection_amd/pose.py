@@ -13,8 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .crop import _device_of, _launch, _ptr, _to_device
-from .depth_filters import _is_torch
+from ._bridge import as_array, check_out, device_of, empty, launch, ptr
 
 _ROT = {"axis_angle": _lib.ROT_AXIS_ANGLE, "6d": _lib.ROT_6D}
 
@@ -54,68 +53,34 @@ def pose_update(trans, rot, poseA, params=None, out=None, want_deltas=False, **k
         raise _lib.PedpError(f"pose_update: poseA must be N x 4 x 4, got {shape}")
     n = shape[0]
     width = 6 if prm.rot_rep == _lib.ROT_6D else 3
-    dev = _device_of(trans, rot, poseA)
+    dev = device_of(trans, rot, poseA)
 
     def take(x, k, what):
-        if dev is not None:
-            a = _to_device(x, dev).contiguous()
-        else:
-            a = np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+        a = as_array(x, dev)
         if int(np.prod(tuple(a.shape))) != n * k or (k < 16 and tuple(a.shape) not in ((n, k), (n * k,))):
             raise _lib.PedpError(f"pose_update: {what} must be {n} x {k}, got {tuple(a.shape)}")
         return a
 
-    def new(*s):
-        if dev is None:
-            return np.empty(s, np.float32)
-        import torch
-
-        return torch.empty(s, dtype=torch.float32, device=dev)
-
     pa, t, r = take(poseA, 16, "poseA"), take(trans, 3, "trans"), take(rot, width, "rot")
     if out is None:
-        out = new(n, 4, 4)
+        out = empty(dev, (n, 4, 4))
     else:
-        _check_out(out, n, dev)
-    td, rd = (new(n, 3), new(n, 3, 3)) if want_deltas else (None, None)
-    _launch(dev, "pedp_pose_update", lambda lib, h, mem: lib.pedp_pose_update(
-        h, C.byref(prm), n, _ptr(t), _ptr(r), _ptr(pa), mem, _ptr(out), _ptr(td), _ptr(rd)))
+        check_out("pose_update", out, (n, 4, 4), np.float32, dev, f"C-contiguous {n} x 4 x 4 float32 array")
+    td, rd = (empty(dev, (n, 3)), empty(dev, (n, 3, 3))) if want_deltas else (None, None)
+    launch(dev, "pedp_pose_update", lambda lib, h, mem: lib.pedp_pose_update(
+        h, C.byref(prm), n, ptr(t), ptr(r), ptr(pa), mem, ptr(out), ptr(td), ptr(rd)))
     return out, td, rd
-
-
-def _check_out(out, n, dev):
-    """The kernel writes 16 n float32 values through out's pointer, on the inputs' side: anything else is refused."""
-    where = f"on {dev}" if dev is not None else "in host memory"
-    if _is_torch(out):
-        import torch
-
-        ok = (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 4, 4)
-              and (out.device == dev if dev is not None else not out.is_cuda))
-        kind = f"{out.dtype} tensor of shape {tuple(out.shape)} on {out.device}{'' if out.is_contiguous() else ', strided'}"
-    else:
-        a = out if isinstance(out, np.ndarray) else None
-        ok = (dev is None and a is not None and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable
-              and a.shape == (n, 4, 4))
-        kind = (f"{type(out).__name__}" if a is None else
-                f"{a.dtype} array of shape {a.shape}{'' if a.flags.c_contiguous else ', strided'}")
-    if not ok:
-        raise _lib.PedpError(f"pose_update: out must be a C-contiguous {n} x 4 x 4 float32 array {where}, got a {kind}")
 
 
 def max_pair_distance(pts):
     """The largest distance between two of the n x 3 points (numpy, CPU or CUDA tensor; float64), equal bit for bit to
     numpy's `np.linalg.norm(p[None] - p[:, None], axis=-1).max()`; NaN if a coordinate is not finite, 0.0 for one
     point.  Returns a Python float (the call waits for it)."""
-    dev = _device_of(pts)
-    if dev is not None:
-        import torch
-
-        p = pts.to(torch.float64).contiguous()
-    else:
-        p = np.ascontiguousarray(pts.detach().cpu().numpy() if _is_torch(pts) else pts, dtype=np.float64)
+    dev = device_of(pts)
+    p = as_array(pts, dev, np.float64)
     if p.ndim != 2 or p.shape[1] != 3:
         raise _lib.PedpError(f"max_pair_distance: expected n x 3 points, got {tuple(p.shape)}")
     res = C.c_double()
-    _launch(dev, "pedp_max_pair_distance", lambda lib, h, mem: lib.pedp_max_pair_distance(
-        h, _ptr(p), int(p.shape[0]), mem, C.byref(res)))
+    launch(dev, "pedp_max_pair_distance", lambda lib, h, mem: lib.pedp_max_pair_distance(
+        h, ptr(p), int(p.shape[0]), mem, C.byref(res)))
     return res.value

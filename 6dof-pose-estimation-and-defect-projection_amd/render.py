@@ -23,7 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .depth_filters import _is_torch, _stream_context
+from ._bridge import device_of, empty, is_torch, launch, ptr
 
 glcam_in_cvcam = np.array([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]]).astype(float)
 
@@ -60,7 +60,7 @@ def projection_matrix_from_intrinsics(K, height, width, znear, zfar, window_coor
 def _np(x, dtype):
     if x is None:
         return None
-    if _is_torch(x):
+    if is_torch(x):
         x = x.detach().cpu().numpy()
     return np.ascontiguousarray(x, dtype=dtype)
 
@@ -118,12 +118,12 @@ def make_mesh_tensors(mesh, device="cuda", max_tex_size=None):
 # ---------------------------------------------------------------- dispatch
 
 class _Call:
-    """One library call on host (numpy) or device (torch CUDA) memory: inputs are made contiguous float32 / int32 on
-    the call's side, outputs allocated there; device calls are ordered on the caller's current torch stream."""
+    """The arrays of one library call on host (numpy) or device (torch CUDA) memory: inputs are made contiguous float32 /
+    int32 on the call's side (host arrays by a pageable copy that torch waits for), results come back as the inputs' kind."""
 
     def __init__(self, *probe):
-        self.dev = next((x.device for x in probe if _is_torch(x) and x.is_cuda), None)
-        self.torch_cpu = _is_torch(probe[0]) and not probe[0].is_cuda  # host results come back as the first input's kind
+        self.dev = device_of(*probe)
+        self.torch_cpu = is_torch(probe[0]) and not probe[0].is_cuda  # host results come back as the first input's kind
         self.keep = []
 
     def arr(self, x, dtype="f4"):
@@ -139,43 +139,21 @@ class _Call:
         self.keep.append(a)
         return a
 
-    def ptr(self, a):
-        if a is None:
-            return None
-        return C.c_void_p(a.data_ptr()) if self.dev is not None else _lib._ptr(a)
-
-    def empty(self, shape):
-        if self.dev is not None:
-            import torch
-
-            return torch.empty(shape, dtype=torch.float32, device=self.dev)
-        return np.empty(shape, np.float32)
-
-    def run(self, fn_name, call):
-        lib = _lib.load()
-        if self.dev is not None:
-            import torch
-
-            cur = torch.cuda.current_stream(self.dev)
-            ctx = _stream_context(self.dev.index or 0, cur.cuda_stream)
-            shared = ctx.stream_handle not in (None, 0) and ctx.stream_handle == cur.cuda_stream
-            if not shared:
-                cur.synchronize()  # the context runs on another stream: the inputs must be complete
-            _lib.check(lib.pedp_render_configure(ctx._h, _pose_chunk), "pedp_render_configure")
-            _lib.check(call(lib, ctx._h, _lib.DEVICE), fn_name)
-            if not shared:
-                ctx.synchronize()  # ... and the outputs before torch touches them
-        else:
-            ctx = _lib.default_context()
-            _lib.check(lib.pedp_render_configure(ctx._h, _pose_chunk), "pedp_render_configure")
-            _lib.check(call(lib, ctx._h, _lib.HOST), fn_name)
-
     def result(self, a):
         if a is None or self.dev is not None or not self.torch_cpu:
             return a
         import torch
 
         return torch.from_numpy(a)
+
+
+def _run(call, fn_name, fn):
+    """launch with the pose chunk set on the same context in front of the call."""
+    def configured(lib, h, mem):
+        _lib.check(lib.pedp_render_configure(h, _pose_chunk), "pedp_render_configure")
+        return fn(lib, h, mem)
+
+    launch(call.dev, fn_name, configured)
 
 
 def _shape_error(msg):
@@ -201,7 +179,7 @@ def nvdiffrast_render(K=None, H=None, W=None, ob_in_cams=None, glctx=None, conte
     if context not in ("cuda", "gl"):
         raise NotImplementedError(context)
     if mesh_tensors is None:
-        dev = ob_in_cams.device if _is_torch(ob_in_cams) else "cpu"
+        dev = ob_in_cams.device if is_torch(ob_in_cams) else "cpu"
         mesh_tensors = make_mesh_tensors(mesh, device=dev)
     call = _Call(ob_in_cams, mesh_tensors["pos"])
     poses = call.arr(ob_in_cams)
@@ -265,12 +243,12 @@ def nvdiffrast_render(K=None, H=None, W=None, ob_in_cams=None, glctx=None, conte
     if light_color is not None:
         prm.light_color[:] = np.broadcast_to(_np(light_color, np.float32).reshape(-1), (3,)).tolist()
     prm.w_ambient, prm.w_diffuse = float(w_ambient), float(w_diffuse)
-    color = call.empty((N, oh, ow, 3))
-    depth = call.empty((N, oh, ow))
-    normal = call.empty((N, oh, ow, 3)) if get_normal else None
-    xyz = call.empty((N, oh, ow, 3))
-    p = call.ptr
-    call.run("pedp_render", lambda lib, h, mem: lib.pedp_render(
+    color = empty(call.dev, (N, oh, ow, 3))
+    depth = empty(call.dev, (N, oh, ow))
+    normal = empty(call.dev, (N, oh, ow, 3)) if get_normal else None
+    xyz = empty(call.dev, (N, oh, ow, 3))
+    p = ptr
+    _run(call, "pedp_render", lambda lib, h, mem: lib.pedp_render(
         h, p(verts), V, p(faces), F, p(vnormals), p(vcolor), p(uv), p(tex), th, tw, p(poses), p(bb), N, C.byref(prm), mem,
         p(color), p(depth), p(normal), p(xyz)))
     extra["xyz_map"] = call.result(xyz)
@@ -289,7 +267,7 @@ class RasterizeCudaContext:
 def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     """Instanced mode: pos N x V x 4 clip space, tri F x 3 -> (rast_out N x H x W x 4, None); rast_out = (u, v, z/w,
     triangle id + 1), zero on the background, GL row order (row 0 at NDC y = -1)."""
-    if ranges is not None or (_is_torch(pos) and pos.requires_grad):
+    if ranges is not None or (is_torch(pos) and pos.requires_grad):
         raise NotImplementedError("dr.rasterize: range mode and gradients are not supported")
     if len(getattr(pos, "shape", ())) != 3:
         raise NotImplementedError("dr.rasterize: instanced mode only (pos N x V x 4)")
@@ -299,14 +277,14 @@ def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
         raise _shape_error(f"dr.rasterize: pos must be N x V x 4 and tri F x 3, got {tuple(P.shape)}, {tuple(T.shape)}")
     H, W = _resolution(resolution)
     N, V, F = int(P.shape[0]), int(P.shape[1]), int(T.shape[0])
-    out = call.empty((N, H, W, 4))
-    call.run("pedp_rasterize", lambda lib, h, mem: lib.pedp_rasterize(h, call.ptr(P), N, V, call.ptr(T), F, H, W, mem, call.ptr(out)))
+    out = empty(call.dev, (N, H, W, 4))
+    _run(call, "pedp_rasterize", lambda lib, h, mem: lib.pedp_rasterize(h, ptr(P), N, V, ptr(T), F, H, W, mem, ptr(out)))
     return call.result(out), None
 
 
 def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
     """attr V x A or N x V x A, rast N x H x W x 4, tri F x 3 -> (out N x H x W x A, None); zero on the background."""
-    if diff_attrs is not None or (_is_torch(attr) and attr.requires_grad):
+    if diff_attrs is not None or (is_torch(attr) and attr.requires_grad):
         raise NotImplementedError("dr.interpolate: gradients are not supported")
     call = _Call(attr, rast, tri)
     A_, R, T = call.arr(attr), call.arr(rast), call.arr(tri, "i4")
@@ -317,9 +295,9 @@ def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
     if batched and A_.shape[0] != N:
         raise _shape_error(f"dr.interpolate: {A_.shape[0]} attribute sets for {N} images")
     V, A = int(A_.shape[-2]), int(A_.shape[-1])
-    out = call.empty((N, H, W, A))
-    call.run("pedp_interpolate", lambda lib, h, mem: lib.pedp_interpolate(
-        h, call.ptr(A_), int(batched), V, A, call.ptr(R), N, H, W, call.ptr(T), int(T.shape[0]), mem, call.ptr(out)))
+    out = empty(call.dev, (N, H, W, A))
+    _run(call, "pedp_interpolate", lambda lib, h, mem: lib.pedp_interpolate(
+        h, ptr(A_), int(batched), V, A, ptr(R), N, H, W, ptr(T), int(T.shape[0]), mem, ptr(out)))
     return call.result(out), None
 
 
@@ -329,7 +307,7 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="aut
         raise NotImplementedError("dr.texture: mipmaps are not supported")
     if filter_mode not in ("linear", "auto") or boundary_mode != "wrap":
         raise NotImplementedError(f"dr.texture: filter_mode {filter_mode!r} / boundary_mode {boundary_mode!r}")
-    if (_is_torch(tex) and tex.requires_grad) or (_is_torch(uv) and uv.requires_grad):
+    if (is_torch(tex) and tex.requires_grad) or (is_torch(uv) and uv.requires_grad):
         raise NotImplementedError("dr.texture: gradients are not supported")
     call = _Call(tex, uv)
     Tx, U = call.arr(tex), call.arr(uv)
@@ -337,9 +315,9 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="aut
         raise _shape_error("dr.texture: tex must be n x h x w x C and uv N x H x W x 2")
     N, H, W = (int(v) for v in U.shape[:3])
     tn, th, tw, Cc = (int(v) for v in Tx.shape)
-    out = call.empty((N, H, W, Cc))
-    call.run("pedp_texture", lambda lib, h, mem: lib.pedp_texture(h, call.ptr(Tx), tn, th, tw, Cc, call.ptr(U), N, H, W, mem,
-                                                                  call.ptr(out)))
+    out = empty(call.dev, (N, H, W, Cc))
+    _run(call, "pedp_texture", lambda lib, h, mem: lib.pedp_texture(h, ptr(Tx), tn, th, tw, Cc, ptr(U), N, H, W, mem,
+                                                             ptr(out)))
     return call.result(out)
 
 

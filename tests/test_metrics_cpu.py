@@ -174,6 +174,21 @@ def test_bad_arguments_are_refused_before_any_library_call(monkeypatch):
             fn(np.eye(4), np.eye(3), pts)
 
 
+def test_the_out_refusal_says_what_it_got():
+    """The full text of the batch functions' refusal of `out`: a wrong dtype, a wrong shape, a strided array."""
+    from pedp_hip import _lib, metrics
+
+    P, pts = np.tile(np.eye(4, dtype=np.float32), (2, 1, 1)), np.zeros((5, 3))
+    for fn in (metrics.add_err_batch, metrics.adds_err_batch):
+        want = f"{fn.__name__}: out must be a C-contiguous float64 array of 2 values in host memory, got a "
+        for out, got in ((np.empty(2, np.float32), "float32 array of shape (2,)"),
+                         (np.empty(3, np.float64), "float64 array of shape (3,)"),
+                         (np.empty(4, np.float64)[::2], "float64 array of shape (2,), strided")):
+            with pytest.raises(_lib.PedpError) as e:
+                fn(P, P[0], pts, out=out)
+            assert str(e.value) == want + got
+
+
 def test_the_abi_symbol_is_declared_and_exported():
     from pedp_hip import _lib
 

@@ -1,5 +1,9 @@
 """The pose kernels' numpy restatement (tests/_pose_ref.py) against independent references, and the parameter mapping
 of pose.py; no GPU."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -107,3 +111,29 @@ def test_pose_update_checks_its_arguments_before_any_launch():
         pose_update(t, t, P, params=update_params(), rot_rep="6d")
     with pytest.raises(NotImplementedError):
         pose_update(t, t, P, trans_rep="deepim")
+
+
+def test_the_out_refusal_says_what_it_got():
+    """The full text of pose_update's refusal of `out`: a wrong dtype, a wrong shape, a strided array."""
+    from pedp_hip import _lib
+    from pedp_hip.pose import pose_update
+
+    P = np.tile(np.eye(4, dtype=np.float32), (2, 1, 1))
+    t = np.zeros((2, 3), np.float32)
+    want = "pose_update: out must be a C-contiguous 2 x 4 x 4 float32 array in host memory, got a "
+    for out, got in ((np.empty((2, 4, 4), np.float64), "float64 array of shape (2, 4, 4)"),
+                     (np.empty((3, 4, 4), np.float32), "float32 array of shape (3, 4, 4)"),
+                     (np.empty((2, 4, 8), np.float32)[:, :, ::2], "float32 array of shape (2, 4, 4), strided")):
+        with pytest.raises(_lib.PedpError) as e:
+            pose_update(t, t, P, out=out)
+        assert str(e.value) == want + got
+
+
+def test_the_kernel_wrappers_do_not_load_the_crop_builder_the_renderer_or_the_depth_filters():
+    """In a fresh interpreter: the wrappers take their plumbing from _bridge, not from the modules written before them."""
+    code = ("import sys, pedp_hip.linear, pedp_hip.attention, pedp_hip.conv, pedp_hip.pose, pedp_hip.metrics\n"
+            "print(*sorted(m for m in ('pedp_hip.crop', 'pedp_hip.render', 'pedp_hip.depth_filters') if m in sys.modules))")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "-c", code], cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 0, p.stderr.decode()
+    assert p.stdout.decode().split() == []
