@@ -157,6 +157,11 @@ PROTOTYPES = {
     "pedp_max_pair_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_double)]),
     "pedp_pose_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pedp_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "pedp_mesh_face_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "pedp_closest_configure": (C.c_int, [C.c_void_p, C.c_int]),
+    "pedp_closest_last_stats": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_mask_depth_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
@@ -541,6 +546,42 @@ class Mesh:
         check(load().pedp_raycast(self.ctx._h, self._h, C.c_void_p(rays_ptr), int(n), DEVICE, C.c_void_p(t_ptr),
                                   C.c_void_p(id_ptr), C.c_void_p(uv_ptr) if uv_ptr else None), "pedp_raycast")
 
+    CLOSEST_OUTPUTS = {"points": (3, np.float64), "distances": (None, np.float64), "primitive_ids": (None, np.uint32),
+                       "primitive_uvs": (2, np.float64), "sides": (None, np.int8)}
+
+    def closest_points(self, points, want=("points", "distances", "primitive_ids", "primitive_uvs", "sides")):
+        """The closest point of the mesh, as posed, to every row of `points` (N x 3 host array, taken as float64):
+        pedp_closest_points, DESIGN.md s4.16.  Returns a dict like RaycastingScene.compute_closest_points with the
+        entries named in `want`: points N x 3 f64, distances N f64, primitive_ids N u32 (0xFFFFFFFF: none),
+        primitive_uvs N x 2 f64 (v, w), sides N int8 (the side of the chosen face's normal, -1 / 0 / +1)."""
+        for k in want:
+            if k not in self.CLOSEST_OUTPUTS:
+                raise PedpError(f"closest_points: unknown output {k!r} (one of {', '.join(self.CLOSEST_OUTPUTS)})")
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise PedpError(f"closest_points: points must be N x 3, got shape {p.shape}")
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        n = len(p)
+        out = {k: np.empty((n,) if w is None else (n, w), t) for k, (w, t) in self.CLOSEST_OUTPUTS.items() if k in want}
+        check(load().pedp_closest_points(self.ctx._h, self._h, _ptr(p), n, HOST, _ptr(out.get("points")),
+                                         _ptr(out.get("distances")), _ptr(out.get("primitive_ids")),
+                                         _ptr(out.get("primitive_uvs")), _ptr(out.get("sides"))), "pedp_closest_points")
+        return out
+
+    def face_normals(self, primitive_ids):
+        """N x 3 float64 unit normals (ab x ac) of the listed triangles of the mesh as posed; NaN where an id names none."""
+        ids = np.ascontiguousarray(primitive_ids, dtype=np.uint32).reshape(-1)
+        out = np.empty((len(ids), 3), np.float64)
+        check(load().pedp_mesh_face_normals(self.ctx._h, self._h, _ptr(ids), len(ids), HOST, _ptr(out)), "pedp_mesh_face_normals")
+        return out
+
+    def closest_points_device(self, pts_ptr, n, closest_ptr=None, dist_ptr=None, id_ptr=None, uv_ptr=None, side_ptr=None):
+        """Device-pointer variant (torch tensors' data_ptr(), float64 points); asynchronous on the stream."""
+        def vp(x):
+            return C.c_void_p(x) if x else None
+        check(load().pedp_closest_points(self.ctx._h, self._h, C.c_void_p(pts_ptr), int(n), DEVICE, vp(closest_ptr),
+                                         vp(dist_ptr), vp(id_ptr), vp(uv_ptr), vp(side_ptr)), "pedp_closest_points")
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             load().pedp_mesh_destroy(self._h)
@@ -668,6 +709,19 @@ def nn_last_sweep_ms(ctx):
     ms = C.c_float(0)
     check(load().pedp_nn_last_sweep_ms(ctx._h, C.byref(ms)), "pedp_nn_last_sweep_ms")
     return ms.value
+
+
+def closest_configure(ctx, exhaustive=False):
+    """pedp_closest_configure: exhaustive=True (1) tests every point against every triangle (no culling); 2 / 3 keep the
+    culling and force the lane-per-point / wave-per-point kernel at every batch size (the bits are the same)."""
+    check(load().pedp_closest_configure(ctx._h, int(exhaustive)), "pedp_closest_configure")
+
+
+def closest_last_stats(ctx):
+    """Point-triangle pairs the last closest-point call on ctx evaluated (waits for the stream)."""
+    n = C.c_int64(0)
+    check(load().pedp_closest_last_stats(ctx._h, C.byref(n)), "pedp_closest_last_stats")
+    return n.value
 
 
 def icp_configure(ctx, exhaustive=False, timed_pass=-1):

@@ -8,7 +8,9 @@ renderer (`nvdiffrast_render`, `make_mesh_tensors` and the `dr` stand-in for `nv
 arithmetic of its refinement loop (`pose_update`, `max_pair_distance`), and the estimator with the two predictors'
 loops (`FoundationPose`, `PoseRefinePredictor`, `ScorePredictor`, estimator.py), and the two networks with their
 checkpoint loaders (`RefineNet`, `ScoreNetMultiPair`, `load_refiner`, `load_scorer`, networks.py), and the evaluation
-metrics (`add_err`, `adds_err`, their batch forms, `compute_auc_sklearn`, `symmetry_tfs_from_info`, metrics.py); the Dash app, sensor
+metrics (`add_err`, `adds_err`, their batch forms, `compute_auc_sklearn`, `symmetry_tfs_from_info`, metrics.py), and the
+exact cloud-to-mesh distance with the deviation heat map (`closest_points`, `compute_distance`, `align_to_mesh`,
+`deviation_heatmap`, surface_distance.py); the Dash app, sensor
 code and the networks' weights stay the reference's own.
 """
 import numpy as np
@@ -54,6 +56,7 @@ from .estimator import (FoundationPose, PoseRefinePredictor, ScorePredictor, com
                         euler_matrix, guess_translation, mask_depth_stats, sample_views_icosphere, set_seed)
 from .metrics import (add_err, add_err_batch, adds_err, adds_err_batch, compute_auc_sklearn,  # noqa: E402,F401  (Utils.py:232-266, :806-834)
                       symmetry_tfs_from_info)
+from .surface_distance import align_to_mesh, closest_points, compute_distance, deviation_heatmap  # noqa: E402,F401  (run.py:64's heat map)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
 
@@ -87,4 +90,5 @@ __all__ = [
     "sample_views_icosphere", "euler_matrix", "compute_mesh_diameter",
     "RefineNet", "ScoreNetMultiPair", "load_refiner", "load_scorer",
     "add_err", "adds_err", "add_err_batch", "adds_err_batch", "compute_auc_sklearn", "symmetry_tfs_from_info",
+    "closest_points", "compute_distance", "align_to_mesh", "deviation_heatmap",
 ]

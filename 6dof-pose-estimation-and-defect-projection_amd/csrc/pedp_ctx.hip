@@ -286,6 +286,8 @@ void pedp_ctx_destroy(pedp_ctx_t c) {
     c->pose_io.release();
     c->metrics_ws.release();
     c->metrics_io.release();
+    c->closest_ws.release();
+    c->closest_io.release();
     c->stats_ws.release();
     c->stats_io.release();
     if (c->pinned) (void)hipHostFree(c->pinned);

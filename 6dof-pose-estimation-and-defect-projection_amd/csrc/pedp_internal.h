@@ -169,6 +169,9 @@ struct pedp_ctx_s {
     bool stage_busy = false;              // an upload's DMA may still be reading stage[0]
     pedp_scratch metrics_ws; // pose errors: the partial sums of one slab of poses (pedp_metrics.hip)
     pedp_scratch metrics_io; // pose errors: inputs and outputs of host-memory calls
+    pedp_scratch closest_ws; // closest points: the counter of tested point-triangle pairs (pedp_closest.hip)
+    pedp_scratch closest_io; // closest points: inputs and outputs of host-memory calls
+    int closest_mode = 0;    // pedp_closest_configure: 0 culled (the kernel by N), 1 exhaustive, 2 / 3 one culled kernel
 };
 
 // Triangle record: 12 floats (48 B, 16-B aligned so a wave fetches it with scalar

@@ -720,6 +720,51 @@ enum { PEDP_ERR_ADD = 0, PEDP_ERR_ADDS = 1 };
 int pedp_pose_errors(pedp_ctx_t ctx, const double *pts, int64_t N, const double *preds, int B, const double *gts, int G,
                      const double *sym, int S, int kind, int mem, double *out);
 
+/* ---------------------------------------------------------------- closest points of the mesh (compute_closest_points)
+ * The closest point of the mesh, as currently posed, to each of N points: RaycastingScene.compute_closest_points /
+ * compute_distance on the handle the ray caster uses.  The contract is DESIGN.md s4.16:
+ *   triangle     the record the ray caster tests, as stored: a = v0, ab = e1, ac = e2, float32 values promoted to float64;
+ *                the vertices are a, a + ab, a + ac.  Pad records and records whose m = e2 x e1 is all zero (degenerate: no
+ *                ray can hit them either) are skipped
+ *   arithmetic   float64, no contraction, every expression in the order written; dot(x, y) = (x0 y0 + x1 y1) + x2 y2.
+ *                With ap = p - a, bp = ap - ab, cp = ap - ac: d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp,
+ *                d6 = ac.cp, vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.  The first matching rule gives (v, w):
+ *                  1  d1 <= 0 && d2 <= 0                          (0, 0)
+ *                  2  d3 >= 0 && d4 <= d3                         (1, 0)
+ *                  3  vc <= 0 && d1 >= 0 && d3 <= 0               (d1 / (d1 - d3), 0)
+ *                  4  d6 >= 0 && d5 <= d6                         (0, 1)
+ *                  5  vb <= 0 && d2 >= 0 && d6 <= 0               (0, d2 / (d2 - d6))
+ *                  6  va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0     e = (d4 - d3) / ((d4 - d3) + (d5 - d6)), (1 - e, e)
+ *                  7  otherwise                                   den = 1 / ((va + vb) + vc), (vb den, vc den)
+ *                c = (a + ab v) + ac w componentwise, r = p - c, d^2 = (r0^2 + r1^2) + r2^2
+ *   selection    the minimum d^2 wins, ties go to the lowest triangle index; a NaN d^2 never wins.  dist = sqrt(d^2),
+ *                uv = (v, w), side = the sign (-1 / 0 / +1) of r . (ab x ac) with the cross product formed as
+ *                (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0): the side of the chosen face's normal, exact where the closest
+ *                point lies inside a face and a convention on edges and vertices
+ *   non-finite   a point with a NaN / infinite coordinate gets NaN in closest, dist and uv, 0xFFFFFFFF in prim_id and 0 in
+ *                side; the other points are not touched.  If no triangle is left (all skipped, F = 0, or every d^2 is
+ *                +inf or NaN): dist = +inf, prim_id = 0xFFFFFFFF, closest and uv NaN, side 0
+ *   determinism  a point's outputs depend on that point and the mesh's records alone: not on N, its position in the
+ *                batch, its neighbours, the handle's history or `exhaustive`; the culled search (the default) returns
+ *                the bits of the exhaustive one in every output
+ * pts N x 3; every output may be null.  All pointers are host or device memory by `mem`; PEDP_DEVICE only enqueues on the
+ * context's stream.  N = 0 does nothing; N > 2^24 is PEDP_ERR_BAD_ARG.  The call's workspace (one counter, and the
+ * staging of a host-memory call) is its own, so PEDP_DEVICE calls are allowed while a registration is pending on ctx
+ * (pedp_icp_begin); PEDP_HOST calls and pedp_closest_last_stats, which wait on the context's stream, are
+ * PEDP_ERR_BAD_ARG then.
+ * pedp_closest_configure: exhaustive = 1 tests every point against every triangle (the yardstick), 0 culls on the
+ * mesh's bounding spheres, with a wave per point up to 16384 points and a lane per point above; 2 and 3 are 0 with
+ * the lane-per-point or the wave-per-point kernel at every N (for tests and measurements: the bits are the same).  pedp_closest_last_stats: the point-triangle pairs the last call on ctx evaluated (finite
+ * points x unskipped triangles tested; it waits for the stream). */
+int pedp_closest_points(pedp_ctx_t ctx, pedp_mesh_t mesh, const double *pts, int64_t N, int mem, double *closest,
+                        double *dist, uint32_t *prim_id, double *uv, int8_t *side);
+int pedp_closest_configure(pedp_ctx_t ctx, int exhaustive);
+int pedp_closest_last_stats(pedp_ctx_t ctx, int64_t *pairs_tested);
+/* The unit normals (ab x ac) / |ab x ac| of the N triangles listed in prim_id (the cross product as above, the length as
+ * sqrt((x^2 + y^2) + z^2), one division per component), N x 3 float64; NaN for an id >= F and for a degenerate record.
+ * Memory, bounds and the pending-registration rule as pedp_closest_points. */
+int pedp_mesh_face_normals(pedp_ctx_t ctx, pedp_mesh_t mesh, const uint32_t *prim_id, int64_t N, int mem, double *normals);
+
 /* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
  * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
  * The contract is DESIGN.md s4.11.  With pos = mask > 0, truthy = mask.astype(bool) (for a float32 mask they differ on
