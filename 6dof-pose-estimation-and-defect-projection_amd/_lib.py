@@ -122,6 +122,7 @@ PROTOTYPES = {
     "pedp_icp_last_planned_passes": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_icp_last_serial_path": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_head_closed": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
+    "pedp_icp_last_certified": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
     "pedp_icp_end": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int32), C.c_void_p, C.c_void_p]),
@@ -790,6 +791,14 @@ def icp_last_head_closed(ctx, rebuilds=False):
     a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     check(load().pedp_icp_last_head_closed(ctx._h, C.byref(a), C.byref(b), C.byref(c)), "pedp_icp_last_head_closed")
     return (a.value, b.value, c.value) if rebuilds else a.value
+
+
+def icp_last_certified(ctx):
+    """(slots certified, slots that searched) of the last single icp(), summed over its passes
+    (pedp_icp_last_certified); PEDP_ICP_CERT=0 gives 0 certified."""
+    a, b = C.c_int64(0), C.c_int64(0)
+    check(load().pedp_icp_last_certified(ctx._h, C.byref(a), C.byref(b)), "pedp_icp_last_certified")
+    return a.value, b.value
 
 
 def icp_graph_captures(ctx):

@@ -109,7 +109,24 @@ struct IcpState {
     int n_wide;                // passes of this registration closed by the wide close (statistics: tests check it was in force)
     int n_head;                // passes of this registration closed at the head of the next launch (statistics, as n_wide)
     double T_init[16];         // the start transformation: slot 0 of the update history (arrives with the state, no copy of its own)
+    long long sum_cert, sum_searched;  // candidate slots whose search a certificate replaced / that searched, summed over passes (statistics)
 };
+
+// Certificates (fused pass, single registration): a chunk's count of certified and of searching slots shares the
+// free 32nd double of its partial, searching slots scaled by CERT_PACK (exact while a pass has fewer than 2^26 of either)
+constexpr double CERT_PACK = 67108864.0;
+// a slot that searches does so within KAPPA times the distance to last pass's neighbour: the margin its certificate lives on
+// (bench registration, one MI355X: 1.25 -- 0.531 ms, 1.5 -- 0.548, 2 -- 0.543, 3 -- 0.542; the certified share is the same)
+#ifndef PEDP_ICP_KAPPA
+#define PEDP_ICP_KAPPA 1.25f
+#endif
+// Rows a lane did not re-score are bounded from below through fp32 g: d^2 >= g + S - (CERT_SLACK eps + 4.8e-7 S).  eps bounds
+// every j-dependent error of one g (the selection window g_min + 2 eps rests on the same bound), 4.8e-7 S the
+// rounding of S.  The `maybe` test's generous 4 eps is a third of a typical gap between first and second neighbour at bench
+// size and left 42 % of the slots certifiable; 1 eps certifies all of them from pass 6 on.
+#ifndef PEDP_ICP_CERT_SLACK
+#define PEDP_ICP_CERT_SLACK 1.0f
+#endif
 
 __device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
 __device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }

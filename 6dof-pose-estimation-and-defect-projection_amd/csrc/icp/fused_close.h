@@ -47,7 +47,7 @@ namespace {
 constexpr int CH = NN_SB * 16;   // 128 scene points per chunk = slots per scene block
 constexpr int BK_W = 8;          // waves of a pass workgroup = sub-blocks of a chunk
 constexpr int BK_WCAP = BK_W * 64;  // mask words (64 tiles each) the fused pass handles: 524,288 target points
-constexpr int PSTRIDE = 32;      // doubles per chunk in the partials: packet, [29] wave-tiles swept, [30] exact searches
+constexpr int PSTRIDE = 32;      // doubles per chunk in the partials: packet, [29] wave-tiles swept, [30] exact searches, [31] certified slots (single registration)
 constexpr int LIVE_CAP = 8192;   // live chunks the finish kernel lists in LDS (1M scene points)
 constexpr int FIN_THREADS = 1024; // threads of icp_finish_kernel
 
@@ -234,6 +234,12 @@ struct PassArgs {
     // Head close: pass p stores its partial sums into copy p & 1 (part_stride doubles apart).  The head of launch L reads
     // pass L - 1's while workgroups of launch L that are through already store pass L's: not into the same buffer.
     size_t part_stride;
+    // Certificates (single registration closed in its launches; PEDP_ICP_CERT=0: off -- null).  One float per scene
+    // position, two copies by pass parity like Pk: a lower bound on the distance from the point as pass p left it to
+    // every target point other than the neighbour pass p found (0: none).  While the point's motion since leaves the
+    // old neighbour strictly inside the bound, the next pass takes it over without a search (fused_pass.h).
+    float *cert;
+    size_t cert_stride;         // floats between the two copies
 };
 
 template <typename T>
@@ -414,7 +420,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 // round: a range is 9 chunks at the bench frame's 281 live chunks; each entry's additions in the same order)
                 constexpr int BW = 10;
                 const int part = tid >> 4, k0 = (tid & 15) * 2, k1 = k0 + 1;
-                const bool has1 = k1 < PACKET + 2;
+                const bool has1 = k1 < PACKET + (LOCAL ? 3 : 2);  // (entry 31, the certificates' count: only a single registration's pass kernel writes it)
                 const int l_lo = part * lper < n_live ? part * lper : n_live, l_hi = l_lo + lper < n_live ? l_lo + lper : n_live;
                 double v0 = 0.0, v1 = 0.0;
                 for (int q = l_lo; q < l_hi; q += BW) {
@@ -538,6 +544,11 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 st->sum_tiles += (long long)L.pk[PACKET];
                 st->sum_fb += (long long)L.pk[PACKET + 1];
                 st->n_live = L.n_live_s;
+                if constexpr (LOCAL) {
+                    const long long searched = (long long)(L.pk[PACKET + 2] / CERT_PACK);  // (the division by 2^26 is exact)
+                    st->sum_searched += searched;
+                    st->sum_cert += (long long)(L.pk[PACKET + 2] - (double)searched * CERT_PACK);
+                }
             }
             L.do_rebuild = 0;
             const double *pk = L.pk;

@@ -123,6 +123,11 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     __shared__ float4 wnode[W][16], wsph0[64];
     __shared__ double rbs[16];  // rebuild passes: the pose so far (3 x 4), its norm bound, the reach
     __shared__ float wnode_r[W][16];
+    // certificates (single registration): per slot, the bound carried over (certified: the search is not needed),
+    // the neighbour it keeps and its squared distance
+    __shared__ float wcert[BATCH ? 1 : W][16];
+    __shared__ int wfj[BATCH ? 1 : W][16];
+    __shared__ double wfd[BATCH ? 1 : W][16];
     if (threadIdx.x == 0) {
         PassArgs t = a0;
         t.Pk = pose_ptr(a0.Pk, pose_off); t.Tprev = pose_ptr(a0.Tprev, pose_off); t.live = pose_ptr(a0.live, pose_off);
@@ -285,6 +290,9 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     if (threadIdx.x == 0 && pass < 32 && blockIdx.x < 512 && blockIdx.y == 0) g_icp_rt[pass][blockIdx.x][0] = rt_entry;
 #endif
     PEDP_RT(pass, 1);
+    // certificates are kept by a single registration that closes its passes itself, and never by a rebuild pass
+    // (its points are recomputed through the history; it writes certificates, the pass behind it reads them)
+    const bool certify = !BATCH && a0.cert != nullptr;
     const float inf = __uint_as_float(0x7F800000u);
     const double dinf = __longlong_as_double(0x7FF0000000000000ll);
     const double dnan = __longlong_as_double(0x7FF8000000000000ll);
@@ -400,10 +408,12 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
         // the half's candidates in ascending position take the half's slots 0.., the wave keeps those
         // whose rank falls into its quarter
         int nsl;  // real slots of this wave's sub-block
+        bool skip = false;  // wave-uniform: every one of them is certified
         {
-            bool cand = false, near = false;
-            int pi = -1;
-            double x = 0.0, y = 0.0, z = 0.0, dprev = dnan;
+            bool cand = false, near = false, certd = false;
+            int pi = -1, jprev = -1;
+            float c_new = 0.f;
+            double x = 0.0, y = 0.0, z = 0.0, dprev = dnan, d2prev = dnan;
             const int64_t k = (int64_t)chunk * CH + half * 64 + lane;
             const bool valid = k < a.N;
             if (valid) {
@@ -421,11 +431,36 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 } else {
                     x = Pk_in[3 * k]; y = Pk_in[3 * k + 1]; z = Pk_in[3 * k + 2];
                     const double ux = Tp_in[3 * k], uy = Tp_in[3 * k + 1], uz = Tp_in[3 * k + 2];
+                    float c_in = 0.f;
+                    if constexpr (!BATCH) {
+                        if (certify) {
+                            c_in = (as_global(a.cert) + (size_t)(pass & 1) * a.cert_stride)[k];
+                            jprev = as_global(a.idx_out)[pi];  // (rewritten in this pass by the slot's own wave only, behind this read)
+                        }
+                    }
+                    const double x0 = x, y0 = y, z0 = z;
                     xform(PEDP_ST.upd, x, y, z);
                     // Temporal coherence: last pass's neighbour is still a target point, so the new nearest
                     // neighbour is no farther than it is now.  NaN (no neighbour last pass) fails the
                     // comparison below and leaves the full radius.
-                    dprev = sqrt(dist2(x, y, z, ux, uy, uz));
+                    d2prev = dist2(x, y, z, ux, uy, uz);
+                    dprev = sqrt(d2prev);
+                    if constexpr (!BATCH) {
+                        if (certify) {
+                            // Certificate: every target point but last pass's neighbour was at least c_in from the point;
+                            // the point has moved by m, so they are at least c_in - m from it now (rounded down: the
+                            // factors cover the float64 roundings of dist2 and sqrt a thousand times over, the last one
+                            // the rounding to float32).  The old neighbour strictly inside that bound is the unique nearest
+                            // neighbour, and dist2 to it is the very number the selection would produce.  Non-finite
+                            // values are told by their exponent bits: they never certify.
+                            const double m = sqrt(dist2(x, y, z, x0, y0, z0));
+                            c_new = (float)(((double)c_in - m * (1.0 + 1e-12)) * (1.0 - 2e-7));
+                            const bool fin = (__double2hiint(d2prev) & 0x7FF00000) != 0x7FF00000 && (__double2hiint(m) & 0x7FF00000) != 0x7FF00000 &&
+                                             (__float_as_int(c_new) & 0x7F800000) != 0x7F800000;
+                            certd = fin && jprev >= 0 && c_new > 0.f && dprev * (1.0 + 1e-12) < (double)c_new;
+                            if (!certd) c_new = 0.f;
+                        }
+                    }
                 }
                 const double ex = fmax(fmax(a.lo[0] - x, x - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - y, y - a.hi[1]), 0.0),
                              ez = fmax(fmax(a.lo[2] - z, z - a.hi[2]), 0.0);
@@ -439,10 +474,21 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 if (lane == 0) misc[half] = mn != 0ull;
                 if (valid) {  // (a rebuild pass stores every visited chunk's coordinates; only the live ones are read again)
                     if (!cand) { as_global(a.idx_out)[pi] = -1; store_nan(&Tp_out[3 * k]); }
+                    if constexpr (!BATCH) {
+                        if (certify && !cand) (as_global(a.cert) + (size_t)((pass + 1) & 1) * a.cert_stride)[k] = 0.f;
+                    }
                     Pk_out[3 * k] = x; Pk_out[3 * k + 1] = y; Pk_out[3 * k + 2] = z;
                 }
             }
             const int sl = __builtin_popcountll(mc & lt) - 16 * q4;
+            if constexpr (!BATCH) {
+                // (a) a wave whose slots are all certified has nothing to search for
+                if (certify) {  // wave-uniform
+                    const bool mine = cand && sl >= 0 && sl < 16;
+                    skip = __builtin_amdgcn_ballot_w64(mine && !certd) == 0ull;
+                    if (mine) { wcert[wv][sl] = c_new; wfj[wv][sl] = jprev; wfd[wv][sl] = d2prev; }
+                }
+            }
             if (cand && sl >= 0 && sl < 16) {
                 const float sx = (float)(x - PEDP_CC(0, ccx_b)), sy = (float)(y - PEDP_CC(1, ccy_b)), sz = (float)(z - PEDP_CC(2, ccz_b));
                 // error bound of the fp32 surrogate against the float64 distance
@@ -455,7 +501,12 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 wp[wv][0][sl] = x; wp[wv][1][sl] = y; wp[wv][2][sl] = z;
                 wcs[wv][0][sl] = sx; wcs[wv][1][sl] = sy; wcs[wv][2][sl] = sz;
                 // search radius of the slot: the distance to last pass's neighbour, rounded up, at most r
-                const float rp = (float)dprev * 1.00001f + 1e-5f * s1 + 1e-6f;
+                float rp = (float)dprev * 1.00001f + 1e-5f * s1 + 1e-6f;
+                if constexpr (!BATCH) {
+                    // with certificates: KAPPA times that.  Any radius not below the true nearest distance gives the same
+                    // result; the wider one leaves a margin between the neighbour and the bound the certificate is made from
+                    if (certify) rp = PEDP_ICP_KAPPA * ((float)dprev * 1.00001f) + 1e-5f * s1 + 1e-6f;
+                }
                 const float r_search = BATCH ? r_search_b : unif(cur.r_search);
                 wrho[wv][sl] = rp < r_search ? rp : r_search;
             }
@@ -480,7 +531,10 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
         double wt[3] = {0.0, 0.0, 0.0}, wn[3] = {0.0, 0.0, 0.0};
         bool have_tn = false;
         int ntl_w = 0, nfb_w = 0;
-        if (nsl > 0) {  // wave-uniform
+        // (the slot's certificate for the next pass waits in wcert: a certified slot's is there already)
+        if (skip) {  // wave-uniform (nothing happens for nsl == 0)
+            if (real) { fj = wfj[wv][j]; fd = wfd[wv][j]; }  // neighbour and normal are fetched by index below
+        } else if (nsl > 0) {  // wave-uniform
             // ---- 2. what the target's spheres are tested against: a COVER of the sub-block's slots by bounding
             // spheres (centred fp32 coordinates), each with the largest search radius of its slots.  The slots'
             // binary tree -- pairs, quads, octets, all sixteen: the levels of a butterfly reduction -- is cut
@@ -660,7 +714,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             mg = fminf(mg, __shfl_xor(mg, 32, 64));
             const bool maybe = real && mg + Si <= unif(PEDP_ST.r2f) + 4.0f * e + 4.8e-7f * Si;  // else certainly farther than r
             const float win = mg + 2.0f * e;
-            double bd = dinf;
+            double bd = dinf, bd2 = dinf;  // (bd2: the second smallest exact d^2 this lane has seen, ties counted -- certificates only)
             int bj = 0x7FFFFFFF;
             auto eval_rows = [&](int tile, const double (&rw)[4][6], const int (&ri)[4]) {
                 const int64_t row0 = (int64_t)tile * 16 + 4 * g;
@@ -668,6 +722,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 for (int r = 0; r < 4; ++r) {
                     if (row0 + r < a.Nt) {
                         const double d = dist2(qx, qy, qz, rw[r][0], rw[r][1], rw[r][2]);
+                        if constexpr (!BATCH) bd2 = (d < bd || (d == bd && ri[r] < bj)) ? bd : (d < bd2 ? d : bd2);
                         if (d < bd || (d == bd && ri[r] < bj)) {
                             bd = d; bj = ri[r];
                             wt[0] = rw[r][0]; wt[1] = rw[r][1]; wt[2] = rw[r][2];
@@ -693,10 +748,16 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             // the slot's winner over its four lanes; the lane that holds it hands neighbour and normal over
             fd = bd;
             int fjj = bj;
+            double f2 = bd2;  // second smallest exact d^2 over the slot's four lanes
 #pragma unroll
             for (int off = 16; off <= 32; off <<= 1) {
                 const double od = __shfl_xor(fd, off, 64);
                 const int oj = __shfl_xor(fjj, off, 64);
+                if constexpr (!BATCH) {
+                    const double o2 = __shfl_xor(f2, off, 64);
+                    const double hi = fd < od ? od : fd, lo2 = f2 < o2 ? f2 : o2;
+                    f2 = hi < lo2 ? hi : lo2;
+                }
                 lexmin(fd, fjj, od, oj);
             }
             const bool found = maybe && fjj != 0x7FFFFFFF;
@@ -720,6 +781,30 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             {
                 const unsigned long long am = __builtin_amdgcn_ballot_w64(maybe && b3 <= win);
                 amb = (unsigned)((am | (am >> 16) | (am >> 32) | (am >> 48)) & 0xFFFFull);
+            }
+            if constexpr (!BATCH) {
+                if (certify) {
+                    // ---- the slot's certificate: a lower bound L on the distance to every target point but the winner.
+                    // Unlisted tiles: farther than rho (less the rounding allowance rho was given on top of the distance it
+                    // stands for).  Rows this lane re-scored: exact, f2 is the best of them behind the winner.  Its other rows:
+                    // g + S - (CERT_SLACK eps + 4.8e-7 S) bounds d^2 from below wherever d <= r1 (common.h), and the smallest g
+                    // among them is b1, b2 or b3 -- the first tile the lane did NOT re-score.  An ambiguous slot, one without
+                    // a neighbour and anything non-finite get 0.
+                    const bool rs1 = maybe && b1 <= win, rs2 = maybe && b2 <= win;
+                    float nr = !rs1 ? b1 : (!rs2 ? b2 : b3);
+                    nr = fminf(nr, __shfl_xor(nr, 16, 64));
+                    nr = fminf(nr, __shfl_xor(nr, 32, 64));
+                    const float s1c = fabsf(wcs[wv][0][j]) + fabsf(wcs[wv][1][j]) + fabsf(wcs[wv][2][j]);
+                    const double rho = (double)wrho[wv][j] * (1.0 - 2e-5) - (double)(1e-5f * s1c + 1e-6f) * 1.000001;
+                    const double Lg = ((double)nr + (double)Si) - (double)(PEDP_ICP_CERT_SLACK * e + 4.8e-7f * Si) * 1.000001;
+                    const double Le = f2 * (1.0 - 1e-12);
+                    double L2 = rho * rho;
+                    L2 = Lg < L2 ? Lg : L2;
+                    L2 = Le < L2 ? Le : L2;
+                    const bool ok = found && rho > 0.0 && (amb >> j & 1u) == 0u && (__float_as_int(nr) & 0x7FFFFFFF) <= 0x7F800000 && L2 > 0.0 &&
+                                    (__double2hiint(L2) & 0x7FF00000) != 0x7FF00000;
+                    if (g == 0 && real) wcert[wv][j] = ok ? (float)(sqrt(L2) * (1.0 - 2e-7)) : 0.f;  // (over phase 1's entry; this lane reads it back in phase 6)
+                }
             }
             if (tid == 0) PEDP_STAMP(1, blockIdx.x, 3);
             while (amb != 0u) {  // wave-uniform, rare
@@ -780,6 +865,9 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 if (g == 0) {
                     as_global(a.idx_out)[i] = jn;
                     if (jn < 0) store_nan(&Tp_out[3 * kp]);
+                    if constexpr (!BATCH) {
+                        if (certify) (as_global(a.cert) + (size_t)((pass + 1) & 1) * a.cert_stride)[kp] = jn >= 0 ? wcert[wv][j] : 0.f;
+                    }
                 }
                 if (jn >= 0) {
                     const double sx = wp[wv][0][j], sy = wp[wv][1][j], sz = wp[wv][2][j];
@@ -832,6 +920,9 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             // (entries 29, 30 of the tree are zero: the statistics replace them)
             __builtin_amdgcn_s_waitcnt(0xC07F);
             if (lane == 0) { accsh[wv][PACKET] = (double)ntl_w; accsh[wv][PACKET + 1] = (double)nfb_w; }
+            if constexpr (!BATCH) {
+                if (lane == 0) accsh[wv][PACKET + 2] = !certify ? 0.0 : (skip ? (double)nsl : CERT_PACK * (double)nsl);
+            }
         }
         PEDP_WV(4, __builtin_amdgcn_s_memtime());
         PEDP_WV(11, __builtin_amdgcn_s_memrealtime());

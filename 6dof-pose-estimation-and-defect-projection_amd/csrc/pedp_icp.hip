@@ -110,6 +110,7 @@ struct IcpWorkspace {
     // fused pass (qt == 1 inside a registration)
     bool fused;
     double *Pk, *hist, *cpart, *Tprev;
+    float *cert;   // certificates, two copies by pass parity (see PassArgs)
     unsigned *ticket;
     unsigned long long *live;
     int32_t *live_list;
@@ -156,7 +157,7 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
     // Every buffer is named once: take() lays it behind the ones before it, 256-byte aligned, and notes where its
     // pointer lives in w; the pointers are set once the executor's scratch buffer is known to be large enough.
     size_t off = 0;
-    constexpr int MAX_SLOTS = 32;  // (30 buffers below)
+    constexpr int MAX_SLOTS = 32;  // (31 buffers below)
     struct { size_t member, off; } slot[MAX_SLOTS];  // byte offset of the pointer inside w, of the buffer inside the block
     int n_slots = 0;
     auto take = [&](auto *&p, size_t bytes) {
@@ -196,6 +197,7 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
     if (fused) {
         take(w.Pk, sizeof(double) * 3 * (size_t)w.Ns_pad * 2);     // read from [pass & 1], written to the other: no wave
         take(w.Tprev, sizeof(double) * 3 * (size_t)w.Ns_pad * 2);  // ever reads what a faster wave of the same pass has rewritten
+        take(w.cert, sizeof(float) * (size_t)w.Ns_pad * (poses <= 1 ? 2 : 0));  // likewise (a batch keeps none)
         take(w.hist, sizeof(double) * 16 * (size_t)iter_capacity(max_iter));
         take(w.cpart, sizeof(double) * PSTRIDE * (size_t)w.blocks_cap * 2);  // two copies by pass parity (head close; else the first)
         // the ticket and the sixteen sign-off counters, a line each, and the live masks right behind them: one span
@@ -308,6 +310,13 @@ inline bool head_close() {
     static const bool m = env_flag("PEDP_ICP_HEAD_CLOSE", true);
     return m;
 }
+// PEDP_ICP_CERT=0: every candidate slot searches in every pass again, within the distance to last pass's neighbour.
+// (Default: a single registration that closes its passes itself keeps a certificate per scene point and skips the search
+// of a wave whose slots' neighbours are proven unchanged; a slot that searches does so within KAPPA times that distance.)
+inline bool icp_certificates() {
+    static const bool m = env_flag("PEDP_ICP_CERT", true);
+    return m;
+}
 
 // Enqueue one correspondence pass (transform, sweep, fallback).  mode as in
 // icp_transform_pack_kernel.
@@ -400,6 +409,8 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pe
     // head close: the launch index, and one workgroup more than the chunks can fill (the service workgroup)
     pa.head = head_launch >= 0 ? 1 : 0; pa.launch = pa.head ? head_launch : 0;
     pa.part_stride = (size_t)PSTRIDE * (size_t)w.blocks_cap;
+    // (batches, passes closed by icp_finish_kernel and the exchange step never certify)
+    pa.cert = poses <= 1 && pa.fuse && icp_certificates() ? w.cert : nullptr; pa.cert_stride = (size_t)w.Ns_pad;
     pa.visit = plan ? w.visit : nullptr; pa.dur = plan ? w.dur : nullptr; pa.visit_cap = w.visit_cap; pa.n_cu = c->num_cus;
     // grid-stride loop over the live chunks: any grid is correct; two workgroups per CU are resident
     int64_t g = w.n_chunks;
@@ -917,6 +928,8 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     x->icp_last_planned = hp->n_planned;
     x->icp_last_wide = hp->n_wide;
     x->icp_last_head = hp->n_head;
+    x->icp_last_cert = hp->sum_cert;
+    x->icp_last_searched = hp->sum_searched;
     x->icp_last_rebuilds = hp->n_rebuilds;
     x->icp_last_bracket = (copy_bracket() ? 0 : 1) + (job.dev_result ? 2 : 0);
     x->icp_last_nt = job.Nt;
@@ -1423,6 +1436,13 @@ int pedp_icp_last_serial_path(pedp_ctx_t c, int64_t *wide_closes, int64_t *brack
     PEDP_REQUIRE(c && wide_closes && bracket, "pedp_icp_last_serial_path: null argument");
     *wide_closes = c->icp_last_wide;
     *bracket = c->icp_last_bracket;
+    return PEDP_OK;
+}
+
+int pedp_icp_last_certified(pedp_ctx_t c, int64_t *slots, int64_t *searched_slots) {
+    PEDP_REQUIRE(c && slots, "pedp_icp_last_certified: null argument");
+    *slots = c->icp_last_cert;
+    if (searched_slots) *searched_slots = c->icp_last_searched;
     return PEDP_OK;
 }
 

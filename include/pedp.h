@@ -532,6 +532,15 @@ int pedp_icp_last_serial_path(pedp_ctx_t ctx, int64_t *wide_closes, int64_t *bra
  * Results do not change in any bit (tests/test_icp_head_close_gpu.py compares). */
 int pedp_icp_last_head_closed(pedp_ctx_t ctx, int64_t *head_closed, int64_t *rebuilds, int64_t *launches);
 
+/* Candidate slots of the last single registration collected on `ctx`, summed over its passes, whose nearest-neighbour
+ * search a certificate replaced (`slots`), and those that searched (`searched_slots`, may be null).  A pass leaves, per
+ * scene point, a lower bound on the distance to every target point other than the neighbour it found; while the point's
+ * motion since keeps that neighbour strictly inside the bound it is still the unique nearest neighbour, and a wave whose
+ * slots are all proven so skips culling, sweep and selection.  Rebuild passes, batches, sharded registrations and
+ * PEDP_ICP_CERT=0 certify nothing: 0 slots (and, for all but the first, 0 searched slots: they are not counted there).
+ * Results do not change in any bit (tests/test_icp_certificate_gpu.py compares). */
+int pedp_icp_last_certified(pedp_ctx_t ctx, int64_t *slots, int64_t *searched_slots);
+
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
  * g[i * n_tgt + j] = |t'_j|^2 - 2 s'_i . t'_j exactly as the sweep's v_mfma_f32_16x16x32_bf16 produces it (same operand packing). */
