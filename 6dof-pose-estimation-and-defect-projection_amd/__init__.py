@@ -13,11 +13,13 @@ Layout
   registration.py  registration_icp, estimation/criteria classes, get_rotation_matrix_from_xyz
   icp_refine.py    host mirror of src/pose_estimation.py's refinement functions
   ray_projection.py host mirror of src/defect_projection.py's projection functions
+  defect_map.py    DefectMap: per-face accumulation of projected heat maps on the model, and the defect regions
   compat.py        `from pedp_hip.compat import *` in place of `from src import *` (run.py:3)
   dist.py          one-process-per-GPU sharding over torch.distributed (RCCL)
   synth.py         deterministic synthetic inputs of the benchmark configurations
 """
 from . import _lib
 from ._lib import PedpError, LIB_PATH
+from .defect_map import DefectMap
 
-__all__ = ["_lib", "PedpError", "LIB_PATH"]
+__all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap"]

@@ -163,6 +163,15 @@ PROTOTYPES = {
     "pedp_mesh_face_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "pedp_closest_configure": (C.c_int, [C.c_void_p, C.c_int]),
     "pedp_closest_last_stats": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
+    "pedp_defect_map_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_void_p)]),
+    "pedp_defect_map_destroy": (C.c_int, [C.c_void_p]),
+    "pedp_defect_map_size": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
+    "pedp_defect_map_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "pedp_defect_map_clear": (C.c_int, [C.c_void_p]),
+    "pedp_defect_map_faces": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_defect_map_stats": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
+    "pedp_defect_map_regions": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                          _P(C.c_int64)]),
     "pedp_mask_depth_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),

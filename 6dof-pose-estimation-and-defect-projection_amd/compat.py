@@ -10,7 +10,8 @@ loops (`FoundationPose`, `PoseRefinePredictor`, `ScorePredictor`, estimator.py),
 checkpoint loaders (`RefineNet`, `ScoreNetMultiPair`, `load_refiner`, `load_scorer`, networks.py), and the evaluation
 metrics (`add_err`, `adds_err`, their batch forms, `compute_auc_sklearn`, `symmetry_tfs_from_info`, metrics.py), and the
 exact cloud-to-mesh distance with the deviation heat map (`closest_points`, `compute_distance`, `align_to_mesh`,
-`deviation_heatmap`, surface_distance.py); the Dash app, sensor
+`deviation_heatmap`, surface_distance.py), and the defect map on the model in the place of run.py:196-201's list of
+hit clouds (`DefectMap`, defect_map.py); the Dash app, sensor
 code and the networks' weights stay the reference's own.
 """
 import numpy as np
@@ -57,6 +58,7 @@ from .estimator import (FoundationPose, PoseRefinePredictor, ScorePredictor, com
 from .metrics import (add_err, add_err_batch, adds_err, adds_err_batch, compute_auc_sklearn,  # noqa: E402,F401  (Utils.py:232-266, :806-834)
                       symmetry_tfs_from_info)
 from .surface_distance import align_to_mesh, closest_points, compute_distance, deviation_heatmap  # noqa: E402,F401  (run.py:64's heat map)
+from .defect_map import DefectMap  # noqa: E402,F401  (run.py:61, :119, :196-201: the history of hits, kept per face)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
 
@@ -91,4 +93,5 @@ __all__ = [
     "RefineNet", "ScoreNetMultiPair", "load_refiner", "load_scorer",
     "add_err", "adds_err", "add_err_batch", "adds_err_batch", "compute_auc_sklearn", "symmetry_tfs_from_info",
     "closest_points", "compute_distance", "align_to_mesh", "deviation_heatmap",
+    "DefectMap",
 ]

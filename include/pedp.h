@@ -774,6 +774,82 @@ int pedp_closest_last_stats(pedp_ctx_t ctx, int64_t *pairs_tested);
  * Memory, bounds and the pending-registration rule as pedp_closest_points. */
 int pedp_mesh_face_normals(pedp_ctx_t ctx, pedp_mesh_t mesh, const uint32_t *prim_id, int64_t N, int mem, double *normals);
 
+/* ---------------------------------------------------------------- the defect map: per-face accumulation and regions
+ * What the projected heat maps of many frames say about the CAD model itself: per face the peak intensity, the hits and
+ * the frames that saw it, and the connected regions of the marked faces with their sizes.  It stands in the place of
+ * run.py:61, :119, :196-201, which keep a growing list of hit clouds and move every one of them at every detection:
+ * triangle indices keep the input's order in every mesh handle whatever the pose, so a map kept per face in the MODEL
+ * frame is a constant-size object that never needs a transform.  The contract is DESIGN.md s4.17.
+ *
+ * pedp_defect_map_create: verts V x 3 float64 and tris F x 3 on the host, the model frame.  A mesh handle keeps neither,
+ * so the map takes them itself; it is tied to a mesh only by the shared triangle order.  An index >= V is
+ * PEDP_ERR_BAD_ARG; F = 0 is allowed; F > 2^28 is PEDP_ERR_BAD_ARG.  Built on the device and kept resident, float64, no
+ * contraction, every expression in the order written (a, b, c: the face's corners):
+ *   area[f]      0.5 * sqrt((n0^2 + n1^2) + n2^2), n = ab x ac formed as (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0),
+ *                ab = b - a, ac = c - a
+ *   centroid[f]  ((a + b) + c) / 3 componentwise
+ *   box[f]       minimum and maximum of the corners per axis, -0 below +0; a NaN coordinate takes no part
+ *   weld         w[v] = the lowest index of a vertex whose three coordinates compare equal with == (so -0 equals +0, and a
+ *                vertex with a NaN is welded to nothing): OBJ files duplicate vertices along UV seams, and a defect
+ *                must not fall apart there
+ *   adjacency    two faces are neighbours iff they share an unordered edge {w_i, w_j} with w_i != w_j; any number of
+ *                faces may share an edge and are then all neighbours of each other; a face's edge with w_i == w_j is
+ *                no edge
+ * The call returns after the build; it waits on the context's stream, so it is PEDP_ERR_BAD_ARG while a registration is
+ * pending on ctx (pedp_icp_begin).
+ *
+ * pedp_defect_map_add is one OBSERVATION (one frame's hits): for every row with prim_id < F and a non-NaN intensity
+ *   peak[f] = max(peak[f], intensity) with +0 above -0;  hits[f] += 1 (64-bit);  frames[f] += 1 ONCE per observation
+ * whatever the number of rows on f.  Rows with 0xFFFFFFFF (a miss), any other id >= F or a NaN intensity are ignored and
+ * counted.  n = 0 still counts as an observation.  PEDP_DEVICE only enqueues on the context's stream and is allowed
+ * while a registration is pending on the context (pedp_icp_begin); PEDP_HOST is PEDP_ERR_BAD_ARG then.  Runs of equal
+ * ids in neighbouring rows (hits arrive in pixel order) are combined inside a wave before the atomics.  There is no
+ * floating-point atomic: the maximum is an integer atomic max on an order-preserving 64-bit key, the counts are integer
+ * atomics.  The per-face state after a sequence of calls is a function of the multiset of rows of each observation
+ * alone: not of the rows' order, of how an observation's rows sit in memory, or of the handle's history before the
+ * last pedp_defect_map_clear (which forgets everything, the observation count included).
+ * pedp_defect_map_faces: F values each, every pointer nullable, host or device memory by `mem`; a face never hit reads
+ * peak 0, hits 0, frames 0 (PEDP_HOST and a pending registration: as for add).  pedp_defect_map_stats: observations, rows taken and rows ignored since the last clear (it
+ * waits on the stream: PEDP_ERR_BAD_ARG while a registration is pending).
+ *
+ * pedp_defect_map_regions:
+ *   1  a face is MARKED iff hits > 0 && peak > threshold && frames >= min_frames (strictly above the threshold, like
+ *      heatmap_to_points)
+ *   2  the marking is grown `grow` times (0 <= grow <= 64): a face is marked after a round if it or one of its
+ *      neighbours was marked before the round.  This bridges the faces that lie BETWEEN two pixels' rays on a mesh
+ *      whose triangles are smaller than a pixel's footprint
+ *   3  regions are the connected components of the marked faces under the adjacency, numbered 0 ... R - 1 by their
+ *      lowest face index
+ * labels (F x int32, nullable): the region of each face or -1.  table (nullable with capacity 0): one row per region.
+ * If R > capacity nothing is written to table, n_regions still reports R and the call returns PEDP_ERR_BAD_ARG, like
+ * pedp_project_heatmap; capacity = F always suffices.  n_regions is a host scalar, so the call waits on the stream, and
+ * like pedp_closest_last_stats it is PEDP_ERR_BAD_ARG while a registration is pending on the context.  The workspace is
+ * the map's own (its two sorts use the context's pooled sort buffers, like every sort of the library): never the pinned
+ * result block, never the ICP workspace.  area and moment are floating-point sums formed in a fixed order: the same bits on
+ * every call for the same per-face state. */
+typedef struct pedp_defect_map_s *pedp_defect_map_t;
+typedef struct pedp_defect_region {
+    int32_t first_face;    /* the region's lowest face index */
+    int32_t n_faces;       /* faces after the growth */
+    int32_t n_seed_faces;  /* faces marked before the growth */
+    int32_t max_frames;    /* largest `frames` among the faces */
+    int64_t hits;          /* sum of the faces' hits */
+    double area;           /* sum of the faces' areas */
+    double centroid[3];    /* moment / area; NaN for a region of zero area */
+    double moment[3];      /* sum of area * centroid over the faces: the centroid's numerators */
+    double peak;           /* maximum over its faces with hits */
+    double lo[3], hi[3];   /* the box of its faces' vertices */
+} pedp_defect_region;
+int pedp_defect_map_create(pedp_ctx_t ctx, const double *verts, int64_t V, const uint32_t *tris, int64_t F, pedp_defect_map_t *out);
+int pedp_defect_map_destroy(pedp_defect_map_t map);
+int pedp_defect_map_size(pedp_defect_map_t map, int64_t *V, int64_t *F);
+int pedp_defect_map_add(pedp_defect_map_t map, const uint32_t *prim_id, const double *intensity, int64_t n, int mem);
+int pedp_defect_map_clear(pedp_defect_map_t map);
+int pedp_defect_map_faces(pedp_defect_map_t map, int mem, double *peak, int64_t *hits, int32_t *frames);
+int pedp_defect_map_stats(pedp_defect_map_t map, int64_t *observations, int64_t *rows_added, int64_t *rows_ignored);
+int pedp_defect_map_regions(pedp_defect_map_t map, double threshold, int32_t min_frames, int32_t grow, int mem, int32_t *labels,
+                            int64_t capacity, pedp_defect_region *table, int64_t *n_regions);
+
 /* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
  * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
  * The contract is DESIGN.md s4.11.  With pos = mask > 0, truthy = mask.astype(bool) (for a float32 mask they differ on
