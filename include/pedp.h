@@ -417,10 +417,19 @@ int pedp_icp(pedp_ctx_t ctx, pedp_cloud_t source, pedp_cloud_t target,
  * once (passes after convergence are no-ops on the device: the host does not look at the criteria in between);
  * pedp_icp_end waits for them and hands the result over -- the same bits as pedp_icp's.  What the host does in between
  * (enqueueing a frame's ray stage on ANOTHER context, bench.py's step) overlaps with the registration instead of waiting in
- * front of it.  Between the two calls this context must not be used for anything else (its workspace and its page-locked
- * state block belong to the pending registration): a second pedp_icp_begin, pedp_icp, pedp_icp_batched(_ex), pedp_nn,
- * pedp_icp_configure or pedp_ransac_hypotheses returns PEDP_ERR_BAD_ARG; destroying the context or either cloud with a registration pending is an error of the caller.  want_trace:
- * pedp_icp_end's `trace` may be non-null.  The reference has no counterpart (registration_icp is one blocking call,
+ * front of it.  Between the two calls the registration's workspace, the first 8,192 bytes of the context's page-locked block
+ * and the two clouds belong to the pending registration.  Every call that shares them is refused: a second pedp_icp_begin,
+ * pedp_icp, pedp_icp_batched(_ex), pedp_nn, pedp_icp_configure, pedp_ransac_hypotheses, pedp_cloud_set_target_order and
+ * pedp_debug_target_pack return
+ * PEDP_ERR_BAD_ARG, and so do the calls that say so at their own declaration (the closest-point, defect-map and pose-error
+ * calls in PEDP_HOST mode and their statistics, which would only wait for the stream).  Every other call of this header
+ * keeps to state of its own that the stream orders -- the ray caster, the projection, the depth entry and filters, the
+ * point-cloud operations and pedp_preprocess_source, pedp_cloud_create(_device), the renderer, crops, pose arithmetic,
+ * statistics and the network kernels -- and may be used on the context in between: it gives the bits it gives on a fresh
+ * context, and the registration ends with pedp_icp's bits (tests/test_call_history_gpu.py runs each of them in that
+ * window; DESIGN.md s4.18 lists what each touches).  A PEDP_HOST call among them returns after the registration's passes,
+ * so only PEDP_DEVICE calls overlap with it.  Destroying the context or either cloud with a registration pending is an
+ * error of the caller.  want_trace: pedp_icp_end's `trace` may be non-null.  The reference has no counterpart (registration_icp is one blocking call,
  * src/pose_estimation.py:447-453). */
 int pedp_icp_begin(pedp_ctx_t ctx, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *params,
                    const double init[16], int want_trace);
