@@ -123,6 +123,7 @@ PROTOTYPES = {
     "pedp_icp_last_serial_path": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_head_closed": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_certified": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
+    "pedp_icp_last_steady": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
     "pedp_icp_end": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int32), C.c_void_p, C.c_void_p]),
@@ -807,6 +808,14 @@ def icp_last_certified(ctx):
     (pedp_icp_last_certified); PEDP_ICP_CERT=0 gives 0 certified."""
     a, b = C.c_int64(0), C.c_int64(0)
     check(load().pedp_icp_last_certified(ctx._h, C.byref(a), C.byref(b)), "pedp_icp_last_certified")
+    return a.value, b.value
+
+
+def icp_last_steady(ctx):
+    """(passes of the last single icp() that ran inside a steady launch, hand-backs to the generic pass kernel)
+    (pedp_icp_last_steady); PEDP_ICP_STEADY=0 gives (0, 0)."""
+    a, b = C.c_int64(0), C.c_int64(0)
+    check(load().pedp_icp_last_steady(ctx._h, C.byref(a), C.byref(b)), "pedp_icp_last_steady")
     return a.value, b.value
 
 

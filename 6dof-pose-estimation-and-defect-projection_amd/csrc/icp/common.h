@@ -108,6 +108,8 @@ struct IcpState {
     int nonce;                 // of this registration (<< 16 in the tags of the visit plan: entries of an earlier registration never match)
     int n_wide;                // passes of this registration closed by the wide close (statistics: tests check it was in force)
     int n_head;                // passes of this registration closed at the head of the next launch (statistics, as n_wide)
+    int n_steady;              // passes of this registration run inside a steady launch (steady_pass.h; statistics)
+    int reserved_;
     double T_init[16];         // the start transformation: slot 0 of the update history (arrives with the state, no copy of its own)
     long long sum_cert, sum_searched;  // candidate slots whose search a certificate replaced / that searched, summed over passes (statistics)
 };

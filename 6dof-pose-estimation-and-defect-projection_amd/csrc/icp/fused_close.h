@@ -324,13 +324,15 @@ __device__ __forceinline__ unsigned long long load_live(unsigned long long *p) {
 // MODE 0: `st` is the state in memory.  MODE 1: `st` is the workgroup's copy of the state in LDS; the caller writes it
 // out (and the final state to f.down's block) behind the body.  MODE 2: the head close -- as 1, and every workgroup of
 // the launch runs it: nothing is written to memory here (the service workgroup does that from LDS), no live list, no
-// sign-off poll, no live-mask upkeep.
+// sign-off poll, no live-mask upkeep.  MODE 3: the head close inside a launch that goes on (steady_pass.h) -- as 2, but the
+// partial sums were stored in THIS launch: they are read coherently, entry by entry.
 // the close's stamps (diagnostic build): of a head close, which every workgroup runs, workgroup 0's only
 #define PEDP_STAMP_CLOSE(unit, slot) do { if (!HEAD || blockIdx.x == 0) PEDP_STAMP(2, unit, slot); } while (0)
 template <int NT, int LCAP, bool COHERENT, int MODE = 0>
 __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &f, FinishLds<NT, LCAP> &L, const int tid) {
-    constexpr bool LOCAL = MODE != 0, HEAD = MODE == 2;
-    static_assert(!HEAD || !COHERENT, "the head close reads what the launch before stored");
+    constexpr bool LOCAL = MODE != 0, HEAD = MODE >= 2;
+    static_assert(MODE != 2 || !COHERENT, "the head close reads what the launch before stored");
+    static_assert(MODE != 3 || COHERENT, "the close inside a steady launch reads what that launch stored");
     // (a state in LDS comes back in vector registers: the parameters, the same in every lane, are made scalar again)
     auto uni = [](double v) { return LOCAL ? bcast0(v) : v; };
     const int pass = f.known ? f.k_pass : st->pass, max_iter = LOCAL ? __builtin_amdgcn_readfirstlane(st->max_iter) : st->max_iter;
@@ -430,7 +432,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                     for (int u = 0; u < BW; ++u) at[u] = position(q + u < l_hi ? q + u : l_hi - 1);
 #pragma unroll
                     for (int u = 0; u < BW; ++u) {
-                        if constexpr (HEAD) {  // k0 is even and PSTRIDE is 32: the two entries are one aligned 16-byte load
+                        if constexpr (HEAD && !COHERENT) {  // k0 is even and PSTRIDE is 32: the two entries are one aligned 16-byte load
                             typedef double v2d __attribute__((ext_vector_type(2)));
                             const v2d t = *(const PEDP_GLOBAL v2d *)(uintptr_t)&f.partials[(size_t)at[u] * PSTRIDE + k0];
                             x0[u] = t[0];

@@ -1,0 +1,496 @@
+// ICP, steady passes: consecutive non-rebuild passes of ONE fused registration in one launch (icp_steady_kernel).
+//
+// Once every slot of a pass is certified (fused_pass.h), a pass is a transform, a certificate check, a fetch by index
+// and the sums: a few microseconds of work between launch boundaries that cost several times as much.  This kernel
+// keeps a resident grid through such passes and replaces the launch boundary by a bounded device-wide hand-over:
+//
+//   per pass p   every workgroup with a rank runs phases 1 and 6 of its chunks (the float64 sequences of
+//                icp_pass_kernel, same wave / half / quarter / slot layout, same sum tree), stores its partial sums
+//                write-through (sc1) into copy p & 1, drains its stores, meets at a barrier; one lane adds 1 to one of
+//                sixteen counters (a line each; the sign-off counters of the generic kernel, cumulative, base in the
+//                state); lanes 0-15 poll them with sc1 loads and s_sleep until all have arrived -- at most
+//                STEADY_SPIN_CAP looks, then the registration fails loudly (done = -1).  No fence.
+//   the close    EVERY workgroup then closes pass p itself: icp_finish_body in its coherent head mode (MODE 3) -- the
+//                head close's sequence on sc1 loads of the partials -- and goes on with pass p + 1 from the state in
+//                its LDS.  One workgroup (the last rank: it has the fewest chunks) also writes what a head close leaves
+//                behind: the row of the trace, the history slot, the packet.
+//   two copies   of the partial sums suffice: a workgroup stores pass p + 2 only after all have arrived for p + 1,
+//                which they do after reading p.
+//
+// A slot that is not certified runs the exact search of the ambiguous-slot fallback (word spheres, tile spheres, the
+// float64 scan of the near tiles, lexmin) within its own radius rho, the whole wave per slot, and leaves the
+// certificate min(rho^2, e2) of DESIGN 4.2 (e2: the second smallest exact d^2 the scan saw, ties counted).  There is
+// no cover, no sweep and no selection here.
+//
+// A chunk is worked on by the same workgroup in every pass of a launch, so what one pass stores of it (points,
+// neighbours, certificates, indices: plain stores, written through this CU's L1 to its XCD's L2) the next pass of the
+// same workgroup reads back with sc1 loads -- past the L1, which is never refreshed inside a launch.  The workgroup's
+// first chunk is also kept in LDS from its first pass on and read from there; the global buffers are written in every
+// pass all the same, so there is nothing to write back at exit.
+//
+// The launch ends when the registration does (final state into the page-locked block, as the head close does), or hands
+// back to the generic kernel: when a close asks for a rebuild, or when more than 1/8 of a pass's candidate slots
+// searched.  The state then lies in the slot its pass names exactly as an in-launch close leaves it, the other slot
+// names no pass, and the page-locked block carries a copy marked done = STEADY_HANDBACK for the host.
+//
+// The state's slots are rewritten only after a device-wide hand-over that counts EVERY workgroup of the grid once
+// (those without a rank sign off when they have read the state and leave): nobody that starts late reads a slot while
+// it changes.
+//
+// Residency: 512 threads, 128 VGPRs (launch bounds: four waves per SIMD), 36.8 KB of LDS -- two workgroups per CU by
+// registers and waves, four by LDS -- and the host sizes the grid from hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs,
+// at most 2 x CUs: every workgroup of the grid is resident at once, however many of them have a rank.
+#pragma once
+#include "fused_pass.h"
+
+namespace {
+
+constexpr unsigned STEADY_SPIN_CAP = 1u << 21;  // looks at the counters before a hand-over gives up
+constexpr int STEADY_HANDBACK = 2;              // `done` of the page-locked copy of a state that was handed back
+
+__device__ __forceinline__ float load_sc1(const float *p) {
+    return __uint_as_float(__hip_atomic_load((g_u32 *)(uintptr_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// a0.launch: the first pass this launch may run (what a generic launch of that index would run)
+__global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0, const PassArgs a0) {
+    constexpr int W = BK_W;
+    static_assert(W == 8 && CH == 128, "a chunk is two halves of four 16-slot sub-blocks");
+    __shared__ IcpState cur;
+    typedef double __attribute__((may_alias)) state_word;
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    constexpr int SWORDS = (int)(sizeof(IcpState) / sizeof(double));
+    __shared__ PassArgs sa;
+    __shared__ FinishLds<W * 64, 1> fin;
+    __shared__ double wp[W][3][16], accsh[W][PSTRIDE], wfd[W][16];
+    __shared__ float wcs[W][3][16], wrho[W][16], wcert[W][16];
+    __shared__ int wpi[W][16], wkk[W][16], wfj[W][16], misc[4];
+    __shared__ float4 wsph0[64];
+    // The workgroup's first chunk stays resident from its first pass in this launch on, by position in the chunk: the
+    // point (two copies by pass parity, like Pk: the four waves of a half read a pass's input while quarter 0 writes
+    // its output), last pass's neighbour with its normal, the certificate, the neighbour's and the point's index.  Of
+    // the last four a wave uses only its own slots' entries, which it alone rewrites, behind its own reads.
+    __shared__ double rP[2][3][CH], rT[3][CH], rN[3][CH];
+    __shared__ float rc[CH];
+    __shared__ int rj[CH], rpi[CH];
+    if (threadIdx.x == 0) { sa = a0; misc[0] = 0; }
+    const PassArgs &a = sa;
+    const int G = (int)gridDim.x;
+    const int chunk_first = a0.live_list[blockIdx.x < (unsigned)a0.n_chunks ? blockIdx.x : 0];
+    v4i vis = {0, 0, 0, 0};
+    if (a0.visit && blockIdx.x < (unsigned)a0.visit_cap) vis = ((const v4i *)a0.visit)[(size_t)(a0.launch & 1) * a0.visit_cap + blockIdx.x];
+    // (the same entry in every lane: kept in scalar registers through the launch)
+    for (int k = 0; k < 4; ++k) vis[k] = __builtin_amdgcn_readfirstlane(vis[k]);
+    if (threadIdx.x < 64) wsph0[threadIdx.x] = a0.word_sph[(int)threadIdx.x < a0.n_words ? threadIdx.x : 0];
+    // which slot holds what: the head of a generic launch of this index decides the same way (fused_pass.h)
+    bool need_close = false;
+    {
+        IcpState *sA = st0 + (a0.launch & 1), *sB = st0 + ((a0.launch + 1) & 1);
+        double wA = 0.0, wB = 0.0;
+        if (threadIdx.x < SWORDS) {
+            wA = ((const state_word *)sA)[threadIdx.x];
+            wB = ((const state_word *)sB)[threadIdx.x];
+        }
+        if (a0.launch > 0 && sB->pass == a0.launch - 1 && sB->done == 0 && sB->rebuild == 0 && sB->pass < sB->max_iter) need_close = true;
+        else if (sA->pass != a0.launch || sA->done) return;  // the registration is over (every workgroup sees that: nobody writes)
+        if (threadIdx.x < SWORDS) ((state_word *)&cur)[threadIdx.x] = need_close ? wB : wA;
+        __syncthreads();  // the state, the argument block and the word spheres are in LDS
+    }
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+    auto unif = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    const int n_live = uni(cur.n_live), max_iter = uni(cur.max_iter);
+    const unsigned base0 = (unsigned)uni((int)cur.idle_base);
+    int n_part = n_live < G ? n_live : G;
+    n_part = n_part < 1 ? 1 : n_part;  // (no live chunk at all: workgroup 0 still closes the passes)
+    g_u32 *const counters = (g_u32 *)(uintptr_t)(a0.ticket + 32);
+    if ((int)blockIdx.x >= n_part) {  // no rank: this workgroup has read the state -- it signs off and leaves
+        if (threadIdx.x == 0) __hip_atomic_fetch_add(counters + 32 * (blockIdx.x & 15), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const bool service = (int)blockIdx.x == n_part - 1;
+    // the visit plan of the launch's first pass, where there is one, holds for all of them (one chunk per workgroup)
+    const bool planned = a0.visit != nullptr && n_live <= G && vis[2] == uni(cur.nonce) + a0.launch + 1 && vis[3] == n_live;
+    const double dinf = __longlong_as_double(0x7FF0000000000000ll);
+    const double dnan = __longlong_as_double(0x7FF8000000000000ll);
+    auto store_nan = [](PEDP_GLOBAL double *p) {  // (see icp_pass_kernel)
+        int z = 0;
+        asm volatile("" : "+v"(z));
+        typedef int v2i_ __attribute__((ext_vector_type(2)));
+        const v2i_ w = {z, 0x7FF80000 | z};
+        *(PEDP_GLOBAL v2i_ *)p = w;
+    };
+    auto lds_nan = [](double *p) {  // "no neighbour", as two integer words (this file is built with -fno-honor-nans)
+        int z = 0;
+        asm volatile("" : "+v"(z));
+        ((int *)p)[0] = z;
+        ((int *)p)[1] = 0x7FF80000 | z;
+    };
+    // The device-wide hand-over.  Arrivals so far in this launch: the first counts the whole grid, the others the ranks.
+    unsigned arrivals = 0u;
+    int handovers = 0;
+    // (diagnostic build, g_icp_rt of pass p: [0] chunks begun, [2] chunks done, [3] arrived, [4] all seen to have arrived; the
+    // close of pass p - 1 in front of it: [5] partial sums' loads back, [6] sums done, [7] U published)
+    auto hand_over = [&](int p_stamp) -> bool {
+        (void)p_stamp;
+        PEDP_RT(p_stamp, 2);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its stores have left
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_fetch_add(counters + 32 * (blockIdx.x & 15), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        PEDP_RT(p_stamp, 3);
+        arrivals += handovers == 0 ? (unsigned)G : (unsigned)n_part;
+        ++handovers;
+        if (threadIdx.x < 64) {
+            for (unsigned spins = 0;; ++spins) {
+                unsigned c = threadIdx.x < 16 ? __hip_atomic_load(counters + 32 * threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+#pragma unroll
+                for (int off = 8; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+                if (__shfl(c, 0, 64) - base0 >= arrivals) break;
+                if (spins > STEADY_SPIN_CAP) {  // bounded: a lost workgroup must not hang the device
+                    if (threadIdx.x == 0) misc[0] = 1;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(8);
+            }
+        }
+        PEDP_RT(p_stamp, 4);
+        __syncthreads();
+        if (misc[0] != 0) {  // (workgroup-uniform) the registration fails loudly; the others give up the same way
+            if (threadIdx.x == 0 && a0.down) *(int *)((char *)a0.down + offsetof(IcpState, done)) = -1;
+            return false;
+        }
+        return true;
+    };
+    // What the launch leaves behind (the service workgroup, behind at least one hand-over): the state into the slot its
+    // pass names -- a final state into the page-locked block too, a state handed back there marked as such -- and "no
+    // pass" into the other slot, so that the head of the next generic launch does not close a pass again.
+    auto leave = [&](bool handback) {
+        if (!service) return;
+        const int tid = threadIdx.x;
+        const int next = uni(cur.done) != 0 ? uni(cur.pass) + 1 : uni(cur.pass);  // (a stop leaves `pass` at the pass it closed)
+        if (tid < SWORDS) ((PEDP_GLOBAL state_word *)(uintptr_t)(st0 + (next & 1)))[tid] = ((const state_word *)&cur)[tid];
+        if (tid == 0 && handback) as_global(&(st0 + ((next + 1) & 1))->pass)[0] = -1;
+        if (!a0.down) return;
+        __syncthreads();
+        if (tid == 0 && handback) cur.done = STEADY_HANDBACK;
+        __syncthreads();
+        if (tid < SWORDS) ((state_word *)a0.down)[tid] = ((const state_word *)&cur)[tid];
+    };
+
+    bool ran = false;  // a pass of this launch has filled the resident copy of the first chunk
+    for (int p = a0.launch;; ++p) {
+        if (need_close) {
+            // ---- the close of pass p - 1, by every workgroup: same inputs, same float64 sequence, same bits
+            const int q = p - 1;
+            FinishArgs f;
+            f.live = nullptr; f.live_list = nullptr; f.n_lw = 0; f.partials = a0.partials + (size_t)(q & 1) * a0.part_stride; f.packet = nullptr; f.phase = 0;
+            f.estimator = a0.estimator; f.trace = nullptr; f.hist = nullptr; f.bcx = a0.bc[0]; f.bcy = a0.bc[1]; f.bcz = a0.bc[2];
+            f.serial = 0;
+            f.known = 1; f.k_pass = q; f.k_rebuild = 0; f.k_n_live = n_live;
+            icp_finish_body<W * 64, 1, true, 3>(&cur, f, fin, threadIdx.x);  // (ends behind a barrier)
+            PEDP_RT(p, 7);
+            // candidate slots of pass q that searched / that a certificate served (all workgroups agree: the same sums)
+            const double pk31 = fin.pk[PACKET + 2];
+            const long long searched = (long long)(pk31 / CERT_PACK);
+            const long long certified = (long long)(pk31 - (double)searched * CERT_PACK);
+            const bool stopped = uni(cur.done) != 0;
+            // (a pass a generic launch ran counts its slots by waves -- a wave with one uncertified slot searches all sixteen --
+            // and says little about the next pass here: the share decides only behind a pass of this launch)
+            const bool handback = !stopped && (uni(cur.rebuild) != 0 || (q >= a0.launch && searched * 8 > searched + certified));
+            if (threadIdx.x == 0) {
+                if (q >= a0.launch) cur.n_steady += 1;  // (the pass ran in this launch)
+                if (q >= max_iter) cur.n_head -= 1;  // the last pass counts as closed in its launch, as it is without this kernel
+                cur.idle_base = base0 + arrivals;
+                if (planned && !stopped && !handback) cur.n_planned += 1;  // (counted where the pass's state is made)
+            }
+            if (service) {
+                const int tid = threadIdx.x;
+                if (sa.trace && tid < 18)
+                    as_global(sa.trace)[18 * q + tid] = tid == 0 ? cur.fitness : (tid == 1 ? cur.rmse : fin.t0[tid >= 2 ? tid - 2 : 0]);
+                if (!stopped && tid < 16) as_global(sa.hist)[16 * (q + 1) + tid] = cur.upd[tid];
+                if (!stopped && tid < PACKET) as_global(sa.packet)[tid] = fin.pk[tid];
+            }
+            __syncthreads();
+            if (stopped || handback) {
+                if (handovers == 0 && !hand_over(31)) return;
+                if (threadIdx.x == 0) cur.idle_base = base0 + arrivals;
+                __syncthreads();
+                leave(handback);
+                return;
+            }
+        } else if (uni(cur.rebuild) != 0) {  // the pass this launch was to start with is a rebuild pass: not ours
+            if (!hand_over(31)) return;
+            if (threadIdx.x == 0) cur.idle_base = base0 + arrivals;
+            __syncthreads();
+            leave(true);
+            return;
+        }
+        need_close = true;
+        // ---- pass p
+        PEDP_RT(p, 0);
+        for (int it = 0;; ++it) {
+            // (the thread index is made opaque per chunk, as in icp_pass_kernel)
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const int half = wv >> 2, q4 = wv & 3;
+            const int j = lane & 15, g = lane >> 4;
+            const unsigned long long lt = (1ull << lane) - 1ull;
+            const double *Pk_in = a.Pk + (size_t)(p & 1) * a.pp_stride, *Tp_in = a.Tprev + (size_t)(p & 1) * a.pp_stride;
+            PEDP_GLOBAL double *Pk_out = as_global(a.Pk) + (size_t)((p + 1) & 1) * a.pp_stride, *Tp_out = as_global(a.Tprev) + (size_t)((p + 1) & 1) * a.pp_stride;
+            const float *cert_in = a.cert + (size_t)(p & 1) * a.cert_stride;
+            PEDP_GLOBAL float *cert_out = as_global(a.cert) + (size_t)((p + 1) & 1) * a.cert_stride;
+            int unit = (int)(blockIdx.x + (unsigned)it * (unsigned)G), chunk;
+            if (unit >= n_live) break;
+            if (it == 0) {
+                chunk = chunk_first;
+                if (planned) { unit = vis[0]; chunk = vis[1]; }
+            } else {
+                chunk = as_global(a.live_list)[unit];
+            }
+            const bool res = ran && it == 0;  // (workgroup-uniform) the chunk's inputs are in LDS
+            // ---- 1. transform, certificate check, box test, compaction (icp_pass_kernel's phase 1 of a steady pass)
+            int nsl;
+            {
+                bool cand = false, certd = false;
+                int pi = -1, jprev = -1;
+                float c_new = 0.f;
+                double x = 0.0, y = 0.0, z = 0.0, dprev = dnan, d2prev = dnan;
+                const int64_t k = (int64_t)chunk * CH + half * 64 + lane;
+                const bool valid = k < a.N;
+                const int pos = half * 64 + lane;
+                if (valid) {
+                    double ux, uy, uz;
+                    float c_in;
+                    if (res) {
+                        pi = rpi[pos];
+                        x = rP[p & 1][0][pos]; y = rP[p & 1][1][pos]; z = rP[p & 1][2][pos];
+                        ux = rT[0][pos]; uy = rT[1][pos]; uz = rT[2][pos];
+                        c_in = rc[pos];
+                        jprev = rj[pos];
+                    } else {
+                        pi = as_global(a.perm)[k];
+                        x = load_sc1(&Pk_in[3 * k]); y = load_sc1(&Pk_in[3 * k + 1]); z = load_sc1(&Pk_in[3 * k + 2]);
+                        ux = load_sc1(&Tp_in[3 * k]); uy = load_sc1(&Tp_in[3 * k + 1]); uz = load_sc1(&Tp_in[3 * k + 2]);
+                        c_in = load_sc1(&cert_in[k]);
+                        jprev = load_sc1(&a.idx_out[pi]);  // (rewritten in this pass by the slot's own wave only, behind this read)
+                    }
+                    const double x0 = x, y0 = y, z0 = z;
+                    xform(cur.upd, x, y, z);
+                    d2prev = dist2(x, y, z, ux, uy, uz);
+                    dprev = sqrt(d2prev);
+                    const double m = sqrt(dist2(x, y, z, x0, y0, z0));
+                    c_new = (float)(((double)c_in - m * (1.0 + 1e-12)) * (1.0 - 2e-7));
+                    const bool fin_ = (__double2hiint(d2prev) & 0x7FF00000) != 0x7FF00000 && (__double2hiint(m) & 0x7FF00000) != 0x7FF00000 &&
+                                      (__float_as_int(c_new) & 0x7F800000) != 0x7F800000;
+                    certd = fin_ && jprev >= 0 && c_new > 0.f && dprev * (1.0 + 1e-12) < (double)c_new;
+                    if (!certd) c_new = 0.f;
+                    const double ex = fmax(fmax(a.lo[0] - x, x - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - y, y - a.hi[1]), 0.0),
+                                 ez = fmax(fmax(a.lo[2] - z, z - a.hi[2]), 0.0);
+                    const double d2box = ex * ex + ey * ey + ez * ez;
+                    cand = d2box <= bcast0(cur.r2cut);
+                }
+                const unsigned long long mc = __builtin_amdgcn_ballot_w64(cand);
+                const int wc = __builtin_popcountll(mc);
+                if (q4 == 0 && valid) {
+                    if (!cand) { as_global(a.idx_out)[pi] = -1; store_nan(&Tp_out[3 * k]); cert_out[k] = 0.f; }
+                    Pk_out[3 * k] = x; Pk_out[3 * k + 1] = y; Pk_out[3 * k + 2] = z;
+                    if (it == 0) {
+                        rpi[pos] = pi;
+                        rP[(p + 1) & 1][0][pos] = x; rP[(p + 1) & 1][1][pos] = y; rP[(p + 1) & 1][2][pos] = z;
+                        if (!cand) { rj[pos] = -1; lds_nan(&rT[0][pos]); rc[pos] = 0.f; }
+                    }
+                }
+                const int sl = __builtin_popcountll(mc & lt) - 16 * q4;
+                if (cand && sl >= 0 && sl < 16) {
+                    wcert[wv][sl] = c_new; wfj[wv][sl] = jprev; wfd[wv][sl] = d2prev;
+                    const float sx = (float)(x - bcast0(cur.centroid[0])), sy = (float)(y - bcast0(cur.centroid[1])), sz = (float)(z - bcast0(cur.centroid[2]));
+                    const float s1 = fabsf(sx) + fabsf(sy) + fabsf(sz);
+                    wpi[wv][sl] = pi;
+                    wkk[wv][sl] = half * 64 + lane;
+                    wp[wv][0][sl] = x; wp[wv][1][sl] = y; wp[wv][2][sl] = z;
+                    wcs[wv][0][sl] = sx; wcs[wv][1][sl] = sy; wcs[wv][2][sl] = sz;
+                    // the slot's search radius, as a searching slot of icp_pass_kernel gets it under certificates
+                    const float rp = PEDP_ICP_KAPPA * ((float)dprev * 1.00001f) + 1e-5f * s1 + 1e-6f;
+                    const float r_search = unif(cur.r_search);
+                    wrho[wv][sl] = rp < r_search ? rp : r_search;
+                }
+                nsl = wc - 16 * q4;
+                nsl = nsl < 0 ? 0 : (nsl > 16 ? 16 : nsl);
+                __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed
+            }
+            const bool real = j < nsl;
+            double fd = dinf;
+            int fj = -1;
+            if (real) { fj = wfj[wv][j]; fd = wfd[wv][j]; }
+            // ---- the exact search of the slots no certificate serves, the whole wave per slot
+            unsigned amb = (unsigned)(__builtin_amdgcn_ballot_w64(real && g == 0 && __float_as_int(wcert[wv][j]) == 0) & 0xFFFFull);
+            const int n_search = __builtin_popcount(amb);
+            while (amb != 0u) {  // wave-uniform
+                const int s = __builtin_ctz(amb);
+                amb &= amb - 1u;
+                const double sx64 = wp[wv][0][s], sy64 = wp[wv][1][s], sz64 = wp[wv][2][s];
+                const float sx = wcs[wv][0][s], sy = wcs[wv][1][s], sz = wcs[wv][2][s], rho_s = wrho[wv][s];
+                const float slack = 1e-5f * (fabsf(sx) + fabsf(sy) + fabsf(sz)) + 1e-6f;  // fp32 rounding of the centred point
+                auto near_pt = [&](const float4 &ts) -> bool {
+                    const float dx = ts.x - sx, dy = ts.y - sy, dz = ts.z - sz;
+                    const float lim = rho_s + ts.w + slack;
+                    return !((dx * dx + dy * dy + dz * dz) > lim * lim * 1.00001f + 1e-6f) && ts.w >= 0.f;
+                };
+                double xd = dinf, x2 = dinf;  // smallest and second smallest exact d^2 this lane has seen (ties counted)
+                int xj = 0x7FFFFFFF;
+                for (int R = 0; R * 64 < a.n_words; ++R) {
+                    const int wi = R * 64 + lane;
+                    const float4 wsR = R == 0 ? wsph0[lane] : gload4(a.word_sph + (wi < a.n_words ? wi : 0));
+                    unsigned long long km = __builtin_amdgcn_ballot_w64(wi < a.n_words && near_pt(wsR));
+                    while (km != 0ull) {
+                        const int word = R * 64 + __builtin_ctzll(km);
+                        km &= km - 1ull;
+                        const int tile = word * 64 + lane;
+                        const float4 ts = gload4(a.tile_sph + (tile < a.n_tiles ? tile : 0));
+                        unsigned long long near = __builtin_amdgcn_ballot_w64(tile < a.n_tiles && near_pt(ts));
+                        while (near != 0ull) {  // wave-uniform: 64 lanes = 64 rows = 4 tiles per trip (scan_near_tiles)
+                            int t = -1;
+#pragma unroll
+                            for (int gg = 0; gg < 4; ++gg) {
+                                if (near != 0ull) {
+                                    const int bit = __builtin_ctzll(near);
+                                    near &= near - 1ull;
+                                    const int u = __shfl(tile, bit, 64);
+                                    if (gg == g) t = u;
+                                }
+                            }
+                            const int64_t row = (int64_t)t * 16 + j;
+                            if (t >= 0 && row < a.Nt) {
+                                const double d = dist2(sx64, sy64, sz64, as_global(a.tgt_s)[6 * row], as_global(a.tgt_s)[6 * row + 1], as_global(a.tgt_s)[6 * row + 2]);
+                                const int ri = as_global(a.tperm)[row];
+                                const bool wins = d < xd || (d == xd && ri < xj);
+                                x2 = wins ? xd : (d < x2 ? d : x2);
+                                xd = wins ? d : xd;
+                                xj = wins ? ri : xj;
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int off = 1; off <= 32; off <<= 1) {
+                    const double od = __shfl_xor(xd, off, 64), o2 = __shfl_xor(x2, off, 64);
+                    const int oj = __shfl_xor(xj, off, 64);
+                    const double hi = xd < od ? od : xd, lo2 = x2 < o2 ? x2 : o2;
+                    x2 = hi < lo2 ? hi : lo2;
+                    lexmin(xd, xj, od, oj);
+                }
+                if (j == s) {
+                    const bool found = xj != 0x7FFFFFFF;
+                    fd = found ? xd : dinf;
+                    fj = found ? xj : -1;
+                    // the certificate the slot leaves: every target point but the winner is farther than rho (less the rounding
+                    // allowance rho carries) or was scanned, and the best of those behind the winner is x2
+                    const double rho = (double)rho_s * (1.0 - 2e-5) - (double)slack * 1.000001;
+                    const double Le = x2 * (1.0 - 1e-12);
+                    double L2 = rho * rho;
+                    L2 = Le < L2 ? Le : L2;
+                    const bool ok = found && rho > 0.0 && L2 > 0.0 && (__double2hiint(L2) & 0x7FF00000) != 0x7FF00000;
+                    if (g == 0) wcert[wv][s] = ok ? (float)(sqrt(L2) * (1.0 - 2e-7)) : 0.f;
+                }
+            }
+            // ---- 6. the sub-block's partial sums (icp_pass_kernel's phase 6; neighbour and normal by index)
+            {
+                double acc[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[k] = 0.0;
+                const int i = real ? wpi[wv][j] : -1;
+                int jn = fj;
+                const double dd = fd;
+                if (i >= 0) {
+                    if (jn >= 0 && !(dd < bcast0(cur.r2))) jn = -1;  // strict, as SearchHybrid's lower_bound
+                    const int pos = wkk[wv][j];
+                    const int64_t kp = (int64_t)chunk * CH + pos;
+                    // a resident slot that keeps last pass's neighbour has its row and normal in LDS: no fetch by index
+                    const bool kept = res && jn >= 0 && jn == rj[pos];
+                    if (g == 0) {
+                        as_global(a.idx_out)[i] = jn;
+                        if (jn < 0) store_nan(&Tp_out[3 * kp]);
+                        const float c_out = jn >= 0 ? wcert[wv][j] : 0.f;
+                        cert_out[kp] = c_out;
+                        if (it == 0) {
+                            rj[pos] = jn; rc[pos] = c_out;
+                            if (jn < 0) lds_nan(&rT[0][pos]);
+                        }
+                    }
+                    if (jn >= 0) {
+                        const double sx = wp[wv][0][j], sy = wp[wv][1][j], sz = wp[wv][2][j];
+                        double tx, ty, tz, nx = 0.0, ny = 0.0, nz = 0.0;
+                        if (kept) {
+                            tx = rT[0][pos]; ty = rT[1][pos]; tz = rT[2][pos];
+                            if (a.estimator == PEDP_POINT_TO_PLANE) { nx = rN[0][pos]; ny = rN[1][pos]; nz = rN[2][pos]; }
+                        } else {
+                            tx = as_global(a.tgt)[3 * (int64_t)jn]; ty = as_global(a.tgt)[3 * (int64_t)jn + 1]; tz = as_global(a.tgt)[3 * (int64_t)jn + 2];
+                            if (a.estimator == PEDP_POINT_TO_PLANE) {
+                                nx = as_global(a.nrm)[3 * (int64_t)jn]; ny = as_global(a.nrm)[3 * (int64_t)jn + 1]; nz = as_global(a.nrm)[3 * (int64_t)jn + 2];
+                            }
+                        }
+                        if (g == 0) {
+                            Tp_out[3 * kp] = tx; Tp_out[3 * kp + 1] = ty; Tp_out[3 * kp + 2] = tz;
+                            if (it == 0 && !kept) {
+                                rT[0][pos] = tx; rT[1][pos] = ty; rT[2][pos] = tz;
+                                rN[0][pos] = nx; rN[1][pos] = ny; rN[2][pos] = nz;
+                            }
+                        }
+#define PEDP_PUT(K, V)                                   \
+    do {                                                 \
+        const double v_ = (V);                           \
+        if (g == ((K) & 3)) acc[(K) >> 2] = v_;          \
+    } while (0)
+                        if (a.estimator == PEDP_POINT_TO_PLANE) {
+                            const double r = (sx - tx) * nx + (sy - ty) * ny + (sz - tz) * nz;
+                            const double J[6] = {sy * nz - sz * ny, sz * nx - sx * nz, sx * ny - sy * nx, nx, ny, nz};
+                            int k = 0;
+#pragma unroll
+                            for (int u = 0; u < 6; ++u)
+#pragma unroll
+                                for (int v = u; v < 6; ++v) { PEDP_PUT(k, J[u] * J[v]); ++k; }
+#pragma unroll
+                            for (int u = 0; u < 6; ++u) PEDP_PUT(21 + u, J[u] * r);
+                        } else {
+                            const double ccx = bcast0(cur.centroid[0]), ccy = bcast0(cur.centroid[1]), ccz = bcast0(cur.centroid[2]);
+                            const double s3[3] = {sx - ccx, sy - ccy, sz - ccz}, t3[3] = {tx - ccx, ty - ccy, tz - ccz};
+#pragma unroll
+                            for (int u = 0; u < 3; ++u) { PEDP_PUT(u, s3[u]); PEDP_PUT(3 + u, t3[u]); }
+#pragma unroll
+                            for (int u = 0; u < 3; ++u)
+#pragma unroll
+                                for (int v = 0; v < 3; ++v) PEDP_PUT(6 + 3 * u + v, t3[u] * s3[v]);
+                        }
+                        PEDP_PUT(27, dd);
+                        PEDP_PUT(28, 1.0);
+#undef PEDP_PUT
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const double v = row_sum_step<3>(row_sum_step<2>(row_sum_step<1>(row_sum_step<0>(acc[k]))));
+                    if (j == 0) accsh[wv][4 * k + g] = v;
+                }
+                // (entries 29, 30 of the tree are zero: the statistics replace them -- nothing is swept here)
+                __builtin_amdgcn_s_waitcnt(0xC07F);
+                if (lane == 0) {
+                    accsh[wv][PACKET] = 0.0;
+                    accsh[wv][PACKET + 1] = (double)n_search;
+                    accsh[wv][PACKET + 2] = (double)(nsl - n_search) + CERT_PACK * (double)n_search;
+                }
+            }
+            __syncthreads();
+            if (tid < PSTRIDE) {
+                double v = 0.0;
+#pragma unroll
+                for (int w = 0; w < W; ++w) v += accsh[w][tid];
+                store_sc1(&a.partials[(size_t)(p & 1) * a.part_stride + (size_t)unit * PSTRIDE + tid], v);
+            }
+            __syncthreads();  // the waves' sums are reused by the next chunk
+        }
+        ran = true;
+        if (!hand_over(p)) return;
+    }
+}
+
+}  // namespace

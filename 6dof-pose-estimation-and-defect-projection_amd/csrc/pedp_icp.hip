@@ -53,6 +53,7 @@
 //                            icp_finish_body, icp_finish_kernel
 //   icp/fused_pass.h         sweep_sub_block, icp_pass_kernel, batch_state_scatter_kernel, batch_state_gather_kernel,
 //                            icp_state_start_kernel
+//   icp/steady_pass.h        icp_steady_kernel: fully certified passes of a single registration in one resident launch
 #include "pedp_internal.h"
 #include <atomic>
 #include <cmath>
@@ -77,6 +78,7 @@
 #include "icp/ransac.h"
 #include "icp/fused_close.h"
 #include "icp/fused_pass.h"
+#include "icp/steady_pass.h"
 
 namespace {
 
@@ -318,6 +320,52 @@ inline bool icp_certificates() {
     return m;
 }
 
+// PEDP_ICP_STEADY=0: every pass of a single registration is a launch of icp_pass_kernel again.  (Default: a registration
+// that closes its passes at the head of the next launch and keeps certificates runs its passes from PEDP_ICP_STEADY_FROM on,
+// default 5, in ONE launch of icp_steady_kernel, steady_pass.h.)
+inline bool icp_steady() {
+    static const bool m = env_flag("PEDP_ICP_STEADY", true);
+    return m;
+}
+inline int env_int(const char *name, int unset) {
+    const char *v = getenv(name);
+    return v && *v ? atoi(v) : unset;
+}
+inline int steady_from() {
+    static const int f = env_int("PEDP_ICP_STEADY_FROM", 5);
+    return f < 1 ? 1 : f;
+}
+// Workgroups of a steady launch: all of them must be resident at once, so the grid is what the runtime says fits --
+// hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs -- and at most two per CU.  PEDP_ICP_STEADY_GRID=n caps it (tests: several
+// chunks per workgroup at a few hundred points).  0: the kernel cannot be resident -- the registration keeps to generic launches.
+inline int steady_grid(pedp_ctx_t c) {
+    static std::atomic<int> per_cu[64];  // by device; 0: not asked yet, -1: asked and refused
+    const int dev = c->device >= 0 && c->device < 64 ? c->device : 0;
+    int n = per_cu[dev].load(std::memory_order_relaxed);
+    if (n == 0) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel, BK_W * 64, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = -1; }
+        per_cu[dev].store(n = nb, std::memory_order_relaxed);
+    }
+    if (n < 1) return 0;
+    int64_t g = (int64_t)(n < 2 ? n : 2) * c->num_cus;
+    static const int cap = env_int("PEDP_ICP_STEADY_GRID", 0);
+    if (cap > 0 && g > cap) g = cap;
+    return (int)g;
+}
+// One steady launch at a time per device and process: two resident grids whose ranks together exceed what the device holds
+// could each wait for workgroups the other keeps out (the bounded wait would turn that into PEDP_ERR_HIP).  A registration
+// that finds the device taken keeps to generic launches.  (Other PROCESSES on the device are not seen from here.)
+inline std::atomic<int> &steady_busy(int device) {
+    static std::atomic<int> busy[64];
+    return busy[device >= 0 && device < 64 ? device : 0];
+}
+inline bool steady_acquire(int device) {
+    int free_ = 0;
+    return steady_busy(device).compare_exchange_strong(free_, 1, std::memory_order_acq_rel);
+}
+inline void steady_release(int device) { steady_busy(device).store(0, std::memory_order_release); }
+
 // Enqueue one correspondence pass (transform, sweep, fallback).  mode as in
 // icp_transform_pack_kernel.
 int enqueue_nn_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_cloud_t tgt, int mode,
@@ -390,7 +438,7 @@ inline double fused_margin(double r) { return 2.0 * r; }   // (1 r ... 4 r measu
 // (sum, solve, update); otherwise icp_finish_kernel launches follow (exchange step in between).
 int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_cloud_t tgt, int estimator,
                        const TargetPrep &tp, hipEvent_t ev0, hipEvent_t ev1, bool fuse, double *trace, int poses = 1,
-                       unsigned long long *down = nullptr, int head_launch = -1) {
+                       unsigned long long *down = nullptr, int head_launch = -1, bool steady = false) {
     PassArgs pa;
     pa.src = src->pts; pa.perm = w.src_perm; pa.N = src->N; pa.n_chunks = w.n_chunks;
     pa.hist = w.hist; pa.Pk = w.Pk; pa.Tprev = w.Tprev; pa.live = w.live; pa.live_list = w.live_list;
@@ -418,7 +466,9 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pe
     if (g < 1) g = 1;
     if (pa.head) g += 1;
     if (ev0) PEDP_HIP_CHECK(hipEventRecord(ev0, c->stream));
-    if (poses > 1)
+    if (steady)  // head_launch and every pass behind it that is fully certified, in one resident launch (steady_pass.h)
+        hipLaunchKernelGGL(icp_steady_kernel, dim3((unsigned)steady_grid(c)), dim3(BK_W * 64), 0, c->stream, w.st, pa);
+    else if (poses > 1)
         hipLaunchKernelGGL((icp_pass_kernel<BK_W, true>), dim3((unsigned)g, (unsigned)poses), dim3(BK_W * 64), 0, c->stream, w.st, pa);
     else
         hipLaunchKernelGGL((icp_pass_kernel<BK_W, false>), dim3((unsigned)g), dim3(BK_W * 64), 0, c->stream, w.st, pa);
@@ -662,6 +712,14 @@ struct IcpJob {
     // steady passes are left open and closed at the head of the next launch (fused_close.h); decided once, here: the
     // kernels' slots and the slots the host looks at follow from this one flag
     bool head = false;
+    // passes from steady_from() on run in one launch of icp_steady_kernel; icp_collect continues a registration that
+    // the kernel hands back (a rebuild, too many searching slots) and needs what the launches need
+    bool steady = false;
+    bool steady_held = false;  // this job holds the device's steady launch (steady_acquire) until it is collected
+    pedp_cloud_t source = nullptr, target = nullptr;
+    TargetPrep tp{};
+    int estimator = 0;
+    bool want_trace = false;
 };
 constexpr size_t RESULT_OFF = 2048;
 static_assert(sizeof(IcpState) <= RESULT_OFF && sizeof(IcpState) % 8 == 0, "start and final state share the block's first 4 KB, as 8-byte words");
@@ -699,7 +757,7 @@ int icp_prepare(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, TargetPr
 }
 
 // workspace of one registration on executor x (may grow the executor's scratch buffer)
-int icp_job_setup(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *prm, IcpJob &job) {
+int icp_job_setup(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *prm, IcpJob &job, bool no_steady = false) {
     PEDP_HIP_CHECK(hipSetDevice(x->device));
     job.max_iter = prm->max_iteration;
     job.Ns = source->N;
@@ -714,6 +772,10 @@ int icp_job_setup(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const 
                        (job.Nt + 1023) / 1024 <= BK_WCAP;
     job.dev_result = fused && !prm->allreduce && !prm->use_comm && !unfused_finish() && !copy_bracket();
     job.head = job.dev_result && !serial_close() && head_close();
+    // (a pass timed on its own, or every fourth one, is a launch of its own; -3 times the whole registration)
+    job.steady = job.head && icp_certificates() && icp_steady() && !no_steady && (job.timed_pass == -1 || job.timed_pass == -3) &&
+                 steady_grid(x) > 0;
+    job.source = source; job.target = target; job.estimator = prm->estimator;
     int rc = carve_workspace(x, job.Ns, job.Nt, job.max_iter, job.qt, w, fused);
     if (rc) return rc;
     bind_clouds(w, source, target, job.qt);
@@ -831,6 +893,16 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
     if (job.timed_pass != -1) { x->nn_pairs = 0; x->nn_span_launches = 1; }
     for (int pass = 0; pass <= max_iter; ++pass) {
         hipEvent_t ev0, ev1;
+        if (head && job.steady && pass == steady_from()) {
+            // this pass and all behind it in one launch; what it hands back icp_collect continues (the second event of
+            // timed_pass = -3 stands behind the launch that ends the registration: this one, unless it hands back)
+            rc = pass_timing_events(x, job.timed_pass, max_iter, max_iter, ev0, ev1);
+            if (rc) return rc;
+            rc = enqueue_fused_pass(x, w, source, target, prm->estimator, tp, nullptr, ev1, true, trace, 1, down, pass, true);
+            if (rc) return rc;
+            x->icp_last_launches = max_iter + 1;  // (the passes this enqueue covers)
+            break;
+        }
         rc = pass_timing_events(x, job.timed_pass, pass, max_iter, ev0, ev1);
         if (rc) return rc;
         x->icp_last_launches = ++launches;  // passes enqueued (statistics: the early exit stops enqueuing)
@@ -887,30 +959,66 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
 // A registration made ready on executor x: its workspace, its start state in x's pinned block, the result slot armed.
 // (All that a replay of a captured graph needs.)
 int icp_stage(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp, const pedp_icp_params *prm,
-              const double init[16], IcpJob &job) {
-    int rc = icp_job_setup(x, source, target, prm, job);
+              const double init[16], IcpJob &job, bool no_steady = false) {
+    int rc = icp_job_setup(x, source, target, prm, job, no_steady);
     if (rc) return rc;
+    job.tp = tp;
     icp_fill_state((IcpState *)x->pinned, tp, init, prm, source->N);
     icp_arm_result(x);
     return PEDP_OK;
 }
 // ... and started: every pass enqueued on x's stream
 int icp_start(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp, const pedp_icp_params *prm,
-              const double init[16], IcpJob &job, bool want_trace, bool early_stop) {
-    int rc = icp_stage(x, source, target, tp, prm, init, job);
+              const double init[16], IcpJob &job, bool want_trace, bool early_stop, bool no_steady = false) {
+    // (pedp_icp's look at `done` behind every 8th launch needs launches to look behind)
+    int rc = icp_stage(x, source, target, tp, prm, init, job, no_steady || (early_stop && prm->relative_fitness >= 0.0));
     if (rc) return rc;
-    return icp_enqueue(x, source, target, tp, prm, want_trace, early_stop, job);
+    job.want_trace = want_trace;
+    if (job.steady && prm->max_iteration >= steady_from()) {
+        job.steady_held = steady_acquire(x->device);
+        if (!job.steady_held) job.steady = false;
+    }
+    rc = icp_enqueue(x, source, target, tp, prm, want_trace, early_stop, job);
+    if (rc && job.steady_held) { steady_release(x->device); job.steady_held = false; }
+    return rc;
 }
 
 int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitness, double *inlier_rmse,
                 int32_t *n_iter_done, int32_t *corr, double *trace) {
     PEDP_HIP_CHECK(hipSetDevice(x->device));
     const IcpWorkspace &w = job.w;
+    long long handbacks = 0;
+    struct SteadyHold {  // (released on every way out of here, once the stream has been waited for)
+        int device; bool held;
+        ~SteadyHold() { if (held) steady_release(device); }
+    } hold{x->device, job.steady_held};
+    if (job.steady) {
+        // A steady launch either ends the registration or hands it back with the state of the pass that is to run next
+        // (in its slot, and a marked copy in the page-locked block): two generic launches from that pass, the steady
+        // launch again, until the registration is over.  Each round runs at least one pass.
+        PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
+        IcpState *res = (IcpState *)((char *)x->pinned + RESULT_OFF);
+        while (res->done == STEADY_HANDBACK) {
+            ++handbacks;
+            const int from = res->pass;
+            res->done = 0;
+            for (int pass = from; pass <= job.max_iter && pass <= from + 2; ++pass) {
+                const int rc = enqueue_fused_pass(x, w, job.source, job.target, job.estimator, job.tp, nullptr, nullptr, true,
+                                                  job.want_trace ? w.trace : nullptr, 1, (unsigned long long *)res, pass, pass == from + 2);
+                if (rc) return rc;
+            }
+            if (job.timed_pass == -3) { PEDP_HIP_CHECK(hipEventRecord(x->nn_ev1, x->stream)); }
+            PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
+        }
+    }
+    bool copies = false;
     if (corr && job.Ns > 0)
-        { int dn_ = pedp_download(x, corr, w.idx, sizeof(int32_t) * (size_t)job.Ns); if (dn_) return dn_; }
-    if (trace)
+        { int dn_ = pedp_download(x, corr, w.idx, sizeof(int32_t) * (size_t)job.Ns); if (dn_) return dn_; copies = true; }
+    if (trace) {
         PEDP_HIP_CHECK(hipMemcpyAsync(trace, w.trace, sizeof(double) * 18 * (size_t)(job.max_iter + 1), hipMemcpyDeviceToHost, x->stream));
-    PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
+        copies = true;
+    }
+    if (copies || !job.steady) PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
     const IcpState *hp = (const IcpState *)((const char *)x->pinned + (job.dev_result ? RESULT_OFF : 0));
     if (job.dev_result && hp->done == 0) {  // (armed by icp_arm_result; the workgroup that sets `done` writes the state)
         pedp_set_error("pedp_icp: the registration's final state did not arrive");
@@ -930,6 +1038,8 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     x->icp_last_head = hp->n_head;
     x->icp_last_cert = hp->sum_cert;
     x->icp_last_searched = hp->sum_searched;
+    x->icp_last_steady = hp->n_steady;
+    x->icp_last_handbacks = handbacks;
     x->icp_last_rebuilds = hp->n_rebuilds;
     x->icp_last_bracket = (copy_bracket() ? 0 : 1) + (job.dev_result ? 2 : 0);
     x->icp_last_nt = job.Nt;
@@ -952,7 +1062,7 @@ bool graph_key_equal(const pedp_icp_graph_key &a, const pedp_icp_graph_key &b) {
 
 int icp_launch_replayed(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp,
                         const pedp_icp_params *prm, const double init[16], IcpJob &job) {
-    int rc = icp_stage(x, source, target, tp, prm, init, job);
+    int rc = icp_stage(x, source, target, tp, prm, init, job, true);  // (a captured graph holds generic launches only)
     if (rc) return rc;
     pedp_icp_graph_key key;
     key.src_gen = source->gen; key.tgt_gen = target->gen; key.ws = x->icp_ws.ptr;
@@ -1103,6 +1213,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
 
 void pedp_icp_drop_pending(pedp_ctx_t c) {
     if (c && c->icp_pending) {
+        if (((IcpJob *)c->icp_pending)->steady_held) steady_release(c->device);
         delete (IcpJob *)c->icp_pending;
         c->icp_pending = nullptr;
     }
@@ -1201,7 +1312,7 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
     if (!uniform) {
         for (int b = 0; b < B; ++b) {
             IcpJob job;
-            rc = icp_start(c, source, target, tp, &prms[b], inits + 16 * b, job, false, true);
+            rc = icp_start(c, source, target, tp, &prms[b], inits + 16 * b, job, false, true, true);
             if (rc) return rc;
             rc = icp_collect(c, job, T_out + 16 * b, fitness ? fitness + b : nullptr, inlier_rmse ? inlier_rmse + b : nullptr,
                              n_iter_done ? n_iter_done + b : nullptr, nullptr, nullptr);
@@ -1443,6 +1554,13 @@ int pedp_icp_last_certified(pedp_ctx_t c, int64_t *slots, int64_t *searched_slot
     PEDP_REQUIRE(c && slots, "pedp_icp_last_certified: null argument");
     *slots = c->icp_last_cert;
     if (searched_slots) *searched_slots = c->icp_last_searched;
+    return PEDP_OK;
+}
+
+int pedp_icp_last_steady(pedp_ctx_t c, int64_t *passes, int64_t *handbacks) {
+    PEDP_REQUIRE(c && passes, "pedp_icp_last_steady: null argument");
+    *passes = c->icp_last_steady;
+    if (handbacks) *handbacks = c->icp_last_handbacks;
     return PEDP_OK;
 }
 

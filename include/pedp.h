@@ -550,6 +550,22 @@ int pedp_icp_last_head_closed(pedp_ctx_t ctx, int64_t *head_closed, int64_t *reb
  * Results do not change in any bit (tests/test_icp_certificate_gpu.py compares). */
 int pedp_icp_last_certified(pedp_ctx_t ctx, int64_t *slots, int64_t *searched_slots);
 
+/* Passes of the last single registration collected on `ctx` that ran inside a steady launch (`passes`), and how often such
+ * a launch handed the registration back to the generic pass kernel (`handbacks`, may be null).  A registration that closes
+ * its passes at the head of the next launch and keeps certificates (the two read-outs above) runs its passes from
+ * PEDP_ICP_STEADY_FROM (default 5) on in ONE launch of a resident grid: per pass a bounded device-wide hand-over of the
+ * partial sums replaces the launch boundary, every workgroup closes the pass itself, and a slot without a certificate runs
+ * the exact search.  The launch hands back when a close asks for a rebuild of the live set or more than 1/8 of a pass's
+ * candidate slots searched; pedp_icp_end / pedp_icp then run two generic launches and the steady launch again.
+ * PEDP_ICP_STEADY=0 (read once per process): 0 passes; so do batches, sharded registrations, captured graphs, a timed_pass
+ * other than -1 and -3, and pedp_icp with criteria >= 0 (its early-exit look needs launches to look behind).
+ * One steady launch per device is in flight per process (a second registration at the same time keeps to generic launches);
+ * where several PROCESSES register on one device at once, set PEDP_ICP_STEADY=0: two resident grids can keep each other out,
+ * which the bounded hand-over ends with PEDP_ERR_HIP.
+ * PEDP_ICP_STEADY_GRID=n caps the launch's workgroups (tests).  Results do not change in any bit
+ * (tests/test_icp_steady_gpu.py compares). */
+int pedp_icp_last_steady(pedp_ctx_t ctx, int64_t *passes, int64_t *handbacks);
+
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
  * g[i * n_tgt + j] = |t'_j|^2 - 2 s'_i . t'_j exactly as the sweep's v_mfma_f32_16x16x32_bf16 produces it (same operand packing). */

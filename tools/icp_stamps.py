@@ -92,6 +92,21 @@ if hasattr(lib, "pedp_debug_icp_rt") and lib.pedp_debug_icp_rt(C.c_void_p(rt.cty
             line += f"; boundary (closed -> next entry) {(e0 - prev_close) / 100.0:5.2f}"
         prev_close = last
         print(line)
+    # passes inside a steady launch (steady_pass.h): per pass, microseconds after the first workgroup began its chunks
+    for p in range(1, min(iters + 1, 31)):
+        r, n = rt[p], rt[p + 1]
+        on = (r[:, 0] > 0) & (r[:, 4] > r[:, 0]) & (r[:, 0] >= r[:, 0].max() - 5000)
+        if not on.any():
+            continue
+        e0 = r[on, 0].min()
+        us = lambda t: (t - e0) / 100.0
+        line = (f"steady pass {p:2d}: {on.sum():3d} workgroups; begun spread {us(r[on,0].max()):5.2f}; chunks done median {np.median(us(r[on,2])):5.2f} max {us(r[on,2].max()):5.2f}; "
+                f"arrived median {np.median(us(r[on,3])):5.2f} max {us(r[on,3].max()):5.2f}; all seen median {np.median(us(r[on,4])):5.2f} max {us(r[on,4].max()):5.2f}")
+        nx = on & (n[:, 7] > r[:, 4])
+        if nx.any():
+            line += (f"; close: loads back median {np.median(us(n[nx,5])):5.2f} max {us(n[nx,5].max()):5.2f}, sums {np.median(us(n[nx,6])):5.2f}, "
+                     f"U median {np.median(us(n[nx,7])):5.2f} max {us(n[nx,7].max()):5.2f}; next pass begun first {us(n[nx,0].min()):5.2f}")
+        print(line)
 # per-wave view of the last pass
 wvb = np.zeros((512, 8, 16), np.int64)
 if hasattr(lib, "pedp_debug_icp_wave") and lib.pedp_debug_icp_wave(C.c_void_p(wvb.ctypes.data)) == 0:
