@@ -125,6 +125,7 @@ PROTOTYPES = {
     "pedp_icp_last_certified": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_steady": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pedp_debug_icp_path": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
     "pedp_icp_end": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int32), C.c_void_p, C.c_void_p]),
     "pedp_icp_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -817,6 +818,38 @@ def icp_last_steady(ctx):
     a, b = C.c_int64(0), C.c_int64(0)
     check(load().pedp_icp_last_steady(ctx._h, C.byref(a), C.byref(b)), "pedp_icp_last_steady")
     return a.value, b.value
+
+
+ICP_SWITCHES = ("nn_f32", "unfused_finish", "no_visit_plan", "serial_close", "copy_bracket", "head_close", "cert", "steady")
+ICP_PATH_FIELDS = ("fused", "dev_result", "copy_bracket", "head", "certify", "plan", "serial_close", "unfused_finish", "exchange",
+                   "steady", "steady_from")
+
+
+class IcpSwitches(C.Structure):     # pedp_icp_switches
+    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order")]
+
+
+class IcpPathInputs(C.Structure):   # pedp_icp_path_inputs
+    _fields_ = [("n_source", C.c_int64), ("n_target", C.c_int64), ("radius", C.c_double)] + [
+        (n, C.c_int) for n in ("unit_size", "poses", "timed_pass", "exhaustive", "exchange", "batch", "early_exit", "no_steady", "resident")]
+
+
+class IcpPath(C.Structure):         # pedp_icp_path
+    _fields_ = [(n, C.c_int) for n in ICP_PATH_FIELDS]
+
+
+def icp_path(switches=None, steady_from=5, n_source=1, n_target=1, radius=1.0, unit_size=1, poses=1, timed_pass=-1, **flags):
+    """Which way a registration would run (pedp_debug_icp_path; no context, no GPU): a dict of the ICP_PATH_FIELDS, bools
+    and steady_from.  switches: the names out of ICP_SWITCHES that are in force (head_close, cert and steady are the
+    defaults); None: what this process read from its environment.  flags: the 0/1 fields of pedp_icp_path_inputs."""
+    sw = None
+    if switches is not None:
+        sw = IcpSwitches(steady_from=int(steady_from), **{n: 1 for n in switches})
+    q = IcpPathInputs(n_source=int(n_source), n_target=int(n_target), radius=float(radius), unit_size=int(unit_size), poses=int(poses),
+                      timed_pass=int(timed_pass), **{n: int(bool(v)) for n, v in flags.items()})
+    out = IcpPath()
+    check(load().pedp_debug_icp_path(C.byref(sw) if sw is not None else None, C.byref(q), C.byref(out)), "pedp_debug_icp_path")
+    return {n: (getattr(out, n) if n == "steady_from" else bool(getattr(out, n))) for n in ICP_PATH_FIELDS}
 
 
 def icp_graph_captures(ctx):

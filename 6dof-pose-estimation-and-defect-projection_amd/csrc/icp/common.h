@@ -140,4 +140,15 @@ __device__ __forceinline__ double dist2(double ax, double ay, double az, double 
     return dadd(dadd(dmul(dx, dx), dmul(dy, dy)), dmul(dz, dz));
 }
 
+// Pointers that reach a kernel through the argument block parked in LDS have no address space the compiler
+// could infer: every access through them came out as a FLAT operation, which counts on the LDS counter as
+// well as on the memory counter -- each LDS read of a list entry then waited for the loads still in flight
+// (`s_waitcnt vmcnt(0) lgkmcnt(0)` in front of the sweep's MFMAs), so nothing was prefetched at all.  The
+// pass kernel states the address space where it dereferences them.
+#define PEDP_GLOBAL __attribute__((address_space(1)))
+template <typename T>
+__device__ __forceinline__ PEDP_GLOBAL T *as_global(T *p) {
+    return (PEDP_GLOBAL T *)(uintptr_t)p;
+}
+
 }  // namespace

@@ -152,16 +152,6 @@ __device__ __forceinline__ void xform(const double *__restrict__ M, double &x, d
     x = nx; y = ny; z = nz;
 }
 
-// Pointers that reach a kernel through the argument block parked in LDS have no address space the compiler
-// could infer: every access through them came out as a FLAT operation, which counts on the LDS counter as
-// well as on the memory counter -- each LDS read of a list entry then waited for the loads still in flight
-// (`s_waitcnt vmcnt(0) lgkmcnt(0)` in front of the sweep's MFMAs), so nothing was prefetched at all.  The
-// pass kernel states the address space where it dereferences them.
-#define PEDP_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ PEDP_GLOBAL T *as_global(T *p) {
-    return (PEDP_GLOBAL T *)(uintptr_t)p;
-}
 __device__ __forceinline__ float4 gload4(const float4 *p) {
     typedef float v4 __attribute__((ext_vector_type(4)));
     const v4 v = *(const PEDP_GLOBAL v4 *)(uintptr_t)p;

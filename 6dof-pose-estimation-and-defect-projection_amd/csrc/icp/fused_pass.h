@@ -12,6 +12,7 @@ constexpr int L2_WORDS = 8;      // mask words whose tile spheres a wave request
 constexpr int SW_G = 8;          // tiles per group of the sweep (A fragments fetched one group ahead)
 
 // exact float64 scan of the rows of the tiles in `near` (one bit per lane's tile), 64 rows per trip
+// (icp_steady_kernel has a copy of this loop that also tracks the second-smallest d^2: keep the two alike)
 __device__ __forceinline__ void scan_near_tiles(unsigned long long near, int unit_of_lane, const PassArgs &a, double qx,
                                                 double qy, double qz, int lane, double &bd, int &bj) {
     while (near != 0ull) {  // wave-uniform: 64 lanes = 64 rows = 4 tiles per trip
@@ -296,16 +297,6 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     const float inf = __uint_as_float(0x7F800000u);
     const double dinf = __longlong_as_double(0x7FF0000000000000ll);
     const double dnan = __longlong_as_double(0x7FF8000000000000ll);
-    // "no neighbour" in Tprev is this NaN's bits, stored as two integer words made where they are stored: as a double
-    // constant the pair was kept in registers through the chunk loop, and spilled.  (dprev's start value stays the
-    // constant: it folds into the code at compile time.)
-    auto store_nan = [](PEDP_GLOBAL double *p) {
-        int z = 0;
-        asm volatile("" : "+v"(z));
-        typedef int v2i_ __attribute__((ext_vector_type(2)));
-        const v2i_ w = {z, 0x7FF80000 | z};
-        *(PEDP_GLOBAL v2i_ *)p = w;
-    };
     // (a batch keeps these in scalar registers; a single registration reads them from the state in LDS where they are used)
     const double ccx_b = BATCH ? st->centroid[0] : 0.0, ccy_b = BATCH ? st->centroid[1] : 0.0, ccz_b = BATCH ? st->centroid[2] : 0.0;
     const float r_search_b = BATCH ? st->r_search : 0.f;
@@ -368,6 +359,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                         const double cx = sp8[0], cy = sp8[1], cz = sp8[2], cr = sp8[3];
                         const double tx = Rs[0] * cx + Rs[1] * cy + Rs[2] * cz + Rs[3], ty = Rs[4] * cx + Rs[5] * cy + Rs[6] * cz + Rs[7],
                                      tz = Rs[8] * cx + Rs[9] * cy + Rs[10] * cz + Rs[11];
+                        // (box_dist2 of slot_math.h, written out: the call moved instructions of this kernel)
                         const double ex = fmax(fmax(a.lo[0] - tx, tx - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - ty, ty - a.hi[1]), 0.0),
                                      ez = fmax(fmax(a.lo[2] - tz, tz - a.hi[2]), 0.0);
                         const double lim = cr * rscale + reach + 1e-9 * (fabs(tx) + fabs(ty) + fabs(tz) + 1.0);
@@ -447,24 +439,16 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                     dprev = sqrt(d2prev);
                     if constexpr (!BATCH) {
                         if (certify) {
-                            // Certificate: every target point but last pass's neighbour was at least c_in from the point;
-                            // the point has moved by m, so they are at least c_in - m from it now (rounded down: the
-                            // factors cover the float64 roundings of dist2 and sqrt a thousand times over, the last one
-                            // the rounding to float32).  The old neighbour strictly inside that bound is the unique nearest
-                            // neighbour, and dist2 to it is the very number the selection would produce.  Non-finite
-                            // values are told by their exponent bits: they never certify.
+                            // the certificate, less the point's motion m: does last pass's neighbour stay proven?  (slot_math.h)
                             const double m = sqrt(dist2(x, y, z, x0, y0, z0));
-                            c_new = (float)(((double)c_in - m * (1.0 + 1e-12)) * (1.0 - 2e-7));
-                            const bool fin = (__double2hiint(d2prev) & 0x7FF00000) != 0x7FF00000 && (__double2hiint(m) & 0x7FF00000) != 0x7FF00000 &&
-                                             (__float_as_int(c_new) & 0x7F800000) != 0x7F800000;
-                            certd = fin && jprev >= 0 && c_new > 0.f && dprev * (1.0 + 1e-12) < (double)c_new;
+                            c_new = cert_moved(c_in, m);
+                            const bool fin = cert_finite(d2prev, m, c_new);
+                            certd = fin && jprev >= 0 && c_new > 0.f && cert_inside(dprev, c_new);
                             if (!certd) c_new = 0.f;
                         }
                     }
                 }
-                const double ex = fmax(fmax(a.lo[0] - x, x - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - y, y - a.hi[1]), 0.0),
-                             ez = fmax(fmax(a.lo[2] - z, z - a.hi[2]), 0.0);
-                const double d2box = ex * ex + ey * ey + ez * ez;
+                const double d2box = box_dist2(x, y, z, a.lo, a.hi);
                 cand = d2box <= unid(PEDP_ST.r2cut);   // r2cut = r^2 (1 + 1e-12): rounding-safe
                 near = d2box <= unid(PEDP_ST.r2live);
             }
@@ -501,11 +485,11 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 wp[wv][0][sl] = x; wp[wv][1][sl] = y; wp[wv][2][sl] = z;
                 wcs[wv][0][sl] = sx; wcs[wv][1][sl] = sy; wcs[wv][2][sl] = sz;
                 // search radius of the slot: the distance to last pass's neighbour, rounded up, at most r
-                float rp = (float)dprev * 1.00001f + 1e-5f * s1 + 1e-6f;
+                float rp = slot_radius(dprev, s1);
                 if constexpr (!BATCH) {
                     // with certificates: KAPPA times that.  Any radius not below the true nearest distance gives the same
                     // result; the wider one leaves a margin between the neighbour and the bound the certificate is made from
-                    if (certify) rp = PEDP_ICP_KAPPA * ((float)dprev * 1.00001f) + 1e-5f * s1 + 1e-6f;
+                    if (certify) rp = slot_radius_kappa(dprev, s1);
                 }
                 const float r_search = BATCH ? r_search_b : unif(cur.r_search);
                 wrho[wv][sl] = rp < r_search ? rp : r_search;
@@ -550,7 +534,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 float lx = real ? px : big, hx = real ? px : -big, ly = real ? py : big, hy = real ? py : -big,
                       lz = real ? pz : big, hz = real ? pz : -big, rmx = rho_j;
                 // level 0: the point itself, widened by the rounding of its centred coordinates
-                float4 node = make_float4(px, py, pz, 1e-5f * (fabsf(px) + fabsf(py) + fabsf(pz)) + 1e-6f);
+                float4 node = make_float4(px, py, pz, point_slack(px, py, pz));
                 float node_r = rho_j;
                 bool open = real;   // no level of this lane's chain is in the cover yet
                 bool mine = false;  // this lane holds a node of the cover
@@ -595,13 +579,13 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
             auto near_sb = [&](const float4 &ts) -> bool {
                 const float dx = ts.x - node0.x, dy = ts.y - node0.y, dz = ts.z - node0.z;
                 const float lim = node0_r + node0.w + ts.w;
-                bool any = !((dx * dx + dy * dy + dz * dz) > lim * lim * 1.00001f + 1e-6f);
+                bool any = !offset_beyond(dx, dy, dz, lim);
 #pragma nounroll
                 for (int i = 1; i < nn; ++i) {  // wave-uniform; broadcast reads
                     const float4 nd = wnode[wv][i];
                     const float ex = ts.x - nd.x, ey = ts.y - nd.y, ez = ts.z - nd.z;
                     const float li = wnode_r[wv][i] + nd.w + ts.w;
-                    any |= !((ex * ex + ey * ey + ez * ez) > li * li * 1.00001f + 1e-6f);
+                    any |= !offset_beyond(ex, ey, ez, li);
                 }
                 return any && ts.w >= 0.f;
             };
@@ -662,7 +646,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                             for (int u = 0; u < L2_WORDS; ++u) {
                                 const float ex = ts[u].x - nd.x, ey = ts[u].y - nd.y, ez = ts[u].z - nd.z;
                                 const float li = nd_r + nd.w + ts[u].w;
-                                if (!((ex * ex + ey * ey + ez * ez) > li * li * 1.00001f + 1e-6f)) nearbits |= 1u << u;
+                                if (!offset_beyond(ex, ey, ez, li)) nearbits |= 1u << u;
                             }
                             nd = ndn;
                             nd_r = ndn_r;
@@ -795,7 +779,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                     nr = fminf(nr, __shfl_xor(nr, 16, 64));
                     nr = fminf(nr, __shfl_xor(nr, 32, 64));
                     const float s1c = fabsf(wcs[wv][0][j]) + fabsf(wcs[wv][1][j]) + fabsf(wcs[wv][2][j]);
-                    const double rho = (double)wrho[wv][j] * (1.0 - 2e-5) - (double)(1e-5f * s1c + 1e-6f) * 1.000001;
+                    const double rho = cert_rho_s1(wrho[wv][j], s1c);
                     const double Lg = ((double)nr + (double)Si) - (double)(PEDP_ICP_CERT_SLACK * e + 4.8e-7f * Si) * 1.000001;
                     const double Le = f2 * (1.0 - 1e-12);
                     double L2 = rho * rho;
@@ -803,7 +787,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                     L2 = Le < L2 ? Le : L2;
                     const bool ok = found && rho > 0.0 && (amb >> j & 1u) == 0u && (__float_as_int(nr) & 0x7FFFFFFF) <= 0x7F800000 && L2 > 0.0 &&
                                     (__double2hiint(L2) & 0x7FF00000) != 0x7FF00000;
-                    if (g == 0 && real) wcert[wv][j] = ok ? (float)(sqrt(L2) * (1.0 - 2e-7)) : 0.f;  // (over phase 1's entry; this lane reads it back in phase 6)
+                    if (g == 0 && real) wcert[wv][j] = ok ? cert_bound(L2) : 0.f;  // (over phase 1's entry; this lane reads it back in phase 6)
                 }
             }
             if (tid == 0) PEDP_STAMP(1, blockIdx.x, 3);
@@ -813,12 +797,8 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                 ++nfb_w;
                 const double sx64 = wp[wv][0][s], sy64 = wp[wv][1][s], sz64 = wp[wv][2][s];
                 const float sx = wcs[wv][0][s], sy = wcs[wv][1][s], sz = wcs[wv][2][s], rho_s = wrho[wv][s];
-                const float slack = 1e-5f * (fabsf(sx) + fabsf(sy) + fabsf(sz)) + 1e-6f;  // fp32 rounding of the centred point
-                auto near_pt = [&](const float4 &ts) -> bool {
-                    const float dx = ts.x - sx, dy = ts.y - sy, dz = ts.z - sz;
-                    const float lim = rho_s + ts.w + slack;
-                    return !((dx * dx + dy * dy + dz * dz) > lim * lim * 1.00001f + 1e-6f) && ts.w >= 0.f;
-                };
+                const float slack = point_slack(sx, sy, sz);
+                auto near_pt = [&](const float4 &ts) -> bool { return sphere_near_slot(ts, sx, sy, sz, rho_s, slack); };
                 double xd = dinf;
                 int xj = 0x7FFFFFFF;
                 for (int R = 0; R * 64 < a.n_words; ++R) {
@@ -880,6 +860,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
                     }
                     if (g == 0) { Tp_out[3 * kp] = tx; Tp_out[3 * kp + 1] = ty; Tp_out[3 * kp + 2] = tz; }
                     // entry k of the packet goes to lane group g = k % 4, accumulator k / 4
+                    // (icp_steady_kernel has a copy of these entries, steady_pass.h: keep the two alike)
 #define PEDP_PUT(K, V)                                   \
     do {                                                 \
         const double v_ = (V);                           \

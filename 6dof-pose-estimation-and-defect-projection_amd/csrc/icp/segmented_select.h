@@ -130,7 +130,7 @@ __global__ __launch_bounds__(FB_WAVES * 64) void nn_fallback_kernel(const IcpSta
         const unsigned long long *mw = mask + (size_t)(kk >> 7) * n_words;
         const double px = P[3 * (int64_t)i], py = P[3 * (int64_t)i + 1], pz = P[3 * (int64_t)i + 2];
         const float sx = (float)(px - cx), sy = (float)(py - cy), sz = (float)(pz - cz);
-        const float slack = 1e-5f * (fabsf(sx) + fabsf(sy) + fabsf(sz)) + 1e-6f;  // fp32 rounding of the centred point
+        const float slack = point_slack(sx, sy, sz);
         double bd = __longlong_as_double(0x7FF0000000000000ll);
         int bj = 0x7FFFFFFF;
         for (int wi = wave; wi < n_words; wi += FB_WAVES) {
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(FB_WAVES * 64) void nn_fallback_kernel(const IcpSta
                 const float4 ts = tile_sph[wi * 64 + lane];
                 const float dx = ts.x - sx, dy = ts.y - sy, dz = ts.z - sz;
                 const float lim = r_search + ts.w + slack;
-                keep = !((dx * dx + dy * dy + dz * dz) > lim * lim * 1.00001f + 1e-6f);
+                keep = !offset_beyond(dx, dy, dz, lim);
             }
             unsigned long long near = __builtin_amdgcn_ballot_w64(keep);
             while (near != 0ull) {  // wave-uniform: 64 lanes = 64 rows = 64 / (16 QT) units per trip

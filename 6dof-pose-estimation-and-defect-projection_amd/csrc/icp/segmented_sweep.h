@@ -2,6 +2,7 @@
 // segment table and the two MFMA sweeps (f32 and bf16 operands).
 #pragma once
 #include "common.h"
+#include "slot_math.h"
 
 namespace {
 
@@ -35,7 +36,7 @@ __device__ __forceinline__ PackPoint pack_one(const IcpState *__restrict__ st, i
     double nz = dadd(dadd(dadd(dmul(M[8], x), dmul(M[9], y)), dmul(M[10], z)), M[11]);
     P[3 * i] = nx; P[3 * i + 1] = ny; P[3 * i + 2] = nz;
     double ex = fmax(fmax(lox - nx, nx - hix), 0.0), ey = fmax(fmax(loy - ny, ny - hiy), 0.0),
-           ez = fmax(fmax(loz - nz, nz - hiz), 0.0);
+           ez = fmax(fmax(loz - nz, nz - hiz), 0.0);  // (box_dist2 of slot_math.h)
     o.cand = (ex * ex + ey * ey + ez * ez) <= r2cut;  // r2cut = r^2 (1 + 1e-12): rounding-safe
     o.i = (int)i;
     o.sx = (float)(nx - st->centroid[0]); o.sy = (float)(ny - st->centroid[1]); o.sz = (float)(nz - st->centroid[2]);
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(256) void nn_cull_kernel(const IcpState *__restrict
         for (int sb = 0; sb < NN_SB; ++sb) {
             const float dx = ts.x - bs[sb].x, dy = ts.y - bs[sb].y, dz = ts.z - bs[sb].z;
             const float lim = r_search + bs[sb].w + ts.w;
-            keep |= (bs[sb].w >= 0.f) & !((dx * dx + dy * dy + dz * dz) > lim * lim * 1.00001f + 1e-6f);
+            keep |= (bs[sb].w >= 0.f) & !offset_beyond(dx, dy, dz, lim);
         }
         keep = keep && (t < n_tiles) && (ts.w >= 0.f);
         const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);

@@ -112,19 +112,6 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
     const bool planned = a0.visit != nullptr && n_live <= G && vis[2] == uni(cur.nonce) + a0.launch + 1 && vis[3] == n_live;
     const double dinf = __longlong_as_double(0x7FF0000000000000ll);
     const double dnan = __longlong_as_double(0x7FF8000000000000ll);
-    auto store_nan = [](PEDP_GLOBAL double *p) {  // (see icp_pass_kernel)
-        int z = 0;
-        asm volatile("" : "+v"(z));
-        typedef int v2i_ __attribute__((ext_vector_type(2)));
-        const v2i_ w = {z, 0x7FF80000 | z};
-        *(PEDP_GLOBAL v2i_ *)p = w;
-    };
-    auto lds_nan = [](double *p) {  // "no neighbour", as two integer words (this file is built with -fno-honor-nans)
-        int z = 0;
-        asm volatile("" : "+v"(z));
-        ((int *)p)[0] = z;
-        ((int *)p)[1] = 0x7FF80000 | z;
-    };
     // The device-wide hand-over.  Arrivals so far in this launch: the first counts the whole grid, the others the ranks.
     unsigned arrivals = 0u;
     int handovers = 0;
@@ -279,14 +266,11 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
                     d2prev = dist2(x, y, z, ux, uy, uz);
                     dprev = sqrt(d2prev);
                     const double m = sqrt(dist2(x, y, z, x0, y0, z0));
-                    c_new = (float)(((double)c_in - m * (1.0 + 1e-12)) * (1.0 - 2e-7));
-                    const bool fin_ = (__double2hiint(d2prev) & 0x7FF00000) != 0x7FF00000 && (__double2hiint(m) & 0x7FF00000) != 0x7FF00000 &&
-                                      (__float_as_int(c_new) & 0x7F800000) != 0x7F800000;
-                    certd = fin_ && jprev >= 0 && c_new > 0.f && dprev * (1.0 + 1e-12) < (double)c_new;
+                    c_new = cert_moved(c_in, m);
+                    const bool fin_ = cert_finite(d2prev, m, c_new);
+                    certd = fin_ && jprev >= 0 && c_new > 0.f && cert_inside(dprev, c_new);
                     if (!certd) c_new = 0.f;
-                    const double ex = fmax(fmax(a.lo[0] - x, x - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - y, y - a.hi[1]), 0.0),
-                                 ez = fmax(fmax(a.lo[2] - z, z - a.hi[2]), 0.0);
-                    const double d2box = ex * ex + ey * ey + ez * ez;
+                    const double d2box = box_dist2(x, y, z, a.lo, a.hi);
                     cand = d2box <= bcast0(cur.r2cut);
                 }
                 const unsigned long long mc = __builtin_amdgcn_ballot_w64(cand);
@@ -310,7 +294,7 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
                     wp[wv][0][sl] = x; wp[wv][1][sl] = y; wp[wv][2][sl] = z;
                     wcs[wv][0][sl] = sx; wcs[wv][1][sl] = sy; wcs[wv][2][sl] = sz;
                     // the slot's search radius, as a searching slot of icp_pass_kernel gets it under certificates
-                    const float rp = PEDP_ICP_KAPPA * ((float)dprev * 1.00001f) + 1e-5f * s1 + 1e-6f;
+                    const float rp = slot_radius_kappa(dprev, s1);
                     const float r_search = unif(cur.r_search);
                     wrho[wv][sl] = rp < r_search ? rp : r_search;
                 }
@@ -330,12 +314,8 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
                 amb &= amb - 1u;
                 const double sx64 = wp[wv][0][s], sy64 = wp[wv][1][s], sz64 = wp[wv][2][s];
                 const float sx = wcs[wv][0][s], sy = wcs[wv][1][s], sz = wcs[wv][2][s], rho_s = wrho[wv][s];
-                const float slack = 1e-5f * (fabsf(sx) + fabsf(sy) + fabsf(sz)) + 1e-6f;  // fp32 rounding of the centred point
-                auto near_pt = [&](const float4 &ts) -> bool {
-                    const float dx = ts.x - sx, dy = ts.y - sy, dz = ts.z - sz;
-                    const float lim = rho_s + ts.w + slack;
-                    return !((dx * dx + dy * dy + dz * dz) > lim * lim * 1.00001f + 1e-6f) && ts.w >= 0.f;
-                };
+                const float slack = point_slack(sx, sy, sz);
+                auto near_pt = [&](const float4 &ts) -> bool { return sphere_near_slot(ts, sx, sy, sz, rho_s, slack); };
                 double xd = dinf, x2 = dinf;  // smallest and second smallest exact d^2 this lane has seen (ties counted)
                 int xj = 0x7FFFFFFF;
                 for (int R = 0; R * 64 < a.n_words; ++R) {
@@ -348,7 +328,8 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
                         const int tile = word * 64 + lane;
                         const float4 ts = gload4(a.tile_sph + (tile < a.n_tiles ? tile : 0));
                         unsigned long long near = __builtin_amdgcn_ballot_w64(tile < a.n_tiles && near_pt(ts));
-                        while (near != 0ull) {  // wave-uniform: 64 lanes = 64 rows = 4 tiles per trip (scan_near_tiles)
+                        // (fused_pass.h's scan_near_tiles, with the second-smallest d^2 tracked: keep the two alike)
+                        while (near != 0ull) {  // wave-uniform: 64 lanes = 64 rows = 4 tiles per trip
                             int t = -1;
 #pragma unroll
                             for (int gg = 0; gg < 4; ++gg) {
@@ -385,12 +366,12 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
                     fj = found ? xj : -1;
                     // the certificate the slot leaves: every target point but the winner is farther than rho (less the rounding
                     // allowance rho carries) or was scanned, and the best of those behind the winner is x2
-                    const double rho = (double)rho_s * (1.0 - 2e-5) - (double)slack * 1.000001;
+                    const double rho = cert_rho(rho_s, slack);
                     const double Le = x2 * (1.0 - 1e-12);
                     double L2 = rho * rho;
                     L2 = Le < L2 ? Le : L2;
                     const bool ok = found && rho > 0.0 && L2 > 0.0 && (__double2hiint(L2) & 0x7FF00000) != 0x7FF00000;
-                    if (g == 0) wcert[wv][s] = ok ? (float)(sqrt(L2) * (1.0 - 2e-7)) : 0.f;
+                    if (g == 0) wcert[wv][s] = ok ? cert_bound(L2) : 0.f;
                 }
             }
             // ---- 6. the sub-block's partial sums (icp_pass_kernel's phase 6; neighbour and normal by index)
@@ -436,6 +417,7 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
                                 rN[0][pos] = nx; rN[1][pos] = ny; rN[2][pos] = nz;
                             }
                         }
+                        // (the packet entries of icp_pass_kernel's phase 6, fused_pass.h: keep the two alike)
 #define PEDP_PUT(K, V)                                   \
     do {                                                 \
         const double v_ = (V);                           \

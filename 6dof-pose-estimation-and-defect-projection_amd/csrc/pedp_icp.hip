@@ -44,6 +44,7 @@
 //                            tile_sphere_kernel
 //   icp/target_order.h       the compact row order of a target pack: tord_init_kernel, tord_block_box_kernel,
 //                            tord_key_kernel, tord_leaf_kernel
+//   icp/slot_math.h          what several kernels must compute alike: candidate tests, search radii, the certificate's steps
 //   icp/segmented_sweep.h    icp_transform_pack_kernel, nn_cull_kernel, nn_segment_kernel, nn_sweep_kernel,
 //                            pack_target_bf16_kernel, nn_sweep_bf16_kernel, nn_bf16_debug_kernel
 //   icp/segmented_select.h   nn_select_kernel, nn_fallback_kernel, icp_accumulate_kernel, icp_reduce_kernel
@@ -54,6 +55,8 @@
 //   icp/fused_pass.h         sweep_sub_block, icp_pass_kernel, batch_state_scatter_kernel, batch_state_gather_kernel,
 //                            icp_state_start_kernel
 //   icp/steady_pass.h        icp_steady_kernel: fully certified passes of a single registration in one resident launch
+// Host side, here: icp_switches (the one reader of the environment), icp_decide_path (the one decision of a registration's
+// way), then workspace, enqueue, stage / start / collect, the graph and batch forms and the C entry points.
 #include "pedp_internal.h"
 #include <atomic>
 #include <cmath>
@@ -97,6 +100,7 @@ struct IcpWorkspace {
     IcpState *st;
     double *P, *d2, *partials, *packet, *trace;
     float4 *B, *blk_sph;
+    pedp_cloud_t source, target;                      // the pair of clouds it works on (bind_clouds), and its view of them:
     const float4 *tgt4, *tile_sph;
     const int32_t *src_perm, *tgt_perm;
     float *eps, *S;
@@ -110,7 +114,6 @@ struct IcpWorkspace {
     int n_words, max_segs;
     int qt;  // MFMA tiles per target unit for this call (1: culled registration, 4: dense sweep)
     // fused pass (qt == 1 inside a registration)
-    bool fused;
     double *Pk, *hist, *cpart, *Tprev;
     float *cert;   // certificates, two copies by pass parity (see PassArgs)
     unsigned *ticket;
@@ -133,7 +136,6 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
                     int poses = 1) {
     w = IcpWorkspace{};  // (what a path does not use stays null)
     w.qt = qt;
-    w.fused = fused;
     w.Ns_pad = (int64_t)align_up((size_t)(Ns > 0 ? Ns : 1), NN_PTS_PER_WG);
     w.Nt_pad = (int64_t)align_up((size_t)(Nt > 0 ? Nt : 1), 16 * NN_TU);
     w.blocks_cap = w.Ns_pad / (NN_SB * 16) + 1;
@@ -233,6 +235,7 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
 //
 // The ticket with the sign-off counters, then both live masks:
 inline size_t zeroed_span_bytes(const IcpWorkspace &w) {
+    if (!w.ticket) return 0;  // (segmented path)
     const unsigned long long *end = w.live + 2 * (size_t)w.n_lw;
     return (size_t)((const char *)end - (const char *)w.ticket);
 }
@@ -246,6 +249,8 @@ inline size_t plan_span_bytes(const IcpWorkspace &w) {
 // A workspace's view of the pair of clouds it works on: the target's sorted operand with the spheres of its units
 // (qt tiles each) and of its mask words, its sorted rows, and both spatial orders.
 void bind_clouds(IcpWorkspace &w, pedp_cloud_t source, pedp_cloud_t target, int qt) {
+    w.source = source;
+    w.target = target;
     w.tgt4 = (const float4 *)target->tgt4;
     w.word_sph = (const float4 *)target->tile_sphw;
     w.tgt_s = (const double *)target->tgt_s;
@@ -272,69 +277,55 @@ inline IcpRadii icp_radii(double r, double r_cull) {
     return k;
 }
 
-// An environment switch: set, and to something other than 0.  (The switches below each ask once per process.)
-inline bool env_flag(const char *name, bool unset = false) {
-    const char *v = getenv(name);
-    return v ? atoi(v) != 0 : unset;
-}
-inline bool nn_bf16_sweep() {  // PEDP_NN_F32=1: the dense sweep on the f32-input MFMA (A/B, tests)
-    static const bool off = env_flag("PEDP_NN_F32");
-    return !off;
-}
-// Test hook (tests/test_icp_gpu.py): PEDP_ICP_UNFUSED_FINISH=1 closes every pass with a launch of
-// icp_finish_kernel instead of the in-launch hand-over -- the results must not differ in any bit.
-inline bool unfused_finish() {
-    static const bool m = env_flag("PEDP_ICP_UNFUSED_FINISH");
-    return m;
-}
-inline bool no_visit_plan() {  // PEDP_ICP_NO_VISIT_PLAN=1: every workgroup takes the live chunk of its own index (tests compare the two)
-    static const bool m = env_flag("PEDP_ICP_NO_VISIT_PLAN");
-    return m;
-}
-// PEDP_ICP_SERIAL_CLOSE=1: the close of a pass as it was -- the sign-off counters looked at only after the sums, and
-// everything behind them on one lane (A/B timing; tests compare the two bit for bit)
-inline bool serial_close() {
-    static const bool m = env_flag("PEDP_ICP_SERIAL_CLOSE");
-    return m;
-}
-// PEDP_ICP_COPY_BRACKET=1: a single registration bracketed as it was -- a host-to-device copy of the state and a fill
-// in front of pass 0, a device-to-host copy of the state behind the last pass -- instead of icp_state_start_kernel
-// and the closing workgroup's own write of the final state
-inline bool copy_bracket() {
-    static const bool m = env_flag("PEDP_ICP_COPY_BRACKET");
-    return m;
+// Every environment switch this file reads (include/pedp.h: pedp_icp_switches), asked once per process.  Each restores
+// an earlier behaviour so that tests and A/B runs can compare the two sides bit for bit.
+using IcpSwitches = pedp_icp_switches;
+inline const IcpSwitches &icp_switches() {
+    static const IcpSwitches sw = [] {
+        auto flag = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) != 0 : unset; };
+        auto num = [](const char *name, int unset) { const char *v = getenv(name); return v && *v ? atoi(v) : unset; };
+        const char *order = getenv("PEDP_ICP_TARGET_ORDER");
+        IcpSwitches s;
+        s.nn_f32 = flag("PEDP_NN_F32", 0); s.unfused_finish = flag("PEDP_ICP_UNFUSED_FINISH", 0);
+        s.no_visit_plan = flag("PEDP_ICP_NO_VISIT_PLAN", 0); s.serial_close = flag("PEDP_ICP_SERIAL_CLOSE", 0);
+        s.copy_bracket = flag("PEDP_ICP_COPY_BRACKET", 0); s.head_close = flag("PEDP_ICP_HEAD_CLOSE", 1);
+        s.cert = flag("PEDP_ICP_CERT", 1); s.steady = flag("PEDP_ICP_STEADY", 1);
+        s.steady_from = num("PEDP_ICP_STEADY_FROM", 5); s.steady_grid = num("PEDP_ICP_STEADY_GRID", 0);
+        s.target_order = order && !strcmp(order, "hilbert") ? PEDP_TARGET_ORDER_HILBERT
+                         : order && !strcmp(order, "compact") ? PEDP_TARGET_ORDER_COMPACT : PEDP_TARGET_ORDER_AUTO;
+        return s;
+    }();
+    return sw;
 }
 
-// PEDP_ICP_HEAD_CLOSE=0: every pass is closed inside its own launch again.  (Default: a single registration on the fused
-// path, with the wide close and the final state written by the device, leaves its steady passes open; the next launch
-// closes them at its head, see fused_close.h.)
-inline bool head_close() {
-    static const bool m = env_flag("PEDP_ICP_HEAD_CLOSE", true);
-    return m;
+// What is decided for a registration (or a group of a fused batch) before anything is enqueued (include/pedp.h): everything
+// the host code and the kernels' arguments branch on follows from these fields; no switch is read anywhere else.
+using IcpPath = pedp_icp_path;
+using IcpPathInputs = pedp_icp_path_inputs;
+// the fused pass lists a target's mask words in LDS: up to BK_WCAP words of 1024 rows
+inline bool fused_eligible(int qt, bool exhaustive, double r, int64_t Ns, int64_t Nt) {
+    return qt == 1 && !exhaustive && r > 0.0 && Ns > 0 && Nt > 0 && (Nt + 1023) / 1024 <= BK_WCAP;
 }
-// PEDP_ICP_CERT=0: every candidate slot searches in every pass again, within the distance to last pass's neighbour.
-// (Default: a single registration that closes its passes itself keeps a certificate per scene point and skips the search
-// of a wave whose slots' neighbours are proven unchanged; a slot that searches does so within KAPPA times that distance.)
-inline bool icp_certificates() {
-    static const bool m = env_flag("PEDP_ICP_CERT", true);
-    return m;
+// Pure: no HIP call, no global.
+inline IcpPath icp_decide_path(const IcpSwitches &sw, const IcpPathInputs &in) {
+    IcpPath p{};
+    p.fused = fused_eligible(in.unit_size, in.exhaustive, in.radius, in.n_source, in.n_target);
+    p.copy_bracket = sw.copy_bracket; p.exchange = in.exchange;  // (the segmented path has both, too)
+    p.steady_from = sw.steady_from < 1 ? 1 : sw.steady_from;
+    if (!p.fused) return p;
+    const bool single = in.poses <= 1;
+    const bool closes_itself = !in.exchange && !sw.unfused_finish;  // the workgroup that finishes last closes the pass
+    p.serial_close = sw.serial_close; p.unfused_finish = sw.unfused_finish;
+    p.plan = single && !sw.no_visit_plan;  // (a batch fills every CU several times over anyway)
+    p.certify = single && closes_itself && sw.cert;
+    p.dev_result = single && !in.batch && closes_itself && !sw.copy_bracket;
+    p.head = p.dev_result && !sw.serial_close && sw.head_close;
+    // (a pass timed on its own, or every fourth one, is a launch of its own; -3 times the whole registration)
+    p.steady = p.head && p.certify && sw.steady && !in.no_steady && !in.early_exit && (in.timed_pass == -1 || in.timed_pass == -3) &&
+               in.resident;
+    return p;
 }
 
-// PEDP_ICP_STEADY=0: every pass of a single registration is a launch of icp_pass_kernel again.  (Default: a registration
-// that closes its passes at the head of the next launch and keeps certificates runs its passes from PEDP_ICP_STEADY_FROM on,
-// default 5, in ONE launch of icp_steady_kernel, steady_pass.h.)
-inline bool icp_steady() {
-    static const bool m = env_flag("PEDP_ICP_STEADY", true);
-    return m;
-}
-inline int env_int(const char *name, int unset) {
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : unset;
-}
-inline int steady_from() {
-    static const int f = env_int("PEDP_ICP_STEADY_FROM", 5);
-    return f < 1 ? 1 : f;
-}
 // Workgroups of a steady launch: all of them must be resident at once, so the grid is what the runtime says fits --
 // hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs -- and at most two per CU.  PEDP_ICP_STEADY_GRID=n caps it (tests: several
 // chunks per workgroup at a few hundred points).  0: the kernel cannot be resident -- the registration keeps to generic launches.
@@ -349,7 +340,7 @@ inline int steady_grid(pedp_ctx_t c) {
     }
     if (n < 1) return 0;
     int64_t g = (int64_t)(n < 2 ? n : 2) * c->num_cus;
-    static const int cap = env_int("PEDP_ICP_STEADY_GRID", 0);
+    const int cap = icp_switches().steady_grid;
     if (cap > 0 && g > cap) g = cap;
     return (int)g;
 }
@@ -366,24 +357,24 @@ inline bool steady_acquire(int device) {
 }
 inline void steady_release(int device) { steady_busy(device).store(0, std::memory_order_release); }
 
-// Enqueue one correspondence pass (transform, sweep, fallback).  mode as in
+// Enqueue one correspondence pass (transform, sweep, fallback) between the workspace's clouds.  mode as in
 // icp_transform_pack_kernel.
-int enqueue_nn_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_cloud_t tgt, int mode,
-                    const TargetPrep &tp, double r, hipEvent_t ev0, hipEvent_t ev1, bool exhaustive = false) {
+int enqueue_nn_pass(pedp_ctx_t c, const IcpWorkspace &w, int mode, const TargetPrep &tp, double r, hipEvent_t ev0, hipEvent_t ev1,
+                    bool exhaustive) {
+    const pedp_cloud_t src = w.source, tgt = w.target;
     const int64_t Ns = src->N, Nt = target_rows(tgt);
     // exhaustive: the box test and the sphere culling use an infinite radius (every point is a
     // candidate, every mask bit is set); the selection still applies r, so results do not change
     const IcpRadii rad = icp_radii(r, exhaustive ? 1e18 : r);
-    const float r1 = rad.r1, r_search = rad.r_search, r2f = rad.r2f;
-    const double r2cut = rad.r2cut;
+    const float r_search = rad.r_search, r2f = rad.r2f;
     const int n_tiles = (int)(w.Nt_pad / (16 * w.qt));  // target units
     // the dense sweep (units of four tiles) runs on the bf16 matrix pipe (PEDP_NN_F32=1: the f32-input MFMA of rounds 1-3)
-    const bool bf16_sweep = w.qt == 4 && nn_bf16_sweep() && tgt->tgt_bf != nullptr;
+    const bool bf16_sweep = w.qt == 4 && !icp_switches().nn_f32 && tgt->tgt_bf != nullptr;
     {
         int64_t grid = (Ns + 511) / 512;  // 128 points per wave, 4 waves per workgroup
         hipLaunchKernelGGL(icp_transform_pack_kernel, dim3((unsigned)grid), dim3(256), 0, c->stream, w.st, mode,
                            src->pts, w.P, w.src_perm, Ns, w.B, w.eps, w.S, w.list, w.blk_sph, w.idx, w.d2, tp.Tn, tp.T2,
-                           r1, r2cut, tp.lo[0], tp.lo[1], tp.lo[2], tp.hi[0], tp.hi[1], tp.hi[2], bf16_sweep ? 34.0f : 5.0f);
+                           rad.r1, rad.r2cut, tp.lo[0], tp.lo[1], tp.lo[2], tp.hi[0], tp.hi[1], tp.hi[2], bf16_sweep ? 34.0f : 5.0f);
     }
     const unsigned sel_grid = (unsigned)((4 * w.Ns_pad + 255) / 256);
     const unsigned sweep_grid = (unsigned)((w.max_segs + NN_WAVES - 1) / NN_WAVES);
@@ -400,12 +391,11 @@ int enqueue_nn_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_
         hipLaunchKernelGGL(nn_segment_kernel, dim3(1), dim3(1024), 0, c->stream, w.st, w.blk_cnt, w.blk_segstart,
                            w.seg_blk, w.seg_rank0, w.seg_n, w.max_segs, SEG_MIN_TILES / w.qt, NN_LIST_TILES / w.qt);
     }
-#define PEDP_NN_STAGE(QTV, GV)                                                                                          \
+#define PEDP_NN_STAGE(QTV, SWEEP, TGT_OPERAND, B_OPERAND)                                                               \
     do {                                                                                                              \
         if (ev0) PEDP_HIP_CHECK(hipEventRecord(ev0, c->stream));                                                      \
-        hipLaunchKernelGGL((nn_sweep_kernel<QTV, GV>), dim3(sweep_grid), dim3(NN_WAVES * 64), 0, c->stream, w.st,            \
-                           (const float *)w.tgt4, n_tiles, w.n_words, w.mask, w.seg_blk, w.seg_rank0, w.seg_n,         \
-                           (const float *)w.B, w.tr_b1, w.tr_t1, w.tr_b2);                                            \
+        hipLaunchKernelGGL(SWEEP, dim3(sweep_grid), dim3(NN_WAVES * 64), 0, c->stream, w.st, TGT_OPERAND, n_tiles,     \
+                           w.n_words, w.mask, w.seg_blk, w.seg_rank0, w.seg_n, B_OPERAND, w.tr_b1, w.tr_t1, w.tr_b2);  \
         if (ev1) { PEDP_HIP_CHECK(hipEventRecord(ev1, c->stream)); c->nn_timed = true; }                               \
         hipLaunchKernelGGL(nn_select_kernel<QTV>, dim3(sel_grid), dim3(256), 0, c->stream, w.st, w.blk_segstart,       \
                            w.tr_b1, w.tr_t1, w.tr_b2, tgt->pts, w.tgt_perm, Nt, w.P, w.eps, w.S, w.list, r2f, w.idx,   \
@@ -413,19 +403,9 @@ int enqueue_nn_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_
         hipLaunchKernelGGL(nn_fallback_kernel<QTV>, dim3(fb_grid), dim3(FB_WAVES * 64), 0, c->stream, w.st, w.fb, w.list,     \
                            w.mask, w.n_words, w.tile_sph, r_search, tgt->pts, w.tgt_perm, Nt, w.P, w.idx, w.d2);       \
     } while (0)
-    if (bf16_sweep) {
-        if (ev0) PEDP_HIP_CHECK(hipEventRecord(ev0, c->stream));
-        hipLaunchKernelGGL((nn_sweep_bf16_kernel<4, 2>), dim3(sweep_grid), dim3(NN_WAVES * 64), 0, c->stream, w.st,
-                           (const uint4 *)tgt->tgt_bf, n_tiles, w.n_words, w.mask, w.seg_blk, w.seg_rank0, w.seg_n,
-                           (const float4 *)w.B, w.tr_b1, w.tr_t1, w.tr_b2);
-        if (ev1) { PEDP_HIP_CHECK(hipEventRecord(ev1, c->stream)); c->nn_timed = true; }
-        hipLaunchKernelGGL(nn_select_kernel<4>, dim3(sel_grid), dim3(256), 0, c->stream, w.st, w.blk_segstart,
-                           w.tr_b1, w.tr_t1, w.tr_b2, tgt->pts, w.tgt_perm, Nt, w.P, w.eps, w.S, w.list, r2f, w.idx,
-                           w.d2, w.fb);
-        hipLaunchKernelGGL(nn_fallback_kernel<4>, dim3(fb_grid), dim3(FB_WAVES * 64), 0, c->stream, w.st, w.fb, w.list,
-                           w.mask, w.n_words, w.tile_sph, r_search, tgt->pts, w.tgt_perm, Nt, w.P, w.idx, w.d2);
-    } else if (w.qt == 4) PEDP_NN_STAGE(4, 2);
-    else PEDP_NN_STAGE(1, 4);
+    if (bf16_sweep) PEDP_NN_STAGE(4, (nn_sweep_bf16_kernel<4, 2>), (const uint4 *)tgt->tgt_bf, (const float4 *)w.B);
+    else if (w.qt == 4) PEDP_NN_STAGE(4, (nn_sweep_kernel<4, 2>), (const float *)w.tgt4, (const float *)w.B);
+    else PEDP_NN_STAGE(1, (nn_sweep_kernel<1, 4>), (const float *)w.tgt4, (const float *)w.B);
 #undef PEDP_NN_STAGE
     PEDP_HIP_CHECK(hipGetLastError());
     return PEDP_OK;
@@ -434,57 +414,87 @@ int enqueue_nn_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_
 // Margin of the live set beyond the correspondence radius (see the fused-pass comment).
 inline double fused_margin(double r) { return 2.0 * r; }   // (1 r ... 4 r measured on the bench registration: 0.702-0.720 ms, no trend; any margin > 0 is exact)
 
-// Enqueue the kernel of a fused pass.  fuse: the workgroup that finishes last closes the pass
-// (sum, solve, update); otherwise icp_finish_kernel launches follow (exchange step in between).
-int enqueue_fused_pass(pedp_ctx_t c, const IcpWorkspace &w, pedp_cloud_t src, pedp_cloud_t tgt, int estimator,
-                       const TargetPrep &tp, hipEvent_t ev0, hipEvent_t ev1, bool fuse, double *trace, int poses = 1,
-                       unsigned long long *down = nullptr, int head_launch = -1, bool steady = false) {
-    PassArgs pa;
-    pa.src = src->pts; pa.perm = w.src_perm; pa.N = src->N; pa.n_chunks = w.n_chunks;
+// One registration = enqueue (all passes, on the executor's stream and workspace) + collect
+// (one synchronisation, results to the host).  The executor is the clouds' own context for
+// pedp_icp and one of its sub-contexts (own stream + workspace) for pedp_icp_batched, where
+// several registrations are in flight at once.  A group of a fused batch is a job, too.
+struct IcpJob {
+    IcpWorkspace w;
+    int max_iter = 0;
+    IcpPathInputs in{};  // the registration's shape ...
+    IcpPath path{};      // ... and what is decided from it, once, when the job is staged
+    // holds the device's steady launch until collected: the passes from path.steady_from on run in icp_steady_kernel
+    bool steady_held = false;
+    TargetPrep tp{};
+    int estimator = 0;
+    bool want_trace = false;
+    PassArgs pa{};  // fused path: what a pass kernel's arguments have in common over the job's launches (stage_pass_args)
+};
+constexpr size_t RESULT_OFF = 2048;
+static_assert(sizeof(IcpState) <= RESULT_OFF && sizeof(IcpState) % 8 == 0, "start and final state share the block's first 4 KB, as 8-byte words");
+
+// The arguments of the job's pass kernels, from its workspace, clouds and path: filled once, copied per launch.
+void stage_pass_args(pedp_ctx_t x, IcpJob &job) {
+    const IcpWorkspace &w = job.w;
+    const IcpPath &path = job.path;
+    PassArgs &pa = job.pa;
+    pa.src = w.source->pts; pa.perm = w.src_perm; pa.N = w.source->N; pa.n_chunks = w.n_chunks;
     pa.hist = w.hist; pa.Pk = w.Pk; pa.Tprev = w.Tprev; pa.live = w.live; pa.live_list = w.live_list;
-    pa.chunk_sph = (const double *)src->chunk_sph;
+    pa.chunk_sph = (const double *)w.source->chunk_sph;
     pa.pp_stride = 3 * (size_t)w.Ns_pad;
     pa.tgtf = (const float *)w.tgt4; pa.n_tiles = (int)(w.Nt_pad / 16); pa.n_words = w.n_words;
-    pa.tile_sph = w.tile_sph; pa.word_sph = w.word_sph; pa.tgt_s = w.tgt_s; pa.tperm = w.tgt_perm; pa.Nt = target_rows(tgt);
-    pa.tgt = tgt->pts; pa.nrm = tgt->normals;
-    pa.Tn = tp.Tn; pa.T2 = tp.T2;
-    for (int k = 0; k < 3; ++k) { pa.lo[k] = tp.lo[k]; pa.hi[k] = tp.hi[k]; pa.bc[k] = tp.bc[k]; }
-    pa.estimator = estimator; pa.idx_out = w.idx; pa.partials = w.cpart;
-    pa.pose_stride = poses > 1 ? w.pose_stride : 0;
-    pa.fuse = fuse && !unfused_finish() ? 1 : 0; pa.n_lw = w.n_lw; pa.packet = w.packet; pa.trace = trace; pa.ticket = w.ticket;
-    const bool plan = poses <= 1 && !no_visit_plan();
-    pa.down = poses <= 1 && pa.fuse ? down : nullptr; pa.serial_close = serial_close() ? 1 : 0;
-    // head close: the launch index, and one workgroup more than the chunks can fill (the service workgroup)
-    pa.head = head_launch >= 0 ? 1 : 0; pa.launch = pa.head ? head_launch : 0;
+    pa.tile_sph = w.tile_sph; pa.word_sph = w.word_sph; pa.tgt_s = w.tgt_s; pa.tperm = w.tgt_perm; pa.Nt = target_rows(w.target);
+    pa.tgt = w.target->pts; pa.nrm = w.target->normals;
+    pa.Tn = job.tp.Tn; pa.T2 = job.tp.T2;
+    for (int k = 0; k < 3; ++k) { pa.lo[k] = job.tp.lo[k]; pa.hi[k] = job.tp.hi[k]; pa.bc[k] = job.tp.bc[k]; }
+    pa.estimator = job.estimator; pa.idx_out = w.idx; pa.partials = w.cpart;
+    pa.pose_stride = job.in.poses > 1 ? w.pose_stride : 0;
+    // the workgroup that finishes last closes the pass (sum, solve, update); otherwise icp_finish_kernel launches follow
+    pa.fuse = !path.exchange && !path.unfused_finish ? 1 : 0;
+    pa.n_lw = w.n_lw; pa.packet = w.packet; pa.trace = job.want_trace ? w.trace : nullptr; pa.ticket = w.ticket;
+    pa.down = path.dev_result ? (unsigned long long *)((char *)x->pinned + RESULT_OFF) : nullptr;
+    pa.serial_close = path.serial_close; pa.head = path.head; pa.launch = 0;  // (the launch index is the launch's own)
     pa.part_stride = (size_t)PSTRIDE * (size_t)w.blocks_cap;
-    // (batches, passes closed by icp_finish_kernel and the exchange step never certify)
-    pa.cert = poses <= 1 && pa.fuse && icp_certificates() ? w.cert : nullptr; pa.cert_stride = (size_t)w.Ns_pad;
-    pa.visit = plan ? w.visit : nullptr; pa.dur = plan ? w.dur : nullptr; pa.visit_cap = w.visit_cap; pa.n_cu = c->num_cus;
+    pa.cert = path.certify ? w.cert : nullptr; pa.cert_stride = (size_t)w.Ns_pad;
+    pa.visit = path.plan ? w.visit : nullptr; pa.dur = path.plan ? w.dur : nullptr; pa.visit_cap = w.visit_cap; pa.n_cu = x->num_cus;
+}
+
+// What one launch of a fused pass has of its own.
+struct PassLaunch {
+    int pass = 0;                // head close: the index of this launch = the pass it runs
+    bool steady_launch = false;  // `pass` and every pass behind it that is fully certified, in one resident launch (steady_pass.h)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the launch (null: not timed)
+};
+
+// Enqueue the kernel of a fused pass of the job.
+int enqueue_fused_pass(pedp_ctx_t c, const IcpJob &job, const PassLaunch &l) {
+    PassArgs pa = job.pa;
+    pa.launch = pa.head ? l.pass : 0;
     // grid-stride loop over the live chunks: any grid is correct; two workgroups per CU are resident
-    int64_t g = w.n_chunks;
+    int64_t g = job.w.n_chunks;
     if (g > 2 * c->num_cus) g = 2 * c->num_cus;
     if (g < 1) g = 1;
-    if (pa.head) g += 1;
-    if (ev0) PEDP_HIP_CHECK(hipEventRecord(ev0, c->stream));
-    if (steady)  // head_launch and every pass behind it that is fully certified, in one resident launch (steady_pass.h)
-        hipLaunchKernelGGL(icp_steady_kernel, dim3((unsigned)steady_grid(c)), dim3(BK_W * 64), 0, c->stream, w.st, pa);
-    else if (poses > 1)
-        hipLaunchKernelGGL((icp_pass_kernel<BK_W, true>), dim3((unsigned)g, (unsigned)poses), dim3(BK_W * 64), 0, c->stream, w.st, pa);
+    if (pa.head) g += 1;  // head close: one workgroup more than the chunks can fill (the service workgroup)
+    if (l.ev0) PEDP_HIP_CHECK(hipEventRecord(l.ev0, c->stream));
+    if (l.steady_launch)
+        hipLaunchKernelGGL(icp_steady_kernel, dim3((unsigned)steady_grid(c)), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
+    else if (job.in.poses > 1)
+        hipLaunchKernelGGL((icp_pass_kernel<BK_W, true>), dim3((unsigned)g, (unsigned)job.in.poses), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
     else
-        hipLaunchKernelGGL((icp_pass_kernel<BK_W, false>), dim3((unsigned)g), dim3(BK_W * 64), 0, c->stream, w.st, pa);
-    if (ev1) { PEDP_HIP_CHECK(hipEventRecord(ev1, c->stream)); c->nn_timed = true; }
+        hipLaunchKernelGGL((icp_pass_kernel<BK_W, false>), dim3((unsigned)g), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
+    if (l.ev1) { PEDP_HIP_CHECK(hipEventRecord(l.ev1, c->stream)); c->nn_timed = true; }
     PEDP_HIP_CHECK(hipGetLastError());
     return PEDP_OK;
 }
 
-// The close of a fused pass as a launch of its own (icp_finish_kernel): one workgroup per pose of the `grid` that share
-// the launch, their blocks pose_stride bytes apart.  stage 0: sum, solve, update; 1: sum only (the packet then goes
-// through the exchange step); 2: solve from the summed packet.
-void launch_finish(pedp_ctx_t x, const IcpWorkspace &w, const TargetPrep &tp, int grid, int stage, int estimator, double *trace,
-                   size_t pose_stride) {
-    hipLaunchKernelGGL(icp_finish_kernel, dim3((unsigned)grid), dim3(FIN_THREADS), 0, x->stream, w.st, w.live, w.live_list, w.n_lw,
-                       w.cpart, w.packet, stage, estimator, trace, w.hist, tp.bc[0], tp.bc[1], tp.bc[2], pose_stride,
-                       serial_close() ? 1 : 0);
+// The close of a fused pass as a launch of its own (icp_finish_kernel): one workgroup per pose of the job, their blocks
+// pose_stride bytes apart.  stage 0: sum, solve, update; 1: sum only (the packet then goes through the exchange step);
+// 2: solve from the summed packet.
+void launch_finish(pedp_ctx_t x, const IcpJob &job, int stage) {
+    const IcpWorkspace &w = job.w;
+    hipLaunchKernelGGL(icp_finish_kernel, dim3((unsigned)job.in.poses), dim3(FIN_THREADS), 0, x->stream, w.st, w.live, w.live_list, w.n_lw,
+                       w.cpart, w.packet, stage, job.estimator, job.pa.trace, w.hist, job.tp.bc[0], job.tp.bc[1], job.tp.bc[2],
+                       job.pa.pose_stride, job.pa.serial_close);
 }
 
 // Spatial order of a cloud, cached in the handle: a function of the cloud alone (cells over its own
@@ -590,27 +600,18 @@ int build_compact_order(pedp_ctx_t c, pedp_cloud_t tgt) {
 
 // Which order a target's pack should have now.  Automatic mode: the Hilbert runs that the first registration gets for
 // the price of five launches, the compact order from the second registration on against targets large enough that the
-// shorter tile lists pay the build back.  PEDP_ICP_TARGET_ORDER=hilbert|compact decides for every
-// cloud in automatic mode (A/B runs).
+// shorter tile lists pay the build back, unless PEDP_ICP_TARGET_ORDER decides for every cloud in
+// automatic mode.
 constexpr int64_t TORD_AUTO_MIN_ROWS = 16384;
 constexpr int TORD_AUTO_REGISTRATION = 2;
 // a registration against tgt has been enqueued whole (counted up to the one that upgrades the order)
 inline void count_registration(pedp_cloud_t tgt) {
     if (tgt->registrations < TORD_AUTO_REGISTRATION) ++tgt->registrations;
 }
-inline int target_order_env() {
-    static const int m = [] {
-        const char *v = getenv("PEDP_ICP_TARGET_ORDER");
-        if (v && !strcmp(v, "hilbert")) return PEDP_TARGET_ORDER_HILBERT;
-        if (v && !strcmp(v, "compact")) return PEDP_TARGET_ORDER_COMPACT;
-        return PEDP_TARGET_ORDER_AUTO;
-    }();
-    return m;
-}
 // upcoming: the call is a registration (it becomes number registrations + 1 once its passes are enqueued)
 inline int target_order_wanted(pedp_cloud_t tgt, bool upcoming) {
     if (tgt->order_mode != PEDP_TARGET_ORDER_AUTO) return tgt->order_mode;
-    if (target_order_env() != PEDP_TARGET_ORDER_AUTO) return target_order_env();
+    if (icp_switches().target_order != PEDP_TARGET_ORDER_AUTO) return icp_switches().target_order;
     return tgt->registrations + (upcoming ? 1 : 0) >= TORD_AUTO_REGISTRATION && target_rows(tgt) >= TORD_AUTO_MIN_ROWS ? PEDP_TARGET_ORDER_COMPACT
                                                                                                  : PEDP_TARGET_ORDER_HILBERT;
 }
@@ -634,30 +635,19 @@ int ensure_target_pack(pedp_ctx_t c, pedp_cloud_t tgt, TargetPrep &tp, bool regi
         // real tiles rounded to NN_TU, plus readable pad tiles the pipelined sweep may prefetch
         int64_t pad = (int64_t)align_up((size_t)(tgt->N > 0 ? tgt->N : 1), 16 * NN_TU) + 16 * NN_TILE_PAD;
         // all or none: a half-built pack must not look finished to the next call
-        void *t4 = nullptr, *s1 = nullptr, *s4 = nullptr, *sw = nullptr, *ts = nullptr, *tq = nullptr;
         const int64_t n_wsph = (pad / 16 + 63) / 64;
-        hipError_t e = hipMalloc(&t4, sizeof(float4) * (size_t)pad);
-        if (e == hipSuccess) e = hipMalloc(&s1, sizeof(float4) * (size_t)(pad / 16));
-        if (e == hipSuccess) e = hipMalloc(&s4, sizeof(float4) * (size_t)(pad / 64));
-        if (e == hipSuccess) e = hipMalloc(&sw, sizeof(float4) * (size_t)n_wsph);
-        if (e == hipSuccess) e = hipMalloc(&ts, sizeof(double) * 6 * (size_t)pad);
-        if (e == hipSuccess) e = hipMalloc(&tq, sizeof(int32_t) * (size_t)(tgt->N > 0 ? tgt->N : 1));
+        void *buf[6] = {};  // the operand, the spheres of 16 / 64 / 1024 rows, the sorted rows, the tile order
+        const size_t bytes[6] = {sizeof(float4) * (size_t)pad, sizeof(float4) * (size_t)(pad / 16), sizeof(float4) * (size_t)(pad / 64),
+                                 sizeof(float4) * (size_t)n_wsph, sizeof(double) * 6 * (size_t)pad, sizeof(int32_t) * (size_t)(tgt->N > 0 ? tgt->N : 1)};
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 6 && e == hipSuccess; ++k) e = hipMalloc(&buf[k], bytes[k]);
         if (e != hipSuccess) {
-            if (t4) (void)hipFree(t4);
-            if (s1) (void)hipFree(s1);
-            if (s4) (void)hipFree(s4);
-            if (sw) (void)hipFree(sw);
-            if (ts) (void)hipFree(ts);
-            if (tq) (void)hipFree(tq);
+            for (void *b : buf)
+                if (b) (void)hipFree(b);
             pedp_set_error("pedp_icp: target pack allocation failed: %s", hipGetErrorString(e));
             return PEDP_ERR_ALLOC;
         }
-        tgt->tgt4 = t4;
-        tgt->tile_sph = s1;
-        tgt->tile_sph4 = s4;
-        tgt->tile_sphw = sw;
-        tgt->tgt_s = ts;
-        tgt->tile_perm = tq;
+        tgt->tgt4 = buf[0]; tgt->tile_sph = buf[1]; tgt->tile_sph4 = buf[2]; tgt->tile_sphw = buf[3]; tgt->tgt_s = buf[4]; tgt->tile_perm = buf[5];
         tgt->tgt4_pad = pad;
         tgt->order_in_force = PEDP_TARGET_ORDER_AUTO;  // (none yet)
     }
@@ -681,7 +671,7 @@ int ensure_target_pack(pedp_ctx_t c, pedp_cloud_t tgt, TargetPrep &tp, bool regi
 
 // The bf16 pieces of the sorted operand, for the dense sweep: built when a call first takes that path
 int ensure_target_bf16(pedp_ctx_t c, pedp_cloud_t tgt) {
-    if (tgt->tgt_bf || !tgt->tgt4 || !nn_bf16_sweep()) return PEDP_OK;
+    if (tgt->tgt_bf || !tgt->tgt4 || icp_switches().nn_f32) return PEDP_OK;
     void *p = nullptr;
     if (hipMalloc(&p, sizeof(uint4) * 4 * (size_t)tgt->tgt4_pad) != hipSuccess) {
         pedp_set_error("pedp_icp: target pack allocation failed (bf16 operand)");
@@ -694,35 +684,6 @@ int ensure_target_bf16(pedp_ctx_t c, pedp_cloud_t tgt) {
     PEDP_HIP_CHECK(hipGetLastError());
     return PEDP_OK;
 }
-
-// One registration = enqueue (all passes, on the executor's stream and workspace) + collect
-// (one synchronisation, results to the host).  The executor is the clouds' own context for
-// pedp_icp and one of its sub-contexts (own stream + workspace) for pedp_icp_batched, where
-// several registrations are in flight at once.
-struct IcpJob {
-    IcpWorkspace w;
-    int max_iter = 0, qt = 1;
-    int64_t Ns = 0, Nt = 0;
-    bool exhaustive = false;
-    int timed_pass = -1;
-    // the final state is written into the page-locked block by the workgroup that ends the registration, RESULT_OFF
-    // bytes in (the start state is read from the block's first bytes while the passes run); false: a copy brings it
-    // to the block's start
-    bool dev_result = false;
-    // steady passes are left open and closed at the head of the next launch (fused_close.h); decided once, here: the
-    // kernels' slots and the slots the host looks at follow from this one flag
-    bool head = false;
-    // passes from steady_from() on run in one launch of icp_steady_kernel; icp_collect continues a registration that
-    // the kernel hands back (a rebuild, too many searching slots) and needs what the launches need
-    bool steady = false;
-    bool steady_held = false;  // this job holds the device's steady launch (steady_acquire) until it is collected
-    pedp_cloud_t source = nullptr, target = nullptr;
-    TargetPrep tp{};
-    int estimator = 0;
-    bool want_trace = false;
-};
-constexpr size_t RESULT_OFF = 2048;
-static_assert(sizeof(IcpState) <= RESULT_OFF && sizeof(IcpState) % 8 == 0, "start and final state share the block's first 4 KB, as 8-byte words");
 
 int icp_check_args(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *prm) {
     PEDP_REQUIRE(source->ctx == c && target->ctx == c, "pedp_icp: cloud belongs to another context");
@@ -748,39 +709,26 @@ int icp_unit_size(pedp_cloud_t target, double r) {
 
 // Cached per-cloud preparation on the owner's stream: sorted target operand + unit spheres, spatial
 // order of the scene.
-int icp_prepare(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, TargetPrep &tp) {
-    int rc = ensure_target_pack(c, target, tp, true);
+int icp_prepare(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *prm, TargetPrep &tp) {
+    int rc = icp_check_args(c, source, target, prm);
+    if (rc) return rc;
+    PEDP_HIP_CHECK(hipSetDevice(c->device));
+    rc = ensure_target_pack(c, target, tp, true);
     if (rc) return rc;
     rc = ensure_target_bf16(c, target);   // (with the pack, on the owner's stream: sub-contexts start after it is complete)
     if (rc) return rc;
     return ensure_spatial_perm(c, source);
 }
 
-// workspace of one registration on executor x (may grow the executor's scratch buffer)
-int icp_job_setup(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const pedp_icp_params *prm, IcpJob &job, bool no_steady = false) {
-    PEDP_HIP_CHECK(hipSetDevice(x->device));
-    job.max_iter = prm->max_iteration;
-    job.Ns = source->N;
-    job.Nt = target_rows(target);
-    job.qt = x->icp_exhaustive ? 4 : icp_unit_size(target, prm->max_correspondence_distance);
-    job.exhaustive = x->icp_exhaustive;
-    job.timed_pass = x->icp_timed_pass;
-    IcpWorkspace &w = job.w;
-    const double r = prm->max_correspondence_distance;
-    // the fused pass lists a target's mask words in LDS: up to BK_WCAP words of 1024 rows
-    const bool fused = job.qt == 1 && !job.exhaustive && r > 0.0 && job.Ns > 0 && job.Nt > 0 &&
-                       (job.Nt + 1023) / 1024 <= BK_WCAP;
-    job.dev_result = fused && !prm->allreduce && !prm->use_comm && !unfused_finish() && !copy_bracket();
-    job.head = job.dev_result && !serial_close() && head_close();
-    // (a pass timed on its own, or every fourth one, is a launch of its own; -3 times the whole registration)
-    job.steady = job.head && icp_certificates() && icp_steady() && !no_steady && (job.timed_pass == -1 || job.timed_pass == -3) &&
-                 steady_grid(x) > 0;
-    job.source = source; job.target = target; job.estimator = prm->estimator;
-    int rc = carve_workspace(x, job.Ns, job.Nt, job.max_iter, job.qt, w, fused);
-    if (rc) return rc;
-    bind_clouds(w, source, target, job.qt);
-    return PEDP_OK;
-}
+// What a caller asks of one registration.
+enum { ICP_TRACE = 1, ICP_EARLY_STOP = 2 /* pedp_icp: look at `done` behind every 8th launch */, ICP_NO_STEADY = 4 /* generic launches only */ };
+struct IcpCall {
+    pedp_cloud_t source, target;
+    const TargetPrep *tp;
+    const pedp_icp_params *prm;
+    const double *init;
+    unsigned how;  // ICP_* bits
+};
 
 // start state of a registration in the executor's pinned block (uploaded by the first node of
 // icp_enqueue; the same block receives the final state)
@@ -855,75 +803,69 @@ int exchange_packet(pedp_ctx_t x, const pedp_icp_params *prm, double *packet, in
 
 // every pass of one registration on x's stream; nothing here allocates or synchronises unless
 // early_stop is set, so the sequence can be captured into a graph
-int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp,
-                const pedp_icp_params *prm, bool want_trace, bool early_stop, const IcpJob &job) {
-    const int64_t Ns = source->N, Nt = target_rows(target);
+int icp_enqueue(pedp_ctx_t x, const pedp_icp_params *prm, bool early_stop, const IcpJob &job) {
+    const IcpWorkspace &w = job.w;
+    const IcpPath &path = job.path;
+    const int64_t Ns = job.in.n_source, Nt = job.in.n_target;
     const int max_iter = prm->max_iteration;
     const double r = prm->max_correspondence_distance;
     const double n_global = prm->n_source_global > 0 ? (double)prm->n_source_global : (double)Ns;
-    const IcpWorkspace &w = job.w;
     int rc;
-    // Open3D: max_correspondence_distance <= 0 or an empty cloud gives an empty result
+    // Open3D: max_correspondence_distance <= 0 or an empty cloud gives an empty result (never on the fused path)
     const bool degenerate = (r <= 0.0 || Ns == 0 || Nt == 0);
     IcpState *hp = (IcpState *)x->pinned;
-    unsigned long long *down = job.dev_result ? (unsigned long long *)((char *)x->pinned + RESULT_OFF) : nullptr;
-    if (copy_bracket()) PEDP_HIP_CHECK(hipMemcpyAsync(w.st, hp, sizeof(IcpState), hipMemcpyHostToDevice, x->stream));
     const double r2 = r * r;
     const double ng = n_global > 0 ? n_global : 1.0;
-    const bool exchange = prm->allreduce || prm->use_comm;  // the packet is summed over ranks before the solve
-    const bool fused = w.fused && !degenerate;
-    const bool head = fused && job.head;
+    const bool fused = path.fused, head = path.head;
     int launches = 0;
-    double *trace = want_trace ? w.trace : nullptr;
-    if (fused) {
-        // tickets, sign-off counters and both live masks start at zero: one memset (they lie one behind the other); the
-        // start transformation -- slot 0 of the history -- arrives inside the state; pass 0 itself writes "no
-        // correspondence" for every chunk it does not visit
-        if (copy_bracket())
-            PEDP_HIP_CHECK(hipMemsetAsync(w.ticket, 0, zeroed_span_bytes(w), x->stream));
-        else  // state, zeroes and an empty visit plan in one launch (the plan and the durations lie one behind the other)
-            hipLaunchKernelGGL(icp_state_start_kernel, dim3(1), dim3(256), 0, x->stream, (const unsigned long long *)hp, (unsigned long long *)w.st,
-                               (int)(sizeof(IcpState) / 8), (unsigned long long *)w.ticket, (int)(zeroed_span_bytes(w) / 8),
-                               (unsigned long long *)w.visit, (int)(plan_span_bytes(w) / 8), head ? 2 : 1);
-    } else if (!copy_bracket()) {
+    double *trace = job.want_trace ? w.trace : nullptr;
+    // Fused: tickets, sign-off counters and both live masks start at zero (they lie one behind the other); the start
+    // transformation -- slot 0 of the history -- arrives inside the state; pass 0 itself writes "no correspondence" for
+    // every chunk it does not visit.
+    if (path.copy_bracket) {
+        PEDP_HIP_CHECK(hipMemcpyAsync(w.st, hp, sizeof(IcpState), hipMemcpyHostToDevice, x->stream));
+        if (fused) PEDP_HIP_CHECK(hipMemsetAsync(w.ticket, 0, zeroed_span_bytes(w), x->stream));
+    } else  // state, zeroes and an empty visit plan in one launch (the plan and the durations lie one behind the other)
         hipLaunchKernelGGL(icp_state_start_kernel, dim3(1), dim3(256), 0, x->stream, (const unsigned long long *)hp, (unsigned long long *)w.st,
-                           (int)(sizeof(IcpState) / 8), (unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, 0, 1);
-    }
+                           (int)(sizeof(IcpState) / 8), (unsigned long long *)w.ticket, (int)(zeroed_span_bytes(w) / 8),
+                           (unsigned long long *)w.visit, (int)(plan_span_bytes(w) / 8), head ? 2 : 1);  // (null spans off the fused path)
     PEDP_HIP_CHECK(hipGetLastError());
-    if (job.timed_pass != -1) { x->nn_pairs = 0; x->nn_span_launches = 1; }
+    if (job.in.timed_pass != -1) { x->nn_pairs = 0; x->nn_span_launches = 1; }
     for (int pass = 0; pass <= max_iter; ++pass) {
-        hipEvent_t ev0, ev1;
-        if (head && job.steady && pass == steady_from()) {
+        PassLaunch l{pass};
+        if (job.steady_held && pass == path.steady_from) {
             // this pass and all behind it in one launch; what it hands back icp_collect continues (the second event of
             // timed_pass = -3 stands behind the launch that ends the registration: this one, unless it hands back)
-            rc = pass_timing_events(x, job.timed_pass, max_iter, max_iter, ev0, ev1);
+            rc = pass_timing_events(x, job.in.timed_pass, max_iter, max_iter, l.ev0, l.ev1);
             if (rc) return rc;
-            rc = enqueue_fused_pass(x, w, source, target, prm->estimator, tp, nullptr, ev1, true, trace, 1, down, pass, true);
+            l.ev0 = nullptr;
+            l.steady_launch = true;
+            rc = enqueue_fused_pass(x, job, l);
             if (rc) return rc;
             x->icp_last_launches = max_iter + 1;  // (the passes this enqueue covers)
             break;
         }
-        rc = pass_timing_events(x, job.timed_pass, pass, max_iter, ev0, ev1);
+        rc = pass_timing_events(x, job.in.timed_pass, pass, max_iter, l.ev0, l.ev1);
         if (rc) return rc;
         x->icp_last_launches = ++launches;  // passes enqueued (statistics: the early exit stops enqueuing)
         if (fused) {
-            rc = enqueue_fused_pass(x, w, source, target, prm->estimator, tp, ev0, ev1, !exchange, trace, 1, down, head ? pass : -1);
+            rc = enqueue_fused_pass(x, job, l);
             if (rc) return rc;
-            if (!exchange && unfused_finish()) launch_finish(x, w, tp, 1, 0, prm->estimator, trace, 0);
-            if (exchange) {  // sum -> all-reduce over the ranks -> solve
-                launch_finish(x, w, tp, 1, 1, prm->estimator, trace, 0);
+            if (path.exchange) {  // sum -> all-reduce over the ranks -> solve
+                launch_finish(x, job, 1);
                 rc = exchange_packet(x, prm, w.packet, pass);
                 if (rc) return rc;
-                launch_finish(x, w, tp, 1, 2, prm->estimator, trace, 0);
-            }
+                launch_finish(x, job, 2);
+            } else if (path.unfused_finish)
+                launch_finish(x, job, 0);
             PEDP_HIP_CHECK(hipGetLastError());
         } else {
             if (!degenerate) {
-                rc = enqueue_nn_pass(x, w, source, target, pass == 0 ? 0 : 1, tp, r, ev0, ev1, job.exhaustive);
+                rc = enqueue_nn_pass(x, w, pass == 0 ? 0 : 1, job.tp, r, l.ev0, l.ev1, job.in.exhaustive);
                 if (rc) return rc;
                 hipLaunchKernelGGL(icp_accumulate_kernel, dim3(ACC_BLOCKS), dim3(ACC_THREADS), 0, x->stream, w.st,
-                                   prm->estimator, w.P, Ns, target->pts, target->normals, w.idx, w.d2, r2, w.partials);
-                if (exchange) hipLaunchKernelGGL(icp_reduce_kernel, dim3(1), dim3(64), 0, x->stream, w.st, w.partials, w.packet);
+                                   prm->estimator, w.P, Ns, w.target->pts, w.target->normals, w.idx, w.d2, r2, w.partials);
+                if (path.exchange) hipLaunchKernelGGL(icp_reduce_kernel, dim3(1), dim3(64), 0, x->stream, w.st, w.partials, w.packet);
             } else {
                 PEDP_HIP_CHECK(hipMemsetAsync(w.packet, 0, sizeof(double) * 32, x->stream));
                 if (pass == 0 && Ns > 0) PEDP_HIP_CHECK(hipMemsetAsync(w.idx, 0xFF, sizeof(int32_t) * (size_t)Ns, x->stream));
@@ -932,7 +874,7 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
             if (rc) return rc;
             // A fused accumulate + solve (last workgroup done runs the solve) was measured slower:
             // the device-scope release every workgroup needs writes the whole L2 back (43 us vs 12 + 16).
-            const double *fold = (!degenerate && !exchange) ? w.partials : nullptr;
+            const double *fold = (!degenerate && !path.exchange) ? w.partials : nullptr;
             hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(256), 0, x->stream, w.st, w.packet, fold, pass, max_iter,
                                prm->estimator, ng, prm->relative_fitness, prm->relative_rmse, trace);
             PEDP_HIP_CHECK(hipGetLastError());
@@ -942,7 +884,6 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
         // on every rank of a sharded run) and stop enqueuing once it is set.
         if (early_stop && prm->relative_fitness >= 0.0 && (pass & 7) == 7 && pass < max_iter) {
             int *flag = (int *)((char *)x->pinned + 4096);
-            // (head close: the slot this pass's index names -- the one a head close in this launch wrote)
             // (head close: whoever ends the registration writes `done` into the slot of the pass behind the one it closed,
             // either parity; the other slot's `done` stays 0 -- both are read)
             flag[1] = 0;
@@ -952,33 +893,41 @@ int icp_enqueue(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const Ta
             if (flag[0] || flag[1]) break;
         }
     }
-    if (!job.dev_result) PEDP_HIP_CHECK(hipMemcpyAsync(hp, w.st, sizeof(IcpState), hipMemcpyDeviceToHost, x->stream));
+    if (!path.dev_result) PEDP_HIP_CHECK(hipMemcpyAsync(hp, w.st, sizeof(IcpState), hipMemcpyDeviceToHost, x->stream));
     return PEDP_OK;
 }
 
-// A registration made ready on executor x: its workspace, its start state in x's pinned block, the result slot armed.
-// (All that a replay of a captured graph needs.)
-int icp_stage(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp, const pedp_icp_params *prm,
-              const double init[16], IcpJob &job, bool no_steady = false) {
-    int rc = icp_job_setup(x, source, target, prm, job, no_steady);
+// A registration made ready on executor x: its path, workspace (may grow the executor's scratch buffer) and pass arguments,
+// its start state in x's pinned block, the result slot armed.  (All that a replay of a captured graph needs.)
+int icp_stage(pedp_ctx_t x, const IcpCall &call, IcpJob &job) {
+    PEDP_HIP_CHECK(hipSetDevice(x->device));
+    const pedp_icp_params *prm = call.prm;
+    job.max_iter = prm->max_iteration;
+    job.tp = *call.tp; job.estimator = prm->estimator; job.want_trace = call.how & ICP_TRACE;
+    IcpPathInputs &in = job.in;
+    in.n_source = call.source->N; in.n_target = target_rows(call.target); in.radius = prm->max_correspondence_distance;
+    in.exhaustive = x->icp_exhaustive; in.unit_size = in.exhaustive ? 4 : icp_unit_size(call.target, in.radius);
+    in.exchange = prm->allreduce || prm->use_comm; in.poses = 1; in.timed_pass = x->icp_timed_pass;
+    // (pedp_icp's look at `done` behind every 8th launch needs launches to look behind)
+    in.early_exit = (call.how & ICP_EARLY_STOP) && prm->relative_fitness >= 0.0;
+    in.no_steady = (call.how & ICP_NO_STEADY) != 0;
+    in.resident = 1;  // (asked of the runtime only where everything else allows the steady launch)
+    job.path = icp_decide_path(icp_switches(), in);
+    if (job.path.steady && steady_grid(x) <= 0) { in.resident = 0; job.path = icp_decide_path(icp_switches(), in); }
+    int rc = carve_workspace(x, job.in.n_source, job.in.n_target, job.max_iter, job.in.unit_size, job.w, job.path.fused);
     if (rc) return rc;
-    job.tp = tp;
-    icp_fill_state((IcpState *)x->pinned, tp, init, prm, source->N);
+    bind_clouds(job.w, call.source, call.target, job.in.unit_size);
+    if (job.path.fused) stage_pass_args(x, job);
+    icp_fill_state((IcpState *)x->pinned, *call.tp, call.init, prm, call.source->N);
     icp_arm_result(x);
     return PEDP_OK;
 }
 // ... and started: every pass enqueued on x's stream
-int icp_start(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp, const pedp_icp_params *prm,
-              const double init[16], IcpJob &job, bool want_trace, bool early_stop, bool no_steady = false) {
-    // (pedp_icp's look at `done` behind every 8th launch needs launches to look behind)
-    int rc = icp_stage(x, source, target, tp, prm, init, job, no_steady || (early_stop && prm->relative_fitness >= 0.0));
+int icp_start(pedp_ctx_t x, const IcpCall &call, IcpJob &job) {
+    int rc = icp_stage(x, call, job);
     if (rc) return rc;
-    job.want_trace = want_trace;
-    if (job.steady && prm->max_iteration >= steady_from()) {
-        job.steady_held = steady_acquire(x->device);
-        if (!job.steady_held) job.steady = false;
-    }
-    rc = icp_enqueue(x, source, target, tp, prm, want_trace, early_stop, job);
+    if (job.path.steady && call.prm->max_iteration >= job.path.steady_from) job.steady_held = steady_acquire(x->device);
+    rc = icp_enqueue(x, call.prm, call.how & ICP_EARLY_STOP, job);
     if (rc && job.steady_held) { steady_release(x->device); job.steady_held = false; }
     return rc;
 }
@@ -992,7 +941,7 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
         int device; bool held;
         ~SteadyHold() { if (held) steady_release(device); }
     } hold{x->device, job.steady_held};
-    if (job.steady) {
+    if (job.steady_held) {
         // A steady launch either ends the registration or hands it back with the state of the pass that is to run next
         // (in its slot, and a marked copy in the page-locked block): two generic launches from that pass, the steady
         // launch again, until the registration is over.  Each round runs at least one pass.
@@ -1003,24 +952,23 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
             const int from = res->pass;
             res->done = 0;
             for (int pass = from; pass <= job.max_iter && pass <= from + 2; ++pass) {
-                const int rc = enqueue_fused_pass(x, w, job.source, job.target, job.estimator, job.tp, nullptr, nullptr, true,
-                                                  job.want_trace ? w.trace : nullptr, 1, (unsigned long long *)res, pass, pass == from + 2);
+                const int rc = enqueue_fused_pass(x, job, PassLaunch{pass, pass == from + 2});
                 if (rc) return rc;
             }
-            if (job.timed_pass == -3) { PEDP_HIP_CHECK(hipEventRecord(x->nn_ev1, x->stream)); }
+            if (job.in.timed_pass == -3) { PEDP_HIP_CHECK(hipEventRecord(x->nn_ev1, x->stream)); }
             PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
         }
     }
     bool copies = false;
-    if (corr && job.Ns > 0)
-        { int dn_ = pedp_download(x, corr, w.idx, sizeof(int32_t) * (size_t)job.Ns); if (dn_) return dn_; copies = true; }
+    if (corr && job.in.n_source > 0)
+        { int dn_ = pedp_download(x, corr, w.idx, sizeof(int32_t) * (size_t)job.in.n_source); if (dn_) return dn_; copies = true; }
     if (trace) {
         PEDP_HIP_CHECK(hipMemcpyAsync(trace, w.trace, sizeof(double) * 18 * (size_t)(job.max_iter + 1), hipMemcpyDeviceToHost, x->stream));
         copies = true;
     }
-    if (copies || !job.steady) PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
-    const IcpState *hp = (const IcpState *)((const char *)x->pinned + (job.dev_result ? RESULT_OFF : 0));
-    if (job.dev_result && hp->done == 0) {  // (armed by icp_arm_result; the workgroup that sets `done` writes the state)
+    if (copies || !job.steady_held) PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
+    const IcpState *hp = (const IcpState *)((const char *)x->pinned + (job.path.dev_result ? RESULT_OFF : 0));
+    if (job.path.dev_result && hp->done == 0) {  // (armed by icp_arm_result; the workgroup that sets `done` writes the state)
         pedp_set_error("pedp_icp: the registration's final state did not arrive");
         return PEDP_ERR_HIP;
     }
@@ -1030,7 +978,7 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     }
     for (int k = 0; k < 16; ++k) T_out[k] = hp->T[k];
     // (scene slot, target point) pairs the MFMAs evaluated: fused pass counts 16 x 16 wave-tiles, the segmented path units x 128 slots
-    x->icp_last_cand = job.w.fused ? hp->sum_tiles * 256 : hp->sum_tiles * (16 * job.qt) * (NN_SB * 16);
+    x->icp_last_cand = job.path.fused ? hp->sum_tiles * 256 : hp->sum_tiles * (16 * job.in.unit_size) * (NN_SB * 16);
     x->icp_last_fb = hp->sum_fb;
     x->icp_last_passes = hp->iters + 1;
     x->icp_last_planned = hp->n_planned;
@@ -1041,8 +989,8 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     x->icp_last_steady = hp->n_steady;
     x->icp_last_handbacks = handbacks;
     x->icp_last_rebuilds = hp->n_rebuilds;
-    x->icp_last_bracket = (copy_bracket() ? 0 : 1) + (job.dev_result ? 2 : 0);
-    x->icp_last_nt = job.Nt;
+    x->icp_last_bracket = (job.path.copy_bracket ? 0 : 1) + (job.path.dev_result ? 2 : 0);
+    x->icp_last_nt = job.in.n_target;
     if (fitness) *fitness = hp->fitness;
     if (inlier_rmse) *inlier_rmse = hp->rmse;
     if (n_iter_done) *n_iter_done = hp->iters;
@@ -1060,34 +1008,43 @@ bool graph_key_equal(const pedp_icp_graph_key &a, const pedp_icp_graph_key &b) {
            a.rel_fitness == b.rel_fitness && a.rel_rmse == b.rel_rmse && a.seg == b.seg && a.poses == b.poses;
 }
 
-int icp_launch_replayed(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp,
-                        const pedp_icp_params *prm, const double init[16], IcpJob &job) {
-    int rc = icp_stage(x, source, target, tp, prm, init, job, true);  // (a captured graph holds generic launches only)
+// What `enqueue` puts on x's stream, captured into a graph and instantiated into `exec` (whose earlier graph goes).
+// Returns enqueue's error.  `exec` stays null where capture or instantiation failed; `e` says why.
+template <typename Enqueue>
+int capture_graph(pedp_ctx_t x, hipGraphExec_t &exec, hipError_t &e, Enqueue enqueue) {
+    if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+    e = hipStreamBeginCapture(x->stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) return PEDP_OK;
+    hipGraph_t graph = nullptr;
+    const int rc = enqueue();
+    e = hipStreamEndCapture(x->stream, &graph);
+    if (!rc && e == hipSuccess && graph) {
+        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (e == hipSuccess) ++x->icp_graph_captures;
+        else exec = nullptr;
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc;
+}
+
+int icp_launch_replayed(pedp_ctx_t x, const IcpCall &call, IcpJob &job) {
+    int rc = icp_stage(x, call, job);  // (ICP_NO_STEADY: a captured graph holds generic launches only)
     if (rc) return rc;
+    const pedp_icp_params *prm = call.prm;
     pedp_icp_graph_key key;
-    key.src_gen = source->gen; key.tgt_gen = target->gen; key.ws = x->icp_ws.ptr;
-    key.Ns = job.Ns; key.Nt = job.Nt; key.max_iter = job.max_iter; key.qt = job.qt; key.estimator = prm->estimator;
-    key.r = prm->max_correspondence_distance;
-    key.rel_fitness = prm->relative_fitness;
-    key.rel_rmse = prm->relative_rmse;
-    key.seg = job.w.fused ? -1 : 0;
+    key.src_gen = call.source->gen; key.tgt_gen = call.target->gen; key.ws = x->icp_ws.ptr;
+    key.Ns = job.in.n_source; key.Nt = job.in.n_target; key.max_iter = job.max_iter; key.qt = job.in.unit_size; key.estimator = prm->estimator;
+    key.r = prm->max_correspondence_distance; key.rel_fitness = prm->relative_fitness; key.rel_rmse = prm->relative_rmse;
+    key.seg = job.path.fused ? -1 : 0;
     const bool same = x->icp_graph && graph_key_equal(x->icp_graph_key, key);
     if (!same) {
-        if (x->icp_graph) { (void)hipGraphExecDestroy(x->icp_graph); x->icp_graph = nullptr; }
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(x->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            rc = icp_enqueue(x, source, target, tp, prm, false, false, job);
-            const hipError_t e = hipStreamEndCapture(x->stream, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            if (e == hipSuccess && graph && hipGraphInstantiate(&x->icp_graph, graph, nullptr, nullptr, 0) == hipSuccess)
-                { x->icp_graph_key = key; ++x->icp_graph_captures; }
-            else
-                x->icp_graph = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-        }
+        hipError_t e;
+        rc = capture_graph(x, x->icp_graph, e, [&] { return icp_enqueue(x, prm, false, job); });
+        if (rc) return rc;
         (void)hipGetLastError();
         if (!x->icp_graph)  // capture unavailable: plain launches, same work
-            return icp_enqueue(x, source, target, tp, prm, false, false, job);
+            return icp_enqueue(x, prm, false, job);
+        x->icp_graph_key = key;
     }
     PEDP_HIP_CHECK(hipGraphLaunch(x->icp_graph, x->stream));
     return PEDP_OK;
@@ -1102,9 +1059,24 @@ int icp_launch_replayed(pedp_ctx_t x, pedp_cloud_t source, pedp_cloud_t target, 
 // poses -- and a group that converges after 7 iterations costs 10 passes of launches, not 31.
 constexpr int BATCH_GROUP_MAX = 32;
 
+// `n` passes of a group, each closed by a launch of icp_finish_kernel where the pass does not close itself
+int enqueue_batch_stretch(pedp_ctx_t c, const IcpJob &job, int n) {
+    for (int p = 0; p < n; ++p) {
+        const int rc = enqueue_fused_pass(c, job, PassLaunch{});
+        if (rc) return rc;
+        if (job.path.unfused_finish) launch_finish(c, job, 0);
+    }
+    return PEDP_OK;
+}
+
+// Per-pose results of a batch (any but T may be null).
+struct BatchOut {
+    double *T, *fitness, *inlier_rmse;
+    int32_t *n_iter_done;
+};
+
 int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const TargetPrep &tp,
-                    const pedp_icp_params *prms, const double *inits, int B, double *T_out, double *fitness,
-                    double *inlier_rmse, int32_t *n_iter_done) {
+                    const pedp_icp_params *prms, const double *inits, int B, const BatchOut &out) {
     bool no_exit = true;
     for (int b = 0; b < B; ++b) no_exit = no_exit && (prms[b].relative_fitness < 0.0 || prms[b].relative_rmse < 0.0);
     int G = 1;  // group size: the power of two that holds the batch, at most BATCH_GROUP_MAX (one cached graph per size)
@@ -1113,47 +1085,39 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
     static_assert(sizeof(IcpState) * BATCH_GROUP_MAX <= 32768, "two pinned halves hold a group's states");
     IcpJob job;
     job.max_iter = prms[0].max_iteration;
-    job.Ns = source->N;
-    job.Nt = target_rows(target);
-    job.qt = 1;
+    job.tp = tp; job.estimator = prms[0].estimator;
+    IcpPathInputs &in = job.in;  // (every pose is fused-eligible, whatever its radius: pedp_icp_batched_ex has looked)
+    in.n_source = source->N; in.n_target = target_rows(target); in.radius = prms[0].max_correspondence_distance; in.unit_size = 1;
+    in.poses = G; in.batch = 1; in.timed_pass = -1; in.no_steady = 1;
+    job.path = icp_decide_path(icp_switches(), in);
     IcpWorkspace &w = job.w;
-    int rc = carve_workspace(c, job.Ns, job.Nt, job.max_iter, 1, w, true, G);
+    int rc = carve_workspace(c, job.in.n_source, job.in.n_target, job.max_iter, 1, w, true, G);
     if (rc) return rc;
     bind_clouds(w, source, target, 1);
+    stage_pass_args(c, job);
     const int all = job.max_iter + 1;
     pedp_icp_graph_key key;
     key.src_gen = source->gen; key.tgt_gen = target->gen; key.ws = c->icp_ws.ptr;
-    key.Ns = job.Ns; key.Nt = job.Nt; key.qt = 1; key.estimator = prms[0].estimator;
+    key.Ns = job.in.n_source; key.Nt = job.in.n_target; key.qt = 1; key.estimator = prms[0].estimator;
     key.max_iter = iter_capacity(job.max_iter);  // the limit itself is in the device state; the workspace layout (trace, history) depends on its capacity class
-    key.r = -1.0;
     // passes per replay: everything when no pose can stop early, else a stretch that covers the usual
     // convergence (Open3D's default criteria stop problems of this kind after 6-9 iterations)
     key.seg = no_exit ? all : (all < 10 ? all : 10);
-    key.poses = G;
+    key.poses = G; key.r = -1.0;
     slot = 3 * slot + (key.seg == 1 ? 0 : (key.seg == 2 ? 1 : 2));  // a graph per group size and kind of stretch
     // One or two passes per stretch (a z-search probe is a one-iteration registration) are launched as they are: a graph
     // of two kernels saves nothing, and with a new scene handle every frame its capture and instantiation (35-50 us) came
     // back for every frame's first batch
     const bool direct = key.seg <= 2;
     if (!direct && !(c->icp_bgraph[slot] && graph_key_equal(c->icp_bgraph_key[slot], key))) {
-        if (c->icp_bgraph[slot]) { (void)hipGraphExecDestroy(c->icp_bgraph[slot]); c->icp_bgraph[slot] = nullptr; }
-        hipGraph_t graph = nullptr;
-        PEDP_HIP_CHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        for (int p = 0; p < key.seg && !rc; ++p) {
-            rc = enqueue_fused_pass(c, w, source, target, prms[0].estimator, tp, nullptr, nullptr, true, nullptr, G);
-            if (unfused_finish()) launch_finish(c, w, tp, G, 0, prms[0].estimator, nullptr, G > 1 ? w.pose_stride : 0);
-        }
-        const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess || !graph || hipGraphInstantiate(&c->icp_bgraph[slot], graph, nullptr, nullptr, 0) != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            c->icp_bgraph[slot] = nullptr;
+        hipError_t e;
+        rc = capture_graph(c, c->icp_bgraph[slot], e, [&] { return enqueue_batch_stretch(c, job, key.seg); });
+        if (rc) return rc;
+        if (!c->icp_bgraph[slot]) {
             pedp_set_error("pedp_icp_batched: graph capture failed: %s", hipGetErrorString(e));
             return PEDP_ERR_HIP;
         }
-        (void)hipGraphDestroy(graph);
         c->icp_bgraph_key[slot] = key;
-        ++c->icp_graph_captures;
     }
     IcpState *up = (IcpState *)c->pinned, *down = (IcpState *)((char *)c->pinned + 32768);
     c->icp_last_cand = c->icp_last_fb = c->icp_last_passes = 0;  // statistics: totals over the batch
@@ -1175,11 +1139,8 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
         bool finished = false;
         for (int guard = 0; guard < (1 << 20) && !finished; ++guard) {
             if (direct) {
-                for (int p = 0; p < key.seg; ++p) {
-                    int rp = enqueue_fused_pass(c, w, source, target, prms[0].estimator, tp, nullptr, nullptr, true, nullptr, G);
-                    if (rp) return rp;
-                    if (unfused_finish()) launch_finish(c, w, tp, G, 0, prms[0].estimator, nullptr, G > 1 ? w.pose_stride : 0);
-                }
+                rc = enqueue_batch_stretch(c, job, key.seg);
+                if (rc) return rc;
             } else
                 PEDP_HIP_CHECK(hipGraphLaunch(c->icp_bgraph[slot], c->stream));
             hipLaunchKernelGGL(batch_state_gather_kernel, dim3((unsigned)G), dim3(256), 0, c->stream, (const char *)w.st, w.pose_stride,
@@ -1197,10 +1158,10 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
             }
         for (int k = 0; k < n; ++k) {
             const IcpState &h = down[k];
-            for (int q = 0; q < 16; ++q) T_out[16 * (b0 + k) + q] = h.T[q];
-            if (fitness) fitness[b0 + k] = h.fitness;
-            if (inlier_rmse) inlier_rmse[b0 + k] = h.rmse;
-            if (n_iter_done) n_iter_done[b0 + k] = h.iters;
+            for (int q = 0; q < 16; ++q) out.T[16 * (b0 + k) + q] = h.T[q];
+            if (out.fitness) out.fitness[b0 + k] = h.fitness;
+            if (out.inlier_rmse) out.inlier_rmse[b0 + k] = h.rmse;
+            if (out.n_iter_done) out.n_iter_done[b0 + k] = h.iters;
             c->icp_last_cand += h.sum_tiles * 256;
             c->icp_last_fb += h.sum_fb;
             c->icp_last_passes += h.iters + 1;
@@ -1226,14 +1187,11 @@ int pedp_icp(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const pedp_
              int32_t *n_iter_done, int32_t *corr, double *trace) {
     PEDP_REQUIRE(c && source && target && prm && init && T_out, "pedp_icp: null argument");
     PEDP_REQUIRE(!c->icp_pending, "pedp_icp: a registration is pending on this context (pedp_icp_end first)");
-    int rc = icp_check_args(c, source, target, prm);
-    if (rc) return rc;
-    PEDP_HIP_CHECK(hipSetDevice(c->device));
     TargetPrep tp;
-    rc = icp_prepare(c, source, target, tp);
+    int rc = icp_prepare(c, source, target, prm, tp);
     if (rc) return rc;
     IcpJob job;
-    rc = icp_start(c, source, target, tp, prm, init, job, trace != nullptr, true);
+    rc = icp_start(c, IcpCall{source, target, &tp, prm, init, ICP_EARLY_STOP | (trace ? ICP_TRACE : 0u)}, job);
     if (rc) return rc;
     count_registration(target);
     return icp_collect(c, job, T_out, fitness, inlier_rmse, n_iter_done, corr, trace);
@@ -1243,15 +1201,12 @@ int pedp_icp_begin(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const
                    int want_trace) {
     PEDP_REQUIRE(c && source && target && prm && init, "pedp_icp_begin: null argument");
     PEDP_REQUIRE(!c->icp_pending, "pedp_icp_begin: a registration is pending on this context (pedp_icp_end first)");
-    int rc = icp_check_args(c, source, target, prm);
-    if (rc) return rc;
-    PEDP_HIP_CHECK(hipSetDevice(c->device));
     TargetPrep tp;
-    rc = icp_prepare(c, source, target, tp);
+    int rc = icp_prepare(c, source, target, prm, tp);
     if (rc) return rc;
     IcpJob *job = new (std::nothrow) IcpJob;
     PEDP_REQUIRE(job, "pedp_icp_begin: out of memory");
-    rc = icp_start(c, source, target, tp, prm, init, *job, want_trace != 0, false);
+    rc = icp_start(c, IcpCall{source, target, &tp, prm, init, want_trace ? ICP_TRACE : 0u}, *job);
     if (rc) { delete job; return rc; }
     count_registration(target);
     c->icp_pending = job;
@@ -1288,31 +1243,27 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
                   q.relative_fitness == prms[0].relative_fitness && q.relative_rmse == prms[0].relative_rmse;
         if (q.max_correspondence_distance > r_max) r_max = q.max_correspondence_distance;
     }
-    int rc = icp_check_args(c, source, target, &prms[0]);
-    if (rc) return rc;
-    PEDP_HIP_CHECK(hipSetDevice(c->device));
     TargetPrep tp;
-    rc = icp_prepare(c, source, target, tp);
+    int rc = icp_prepare(c, source, target, &prms[0], tp);
     if (rc) return rc;
     // The fused path takes a whole group of poses per launch, whatever their radii and criteria (they
     // live in the device state).  The segmented path replays one graph per pose on sub-contexts and
     // needs one radius and one set of criteria for that; a mixed batch that is not fused-eligible
     // runs one by one on the owner's stream -- same results.
-    bool all_fused = !c->icp_exhaustive;
+    bool all_fused = true;
     for (int b = 0; b < B && all_fused; ++b) {
         const double r = prms[b].max_correspondence_distance;
-        all_fused = icp_unit_size(target, r) == 1 && r > 0.0 && source->N > 0 && target_rows(target) > 0 &&
-                    (target_rows(target) + 1023) / 1024 <= BK_WCAP;
+        all_fused = fused_eligible(icp_unit_size(target, r), c->icp_exhaustive, r, source->N, target_rows(target));
     }
     if (all_fused) {
-        rc = icp_batch_fused(c, source, target, tp, prms, inits, B, T_out, fitness, inlier_rmse, n_iter_done);
+        rc = icp_batch_fused(c, source, target, tp, prms, inits, B, BatchOut{T_out, fitness, inlier_rmse, n_iter_done});
         if (!rc) count_registration(target);
         return rc;
     }
     if (!uniform) {
         for (int b = 0; b < B; ++b) {
             IcpJob job;
-            rc = icp_start(c, source, target, tp, &prms[b], inits + 16 * b, job, false, true, true);
+            rc = icp_start(c, IcpCall{source, target, &tp, &prms[b], inits + 16 * b, ICP_EARLY_STOP | ICP_NO_STEADY}, job);
             if (rc) return rc;
             rc = icp_collect(c, job, T_out + 16 * b, fitness ? fitness + b : nullptr, inlier_rmse ? inlier_rmse + b : nullptr,
                              n_iter_done ? n_iter_done + b : nullptr, nullptr, nullptr);
@@ -1343,7 +1294,7 @@ int pedp_icp_batched_ex(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, 
     for (int b0 = 0; b0 < B; b0 += K) {
         const int n = (B - b0 < K) ? B - b0 : K;
         for (int k = 0; k < n; ++k) {
-            rc = icp_launch_replayed(c->sub[k], source, target, tp, &prms[b0 + k], inits + 16 * (b0 + k), jobs[k]);
+            rc = icp_launch_replayed(c->sub[k], IcpCall{source, target, &tp, &prms[b0 + k], inits + 16 * (b0 + k), ICP_NO_STEADY}, jobs[k]);
             if (rc) return drain(rc);
         }
         for (int k = 0; k < n; ++k) {
@@ -1405,7 +1356,7 @@ int pedp_nn(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const double
     PEDP_HIP_CHECK(hipMemcpyAsync(w.st, hp, sizeof(IcpState), hipMemcpyHostToDevice, c->stream));
     // every point is a candidate: radius = "infinite" (cloud scale bound)
     c->nn_pairs = 0;
-    rc = enqueue_nn_pass(c, w, source, target, 0, tp, 1e18, c->nn_ev0, c->nn_ev1);
+    rc = enqueue_nn_pass(c, w, 0, tp, 1e18, c->nn_ev0, c->nn_ev1, false);
     if (rc) return rc;
     { int dn_ = pedp_download(c, idx, w.idx, sizeof(int32_t) * (size_t)source->N); if (dn_) return dn_; }
     { int dn_ = pedp_download(c, d2, w.d2, sizeof(double) * (size_t)source->N); if (dn_) return dn_; }
@@ -1525,6 +1476,12 @@ int pedp_debug_nn_bf16(pedp_ctx_t c, const float *src4, int64_t n_src, const flo
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d_s); (void)hipFree(d_t); (void)hipFree(d_b); (void)hipFree(d_g);
     PEDP_HIP_CHECK(e);
+    return PEDP_OK;
+}
+
+int pedp_debug_icp_path(const pedp_icp_switches *switches, const pedp_icp_path_inputs *inputs, pedp_icp_path *path) {
+    PEDP_REQUIRE(inputs && path, "pedp_debug_icp_path: null argument");
+    *path = icp_decide_path(switches ? *switches : icp_switches(), *inputs);
     return PEDP_OK;
 }
 

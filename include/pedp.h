@@ -578,6 +578,43 @@ int pedp_debug_nn_bf16(pedp_ctx_t ctx, const float *src4, int64_t n_src, const f
 int pedp_debug_target_pack(pedp_ctx_t ctx, pedp_cloud_t cloud, int64_t *rows, int64_t *pad_rows, int32_t *tile_perm,
                            float *tgt4, float *sph16, float *sph64, float *sph1024);
 
+/* Which way a registration runs: the library's one decision (csrc/pedp_icp.hip: icp_decide_path), exposed for tests.
+ * No context, no GPU.  Every flag is 0 or 1. */
+typedef struct pedp_icp_switches {  /* the environment switches, read once per process: PEDP_ICP_<FIELD>, PEDP_NN_F32 */
+    int nn_f32, unfused_finish, no_visit_plan, serial_close, copy_bracket; /* on when set to a number other than 0 */
+    int head_close, cert, steady;                                          /* on unless set to 0 */
+    int steady_from;  /* default 5 */
+    int steady_grid;  /* cap of a steady launch's workgroups (tests); 0: none */
+    int target_order; /* PEDP_TARGET_ORDER_*: hilbert | compact decide for every cloud in automatic mode */
+} pedp_icp_switches;
+typedef struct pedp_icp_path_inputs {
+    int64_t n_source, n_target; /* source points, finite target rows */
+    double radius;              /* max_correspondence_distance */
+    int unit_size;              /* MFMA tiles per target unit: 1 while radius^2 < diag^2 / 16, else (and exhaustive) 4 */
+    int poses;                  /* start poses that share the launches */
+    int timed_pass;             /* pedp_icp_configure */
+    int exhaustive;
+    int exchange;               /* an all-reduce hook or the communicator sums the packet over ranks */
+    int batch;                  /* a group of a fused batch: the batch's own kernels move its states */
+    int early_exit;             /* pedp_icp with criteria >= 0 looks at `done` behind every 8th launch */
+    int no_steady;              /* the caller needs generic launches only (a captured graph, a mixed batch) */
+    int resident;               /* the steady kernel's grid can be resident on the device */
+} pedp_icp_path_inputs;
+typedef struct pedp_icp_path {  /* DESIGN 4.2 has the table */
+    int fused;          /* passes are launches of the fused pass kernel (else: the segmented kernels) */
+    int dev_result;     /* the workgroup that ends the registration writes the final state to the host's block */
+    int copy_bracket;   /* copies and a fill bracket the passes (else: one start kernel in front of pass 0) */
+    int head;           /* steady passes stay open; the next launch closes them at its head */
+    int certify, plan;  /* the passes keep certificates / a visit plan */
+    int serial_close;   /* the close of a pass on one lane */
+    int unfused_finish; /* a launch of the finish kernel closes every pass */
+    int exchange;       /* the packet is summed over ranks between the sums and the solve */
+    int steady;         /* the passes from steady_from on run in one resident launch, if the device's is free */
+    int steady_from;
+} pedp_icp_path;
+/* switches null: those this process read from its environment. */
+int pedp_debug_icp_path(const pedp_icp_switches *switches, const pedp_icp_path_inputs *inputs, pedp_icp_path *path);
+
 /* ---------------------------------------------------------------- multi-GPU collectives
  * One process per GPU.  The reference has no distributed path; these entry points
  * exist so that the two exchange steps of the sharded path run inside the library, on

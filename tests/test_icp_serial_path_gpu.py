@@ -65,6 +65,20 @@ for config in ("parity", "bench_100k"):
         # ... and a fused batch, whose kernel shares the close
         T, fit, rmse, its = _lib.icp_batched_ex(ctx, src, tgt, np.full(5, 8.0), np.stack([np.linalg.inv(T) for T in synth.batched_start_poses(5)]), max_iteration=15)
         out["batch_T"], out["batch_fit"], out["batch_rmse"], out["batch_its"] = T, fit, rmse, its
+# a small registration whose path the library's decision function predicts: 256 source points (two chunks), 1,024 target
+# rows (one mask word), point-to-plane, 7 passes
+rng = np.random.default_rng(7)
+uv = rng.uniform(-50.0, 50.0, (1024, 2))
+model = np.c_[uv, 0.01 * (uv[:, 0] ** 2 - uv[:, 1] ** 2)]
+nrm = np.c_[-0.02 * uv[:, 0], 0.02 * uv[:, 1], np.ones(1024)]
+nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+shift = np.eye(4); shift[:3, 3] = (0.5, -0.4, 0.3)
+put("small", _lib.icp(ctx, _lib.Cloud(ctx, model[::4] - shift[:3, 3]), _lib.Cloud(ctx, model, nrm), 5.0, np.eye(4), max_iteration=6,
+                      want_corr=True, want_trace=True, **FIXED))
+out["small_path_head"] = np.int64(_lib.icp_last_head_closed(ctx))
+want = _lib.icp_path(None, n_source=256, n_target=1024, radius=5.0, unit_size=1, poses=1, timed_pass=-1, resident=True)
+for k, v in want.items():
+    out["small_path_want_" + k] = np.int64(v)
 np.savez(sys.argv[2], **out)
 """
 
@@ -123,6 +137,19 @@ def test_the_new_paths_were_in_force(probes):
     # the registrations meant to end early, and to run all their passes, did
     for config in ("parity", "bench_100k"):
         assert int(probes["default"][config + "_early_iters"]) < 60 and int(probes["default"][config + "_icp_iters"]) == 20
+
+
+def test_the_decision_function_predicts_the_path_that_ran(probes):
+    """Bracket bits and head closes of a small registration are what pedp_debug_icp_path says for the process's switches:
+    in the default process, and with PEDP_ICP_SERIAL_CLOSE=1 PEDP_ICP_COPY_BRACKET=1."""
+    for setting, dev_result, head in (("default", 1, 1), ("all_off", 0, 0)):
+        r = probes[setting]
+        want = {k[len("small_path_want_"):]: int(v) for k, v in r.items() if k.startswith("small_path_want_")}
+        assert want["fused"] == 1 and want["dev_result"] == dev_result and want["head"] == head, setting
+        assert want["copy_bracket"] == want["serial_close"] == 1 - dev_result, setting
+        assert int(r["small_iters"]) == 6
+        assert int(r["small_path_bracket"]) == (0 if want["copy_bracket"] else 1) + (2 if want["dev_result"] else 0), setting
+        assert (int(r["small_path_head"]) > 0) == bool(want["head"]), setting
 
 
 def _scene(ctx, config):
