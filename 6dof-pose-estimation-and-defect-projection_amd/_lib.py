@@ -174,6 +174,11 @@ PROTOTYPES = {
     "pedp_defect_map_stats": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "pedp_defect_map_regions": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                           _P(C.c_int64)]),
+    "pedp_solid_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_void_p)]),
+    "pedp_solid_destroy": (C.c_int, [C.c_void_p]),
+    "pedp_solid_get_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pedp_signed_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "pedp_mask_depth_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
@@ -597,6 +602,65 @@ class Mesh:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             load().pedp_mesh_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SolidInfo(C.Structure):       # pedp_solid_info
+    _fields_ = [("V", C.c_int64), ("F", C.c_int64), ("welded_vertices", C.c_int64), ("edges", C.c_int64),
+                ("boundary_edges", C.c_int64), ("nonmanifold_edges", C.c_int64), ("flipped_edges", C.c_int64),
+                ("degenerate_faces", C.c_int64), ("closed", C.c_int32), ("orientation", C.c_int32), ("volume", C.c_double)]
+
+
+class Solid:
+    """The topology of one model (pedp_solid_create): what pedp_signed_distance needs besides the posed
+    mesh handle, built once from the model-frame vertices (V x 3, taken as float64) and triangles (F x 3), whatever the
+    pose.  `info` is a dict of pedp_solid_info's fields: V, F, welded_vertices, edges, boundary_edges, nonmanifold_edges,
+    flipped_edges, degenerate_faces, closed, orientation, volume."""
+
+    def __init__(self, ctx, vertices, triangles):
+        self.ctx = ctx
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        t = np.asarray(triangles)
+        if t.size and t.min() < 0:
+            raise PedpError("negative vertex index")
+        t = np.ascontiguousarray(t, dtype=np.uint32).reshape(-1, 3)
+        self.V, self.F = len(v), len(t)
+        self._h = C.c_void_p()
+        check(load().pedp_solid_create(ctx._h, _ptr(v), self.V, _ptr(t), self.F, C.byref(self._h)), "pedp_solid_create")
+        rec = SolidInfo()
+        check(load().pedp_solid_get_info(self._h, C.byref(rec)), "pedp_solid_get_info")
+        self.info = {name: getattr(rec, name) for name, _ in SolidInfo._fields_}
+
+    SIGNED_OUTPUTS = {"signed_distances": (None, np.float64), "occupancy": (None, np.int8), "features": (None, np.uint8),
+                      "normals": (3, np.float64)}
+
+    def signed_distance(self, mesh, points, want=("signed_distances", "occupancy", "features", "normals")):
+        """pedp_signed_distance of `points` (N x 3 host array, taken as float64) against `mesh` (a Mesh of this solid's
+        triangles, as posed): a dict with the entries named in `want`: signed_distances N f64 (negative inside),
+        occupancy N int8 (1 inside), features N u8 (0 face, 1 edge, 2 vertex, 255 none), normals N x 3 f64."""
+        for k in want:
+            if k not in self.SIGNED_OUTPUTS:
+                raise PedpError(f"signed_distance: unknown output {k!r} (one of {', '.join(self.SIGNED_OUTPUTS)})")
+        p = np.asarray(points)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise PedpError(f"signed_distance: points must be N x 3, got shape {p.shape}")
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        n = len(p)
+        out = {k: np.empty((n,) if w is None else (n, w), t) for k, (w, t) in self.SIGNED_OUTPUTS.items() if k in want}
+        check(load().pedp_signed_distance(self.ctx._h, mesh._h, self._h, _ptr(p), n, HOST, _ptr(out.get("signed_distances")),
+                                          _ptr(out.get("occupancy")), _ptr(out.get("features")), _ptr(out.get("normals"))),
+              "pedp_signed_distance")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            load().pedp_solid_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -58,6 +58,8 @@ from .estimator import (FoundationPose, PoseRefinePredictor, ScorePredictor, com
 from .metrics import (add_err, add_err_batch, adds_err, adds_err_batch, compute_auc_sklearn,  # noqa: E402,F401  (Utils.py:232-266, :806-834)
                       symmetry_tfs_from_info)
 from .surface_distance import align_to_mesh, closest_points, compute_distance, deviation_heatmap  # noqa: E402,F401  (run.py:64's heat map)
+from .surface_distance import (Solid, compute_occupancy, compute_signed_distance, signed_closest_points,  # noqa: E402,F401
+                               signed_deviation, split_deviation)
 from .defect_map import DefectMap  # noqa: E402,F401  (run.py:61, :119, :196-201: the history of hits, kept per face)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
@@ -93,5 +95,6 @@ __all__ = [
     "RefineNet", "ScoreNetMultiPair", "load_refiner", "load_scorer",
     "add_err", "adds_err", "add_err_batch", "adds_err_batch", "compute_auc_sklearn", "symmetry_tfs_from_info",
     "closest_points", "compute_distance", "align_to_mesh", "deviation_heatmap",
+    "Solid", "compute_signed_distance", "compute_occupancy", "signed_closest_points", "signed_deviation", "split_deviation",
     "DefectMap",
 ]

@@ -19,6 +19,7 @@
 // exhaustive one as long as it never drops a triangle that could win, which the margin of sphere_culls() is there for.
 // tests/_closest_ref.py restates the contract in numpy.
 #include "pedp_internal.h"
+#include "mesh/record.h"
 #include <cmath>
 
 namespace {
@@ -31,29 +32,11 @@ constexpr int64_t MAX_POINTS = (int64_t)1 << 24;
 constexpr int64_t WAVE_POINTS_MAX = 16384;  // up to here a wave per point: as many waves as the device holds at once (256 CUs x 32) twice over
 enum { MODE_AUTO = 0, MODE_EXHAUSTIVE = 1, MODE_LANE = 2, MODE_WAVE = 3 };
 
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-__device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7FF0000000000000ll); }
-
-__device__ __forceinline__ double dot3(const double x[3], const double y[3]) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
-struct Tri {
-    double a[3], ab[3], ac[3];
-};
-
-// the record as stored, promoted; false: a record no ray can hit either (m all zero: a pad or a degenerate triangle)
-__device__ __forceinline__ bool load_tri(const float *__restrict__ rec, Tri &t) {
-    if (rec[9] == 0.0f && rec[10] == 0.0f && rec[11] == 0.0f) return false;
-    for (int k = 0; k < 3; ++k) {
-        t.a[k] = (double)rec[k];
-        t.ab[k] = (double)rec[3 + k];
-        t.ac[k] = (double)rec[6 + k];
-    }
-    return true;
-}
+using namespace record;
 
 // Ericson's closest point of a triangle: the barycentrics (v, w) of the first matching region, then the squared
-// distance of p from c = (a + ab v) + ac w
-__device__ __forceinline__ double point_triangle(const double p[3], const Tri &t, double &v, double &w, double c[3], double r[3]) {
+// distance of p from c = (a + ab v) + ac w; rule: the number 1 ... 7 of the region that matched (pedp.h's table)
+__device__ __forceinline__ double point_triangle(const double p[3], const Tri &t, double &v, double &w, double c[3], double r[3], int &rule) {
     double ap[3], bp[3], cp[3];
     for (int k = 0; k < 3; ++k) {
         ap[k] = p[k] - t.a[k];
@@ -64,27 +47,31 @@ __device__ __forceinline__ double point_triangle(const double p[3], const Tri &t
                  d6 = dot3(t.ac, cp);
     const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
     if (d1 <= 0.0 && d2 <= 0.0) {
-        v = 0.0; w = 0.0;
+        v = 0.0; w = 0.0; rule = 1;
     } else if (d3 >= 0.0 && d4 <= d3) {
-        v = 1.0; w = 0.0;
+        v = 1.0; w = 0.0; rule = 2;
     } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-        v = d1 / (d1 - d3); w = 0.0;
+        v = d1 / (d1 - d3); w = 0.0; rule = 3;
     } else if (d6 >= 0.0 && d5 <= d6) {
-        v = 0.0; w = 1.0;
+        v = 0.0; w = 1.0; rule = 4;
     } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-        v = 0.0; w = d2 / (d2 - d6);
+        v = 0.0; w = d2 / (d2 - d6); rule = 5;
     } else if (va <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {
         const double e = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        v = 1.0 - e; w = e;
+        v = 1.0 - e; w = e; rule = 6;
     } else {
         const double den = 1.0 / ((va + vb) + vc);
-        v = vb * den; w = vc * den;
+        v = vb * den; w = vc * den; rule = 7;
     }
     for (int k = 0; k < 3; ++k) {
         c[k] = (t.a[k] + t.ab[k] * v) + t.ac[k] * w;
         r[k] = p[k] - c[k];
     }
     return (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+}
+__device__ __forceinline__ double point_triangle(const double p[3], const Tri &t, double &v, double &w, double c[3], double r[3]) {
+    int rule;
+    return point_triangle(p, t, v, w, c, r, rule);
 }
 
 // the running minimum of (d^2, id): a NaN never enters, ties go to the lower index
@@ -101,6 +88,7 @@ struct Args {
     double *closest, *dist, *uv;
     uint32_t *prim;
     int8_t *side;
+    uint8_t *region;  // the rule (1 ... 7) that point_triangle took for the chosen triangle, 0 where there is none
     unsigned long long *pairs;
 };
 
@@ -109,12 +97,12 @@ __device__ __forceinline__ void store_result(const Args &a, int64_t i, bool fini
     double c[3] = {quiet_nan(), quiet_nan(), quiet_nan()}, v = quiet_nan(), w = quiet_nan();
     double d = finite ? pos_inf() : quiet_nan();
     unsigned id = NONE;
-    int s = 0;
+    int s = 0, rule = 0;
     if (finite && bid != NONE && best < pos_inf()) {
         Tri t;
         (void)load_tri(a.tri + (size_t)bid * PEDP_TRI_STRIDE, t);
         double r[3];
-        const double d2 = point_triangle(p, t, v, w, c, r);
+        const double d2 = point_triangle(p, t, v, w, c, r, rule);
         d = sqrt(d2);
         id = bid;
         const double nrm[3] = {t.ab[1] * t.ac[2] - t.ab[2] * t.ac[1], t.ab[2] * t.ac[0] - t.ab[0] * t.ac[2],
@@ -127,6 +115,7 @@ __device__ __forceinline__ void store_result(const Args &a, int64_t i, bool fini
     if (a.prim) a.prim[i] = id;
     if (a.uv) { a.uv[2 * i] = v; a.uv[2 * i + 1] = w; }
     if (a.side) a.side[i] = (int8_t)s;
+    if (a.region) a.region[i] = (uint8_t)rule;
 }
 
 __device__ __forceinline__ bool load_point(const Args &a, int64_t i, double p[3]) {
@@ -342,18 +331,41 @@ __global__ __launch_bounds__(CT) void face_normal_kernel(const float *__restrict
     double nrm[3] = {quiet_nan(), quiet_nan(), quiet_nan()};
     const uint32_t f = prim[i];
     Tri t;
-    if ((int64_t)f < F && load_tri(tri + (size_t)f * PEDP_TRI_STRIDE, t)) {
-        const double c[3] = {t.ab[1] * t.ac[2] - t.ab[2] * t.ac[1], t.ab[2] * t.ac[0] - t.ab[0] * t.ac[2],
-                             t.ab[0] * t.ac[1] - t.ab[1] * t.ac[0]};
-        const double len = sqrt(dot3(c, c));
-        for (int k = 0; k < 3; ++k) nrm[k] = c[k] / len;
-    }
+    if ((int64_t)f < F && load_tri(tri + (size_t)f * PEDP_TRI_STRIDE, t)) unit_normal(t, nrm);
     out[3 * i] = nrm[0]; out[3 * i + 1] = nrm[1]; out[3 * i + 2] = nrm[2];
 }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
+
+// The search of pedp_closest_points on device memory, enqueued on the context's stream: what the public call and
+// pedp_signed_distance (pedp_solid.hip) both run.  region (nullable): the rule of pedp.h's table, 1 ... 7, that
+// point_triangle took for the chosen triangle (0: no triangle); with it null every other output keeps its bits.
+int pedp_closest_launch(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64_t N, double *closest, double *dist, uint32_t *prim_id,
+                        double *uv, int8_t *side, uint8_t *region) {
+    int rc = c->closest_ws.reserve(256);
+    if (rc) return rc;
+    Args a;
+    a.tri = mesh->tri;
+    a.sph = (const float4 *)mesh->spheres;
+    a.ssph = (const float4 *)mesh->super_spheres;
+    a.F = mesh->F;
+    a.n_clusters = mesh->n_clusters;
+    a.n_super = mesh->n_super;
+    a.pts = pts;
+    a.n = N;
+    a.closest = closest; a.dist = dist; a.prim = prim_id; a.uv = uv; a.side = side; a.region = region;
+    a.pairs = (unsigned long long *)c->closest_ws.ptr;
+    PEDP_HIP_CHECK(hipMemsetAsync(a.pairs, 0, sizeof(unsigned long long), c->stream));
+    const dim3 grid((unsigned)((N + CT - 1) / CT));
+    const int mode = c->closest_mode != MODE_AUTO ? c->closest_mode : (N <= WAVE_POINTS_MAX ? MODE_WAVE : MODE_LANE);
+    if (mode == MODE_EXHAUSTIVE) hipLaunchKernelGGL(closest_exhaustive_kernel, grid, dim3(CT), 0, c->stream, a);
+    else if (mode == MODE_LANE) hipLaunchKernelGGL(closest_culled_kernel, grid, dim3(CT), 0, c->stream, a);
+    else hipLaunchKernelGGL(closest_wave_kernel, dim3((unsigned)((N + CT / 64 - 1) / (CT / 64))), dim3(CT), 0, c->stream, a);
+    PEDP_HIP_CHECK(hipGetLastError());
+    return PEDP_OK;
+}
 
 extern "C" {
 
@@ -420,19 +432,11 @@ int pedp_closest_points(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64
     // context's stream, which a pending registration (pedp_icp_begin) owns until pedp_icp_end
     PEDP_REQUIRE(mem == PEDP_DEVICE || !c->icp_pending, "%s: a registration is pending on this context (host-memory call)", who);
     PEDP_HIP_CHECK(hipSetDevice(c->device));
-    int rc = c->closest_ws.reserve(256);
-    if (rc) return rc;
-    Args a;
-    a.tri = mesh->tri;
-    a.sph = (const float4 *)mesh->spheres;
-    a.ssph = (const float4 *)mesh->super_spheres;
-    a.F = mesh->F;
-    a.n_clusters = mesh->n_clusters;
-    a.n_super = mesh->n_super;
-    a.pts = pts;
-    a.n = N;
-    a.closest = closest; a.dist = dist; a.prim = prim_id; a.uv = uv; a.side = side;
-    a.pairs = (unsigned long long *)c->closest_ws.ptr;
+    int rc = PEDP_OK;
+    const double *d_pts = pts;
+    double *d_closest = closest, *d_dist = dist, *d_uv = uv;
+    uint32_t *d_prim = prim_id;
+    int8_t *d_side = side;
     const size_t n = (size_t)N;
     const size_t o_pts = 0, o_cl = o_pts + align256(24 * n), o_uv = o_cl + align256(24 * n), o_d = o_uv + align256(16 * n),
                  o_id = o_d + align256(8 * n), o_side = o_id + align256(4 * n), io_bytes = o_side + align256(n);
@@ -442,26 +446,21 @@ int pedp_closest_points(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64
         char *io = (char *)c->closest_io.ptr;
         rc = pedp_upload(c, io + o_pts, pts, 24 * n);
         if (rc) return rc;
-        a.pts = (const double *)(io + o_pts);
-        a.closest = closest ? (double *)(io + o_cl) : nullptr;
-        a.uv = uv ? (double *)(io + o_uv) : nullptr;
-        a.dist = dist ? (double *)(io + o_d) : nullptr;
-        a.prim = prim_id ? (uint32_t *)(io + o_id) : nullptr;
-        a.side = side ? (int8_t *)(io + o_side) : nullptr;
+        d_pts = (const double *)(io + o_pts);
+        d_closest = closest ? (double *)(io + o_cl) : nullptr;
+        d_uv = uv ? (double *)(io + o_uv) : nullptr;
+        d_dist = dist ? (double *)(io + o_d) : nullptr;
+        d_prim = prim_id ? (uint32_t *)(io + o_id) : nullptr;
+        d_side = side ? (int8_t *)(io + o_side) : nullptr;
     }
-    PEDP_HIP_CHECK(hipMemsetAsync(a.pairs, 0, sizeof(unsigned long long), c->stream));
-    const dim3 grid((unsigned)((N + CT - 1) / CT));
-    const int mode = c->closest_mode != MODE_AUTO ? c->closest_mode : (N <= WAVE_POINTS_MAX ? MODE_WAVE : MODE_LANE);
-    if (mode == MODE_EXHAUSTIVE) hipLaunchKernelGGL(closest_exhaustive_kernel, grid, dim3(CT), 0, c->stream, a);
-    else if (mode == MODE_LANE) hipLaunchKernelGGL(closest_culled_kernel, grid, dim3(CT), 0, c->stream, a);
-    else hipLaunchKernelGGL(closest_wave_kernel, dim3((unsigned)((N + CT / 64 - 1) / (CT / 64))), dim3(CT), 0, c->stream, a);
-    PEDP_HIP_CHECK(hipGetLastError());
+    rc = pedp_closest_launch(c, mesh, d_pts, N, d_closest, d_dist, d_prim, d_uv, d_side, nullptr);
+    if (rc) return rc;
     if (mem == PEDP_HOST) {
-        if (closest) rc = pedp_download(c, closest, a.closest, 24 * n);
-        if (!rc && uv) rc = pedp_download(c, uv, a.uv, 16 * n);
-        if (!rc && dist) rc = pedp_download(c, dist, a.dist, 8 * n);
-        if (!rc && prim_id) rc = pedp_download(c, prim_id, a.prim, 4 * n);
-        if (!rc && side) rc = pedp_download(c, side, a.side, n);
+        if (closest) rc = pedp_download(c, closest, d_closest, 24 * n);
+        if (!rc && uv) rc = pedp_download(c, uv, d_uv, 16 * n);
+        if (!rc && dist) rc = pedp_download(c, dist, d_dist, 8 * n);
+        if (!rc && prim_id) rc = pedp_download(c, prim_id, d_prim, 4 * n);
+        if (!rc && side) rc = pedp_download(c, side, d_side, n);
     }
     return rc;
 }

@@ -8,6 +8,7 @@
 // integers, and a region's floating-point sums are formed in a fixed order (below), so every output is a function of
 // the inputs alone.
 #include "pedp_internal.h"
+#include "mesh/topology.h"
 #include <cmath>
 #include <rocprim/device/device_scan.hpp>
 
@@ -45,7 +46,7 @@ struct Carver {
 // ------------------------------------------------------------------ the order-preserving key of a double
 // key(x) < key(y) <=> x < y for non-NaN x, y, with -0 below +0; no non-NaN value has key 0 (-inf has 0x000F...F), so
 // 0 stands for "nothing yet".
-__host__ __device__ inline uint64_t bits_of(double x) { uint64_t b; memcpy(&b, &x, 8); return b; }
+using topology::bits_of;
 __host__ __device__ inline double double_of(uint64_t b) { double x; memcpy(&x, &b, 8); return x; }
 __host__ __device__ inline bool is_nan_bits(uint64_t b) { return (b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull; }
 __host__ __device__ inline uint64_t key_of(double x) {
@@ -85,63 +86,6 @@ __global__ __launch_bounds__(DT) void face_geometry_kernel(const double *__restr
     }
 }
 
-// The weld: a hash table of vertex indices, open addressing.  A slot holds the lowest index seen so far of one
-// position; positions compare with ==, so -0 equals +0 (and hashes like it); a vertex with a NaN stays out.
-__device__ __forceinline__ bool vertex_has_nan(const double *v, size_t i) { return !(v[3 * i] == v[3 * i] && v[3 * i + 1] == v[3 * i + 1] && v[3 * i + 2] == v[3 * i + 2]); }
-__device__ __forceinline__ bool vertex_equal(const double *v, size_t i, size_t j) {
-    return v[3 * i] == v[3 * j] && v[3 * i + 1] == v[3 * j + 1] && v[3 * i + 2] == v[3 * j + 2];
-}
-__device__ __forceinline__ uint64_t vertex_hash(const double *v, size_t i) {
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    for (int d = 0; d < 3; ++d) {
-        const double x = v[3 * i + d];
-        uint64_t b = x == 0.0 ? 0ull : bits_of(x);
-        b *= 0xFF51AFD7ED558CCDull; b ^= b >> 33;
-        h = (h ^ b) * 0xC4CEB9FE1A85EC53ull; h ^= h >> 29;
-    }
-    return h;
-}
-__global__ __launch_bounds__(DT) void weld_insert_kernel(const double *__restrict__ v, int64_t V, uint32_t *__restrict__ slot, uint64_t mask) {
-    const int64_t i = (int64_t)blockIdx.x * DT + threadIdx.x;
-    if (i >= V || vertex_has_nan(v, (size_t)i)) return;
-    uint64_t h = vertex_hash(v, (size_t)i) & mask;
-    while (true) {  // the table has at least 2 V slots: an empty one is always met
-        const uint32_t u = atomicCAS(&slot[h], NONE, (uint32_t)i);
-        if (u == NONE) return;
-        if (vertex_equal(v, u, (size_t)i)) { atomicMin(&slot[h], (uint32_t)i); return; }  // whoever holds the slot has this position
-        h = (h + 1) & mask;
-    }
-}
-__global__ __launch_bounds__(DT) void weld_lookup_kernel(const double *__restrict__ v, int64_t V, const uint32_t *__restrict__ slot, uint64_t mask,
-                                                        uint32_t *__restrict__ w) {
-    const int64_t i = (int64_t)blockIdx.x * DT + threadIdx.x;
-    if (i >= V) return;
-    uint32_t r = (uint32_t)i;
-    if (!vertex_has_nan(v, (size_t)i)) {
-        uint64_t h = vertex_hash(v, (size_t)i) & mask;
-        while (true) {
-            const uint32_t u = slot[h];
-            if (u == NONE) break;  // cannot happen: the vertex was inserted
-            if (vertex_equal(v, u, (size_t)i)) { r = u; break; }
-            h = (h + 1) & mask;
-        }
-    }
-    w[i] = r;
-}
-
-// edge slot e = 3 f + k joins corners k and (k + 1) % 3 of face f: key (min w, max w), or all ones where the two weld
-// to one vertex (such a slot names no edge; the sort puts these last)
-__global__ __launch_bounds__(DT) void edge_key_kernel(const uint32_t *__restrict__ tri, const uint32_t *__restrict__ w, int64_t E,
-                                                     unsigned long long *__restrict__ key, unsigned long long *__restrict__ key_copy) {
-    const int64_t e = (int64_t)blockIdx.x * DT + threadIdx.x;
-    if (e >= E) return;
-    const int64_t f = e / 3;
-    const int k = (int)(e - 3 * f);
-    const uint32_t a = w[tri[3 * f + k]], b = w[tri[3 * f + (k + 1) % 3]];
-    const unsigned long long q = a == b ? ~0ull : ((unsigned long long)(a < b ? a : b) << 32) | (a < b ? b : a);
-    key[e] = q;
-    key_copy[e] = q;
-}
 // position p of the sorted slots opens a run of equal keys: its own position, else 0 (an inclusive max scan turns
 // these into every position's run start)
 __global__ __launch_bounds__(DT) void run_head_kernel(const unsigned long long *__restrict__ key, const int32_t *__restrict__ perm, int64_t E,
@@ -522,11 +466,7 @@ int build_adjacency(pedp_defect_map_s *m, const uint32_t *d_tri, const uint32_t 
     unsigned long long *key_copy = cv.take<unsigned long long>((size_t)E);
     int32_t *perm = cv.take<int32_t>((size_t)E), *head = cv.take<int32_t>((size_t)E), *start = cv.take<int32_t>((size_t)E);
     void *tmp = cv.take<char>(tmp_bytes);
-    unsigned long long *keys = nullptr;
-    rc = pedp_sort_keys64_exact_begin(c, E, 64, &keys);
-    if (rc) return rc;
-    hipLaunchKernelGGL(edge_key_kernel, dim3(blocks_for(E)), dim3(DT), 0, c->stream, d_tri, d_w, E, keys, key_copy);
-    rc = pedp_sort_keys64_exact_run(c, E, 64, perm);
+    rc = topology::sort_edges(c, d_tri, d_w, E, key_copy, perm);
     if (rc) return rc;
     hipLaunchKernelGGL(run_head_kernel, dim3(blocks_for(E)), dim3(DT), 0, c->stream, key_copy, perm, E, head);
     PEDP_ROCPRIM(rocprim::inclusive_scan(tmp, tmp_bytes, head, start, (size_t)E, rocprim::maximum<int32_t>(), c->stream));
@@ -578,8 +518,7 @@ int pedp_defect_map_create(pedp_ctx_t c, const double *verts, int64_t V, const u
         m->frames = (int32_t *)(m->store + o_frames); m->stamp = (uint32_t *)(m->store + o_stamp);
         m->counters = (unsigned long long *)(m->store + o_cnt);
         // the vertices, the triangles, the weld's table and ids: needed by the build alone
-        uint64_t slots = 64;
-        while (slots < 2 * (uint64_t)V) slots <<= 1;
+        const uint64_t slots = topology::weld_slots(V);
         const size_t b_v = a256(24 * (size_t)V), b_t = a256(4 * E), b_s = a256(4 * slots), b_w = a256(4 * (size_t)V);
         rc = m->io.reserve(b_v + b_t + b_s + b_w);
         if (!rc) {
@@ -588,13 +527,11 @@ int pedp_defect_map_create(pedp_ctx_t c, const double *verts, int64_t V, const u
             uint32_t *d_t = (uint32_t *)(io + b_v), *d_s = (uint32_t *)(io + b_v + b_t), *d_w = (uint32_t *)(io + b_v + b_t + b_s);
             rc = pedp_upload(c, d_v, verts, 24 * (size_t)V);
             if (!rc) rc = pedp_upload(c, d_t, tris, 4 * E);
-            if (!rc && hipMemsetAsync(d_s, 0xFF, 4 * slots, c->stream) != hipSuccess) rc = PEDP_ERR_HIP;
             if (!rc && hipMemsetAsync(m->store + m->state_off, 0, m->state_bytes, c->stream) != hipSuccess) rc = PEDP_ERR_HIP;
             if (!rc) {
                 hipLaunchKernelGGL(face_geometry_kernel, dim3(blocks_for(F)), dim3(DT), 0, c->stream, d_v, d_t, F, m->area, m->cen, m->box);
-                hipLaunchKernelGGL(weld_insert_kernel, dim3(blocks_for(V)), dim3(DT), 0, c->stream, d_v, V, d_s, slots - 1);
-                hipLaunchKernelGGL(weld_lookup_kernel, dim3(blocks_for(V)), dim3(DT), 0, c->stream, d_v, V, d_s, slots - 1, d_w);
-                rc = build_adjacency(m, d_t, d_w);
+                rc = topology::weld(c, d_v, V, d_s, d_w);
+                if (!rc) rc = build_adjacency(m, d_t, d_w);
             }
             if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
                 pedp_set_error("%s: the build failed on the device", who);

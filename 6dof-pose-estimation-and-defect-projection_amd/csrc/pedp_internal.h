@@ -181,6 +181,7 @@ struct pedp_ctx_s {
 struct pedp_mesh_s {
     pedp_ctx_t ctx = nullptr;
     int device = 0;  // copied at creation: destroy must not dereference a context that may be gone
+    uint64_t gen = 0;  // process-wide creation counter (never reused): names the handle where its address could be reused
     int64_t V = 0, F = 0;
     float *tri = nullptr;  // F_padded x PEDP_TRI_STRIDE floats on the device
     float *tri2 = nullptr; // F_padded/2 pair-interleaved general-origin records (24 floats each)
@@ -236,6 +237,11 @@ struct pedp_cloud_s {
     int order_in_force = 0;  // what the pack holds (0: none)
     int registrations = 0;   // registrations against this handle whose passes were all enqueued, counted up to the one that upgrades the order
 };
+
+// pedp_closest.hip: the search of pedp_closest_points on device memory, enqueued on the context's stream.  region
+// (nullable): the rule 1 ... 7 of pedp.h's table that decided the chosen triangle's closest point, 0 where there is none
+int pedp_closest_launch(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64_t N, double *closest, double *dist, uint32_t *prim_id,
+                        double *uv, int8_t *side, uint8_t *region);
 
 // pedp_icp.hip: frees the job of a pedp_icp_begin that was never ended (called by pedp_ctx_destroy)
 void pedp_icp_drop_pending(pedp_ctx_t c);

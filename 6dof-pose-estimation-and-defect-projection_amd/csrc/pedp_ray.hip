@@ -1704,6 +1704,7 @@ static int mesh_alloc(pedp_ctx_t c, int64_t V, const uint32_t *tris, int64_t F, 
     if (!m) { pedp_set_error("%s: out of host memory", who); return PEDP_ERR_ALLOC; }
     m->ctx = c;
     m->device = c->device;
+    m->gen = pedp_next_generation();
     m->V = V;
     m->F = F;
     m->F_padded = ((F + 63) / 64) * 64;

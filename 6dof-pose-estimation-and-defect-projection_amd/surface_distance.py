@@ -6,12 +6,17 @@
                                        nearest model vertex (defect_projection.py:417-460 snaps to vertices)
     deviation_heatmap                  the distance of every measured depth point from the posed CAD surface as the heat map
                                        that ray_tracing / Mesh.project_heatmap consume (run.py:64 leaves a dummy there)
+    Solid, compute_signed_distance,    RaycastingScene.compute_signed_distance / compute_occupancy: the distance with the
+    compute_occupancy,                 sign of the solid's inside (negative) and outside, by the angle-weighted pseudonormal
+    signed_closest_points              of the closest face, edge or vertex (pedp_signed_distance, csrc/pedp_solid.hip)
+    signed_deviation, split_deviation  a frame's signed distances, and the two heat maps they split into: excess material
+                                       (outside the CAD solid) and missing material (inside it)
 
 CUDA tensors stay on their device: the query is enqueued on the caller's current stream without a host wait when the
 mesh's context was created on that stream (otherwise the two streams are synchronised around the call), and CUDA
 tensors come back.  numpy arrays and CPU tensors use host memory and get their own kind back.  The contract (the
 triangle as the ray caster stores it, float64 with no contraction, Ericson's regions, ties to the lowest index, the
-culled search bit-equal to the exhaustive one) is DESIGN.md s4.16.
+culled search bit-equal to the exhaustive one) is DESIGN.md s4.16; the signed queries' is s4.18.
 """
 import numpy as np
 
@@ -43,7 +48,8 @@ def _mesh_of(name, mesh, ctx, dev):
     return _device_mesh(mesh, ctx)
 
 
-def _query(name, mesh, points, want, ctx=None):
+def _leading_shape(name, points):
+    """(leading shape, number of rows) of a query's points, checked: ... x 3, float32 or float64, at most MAX_POINTS rows."""
     shape = tuple(points.shape) if hasattr(points, "shape") else None
     if shape is None or len(shape) < 1 or shape[-1] != 3:
         raise _lib.PedpError(f"{name}: points must be ... x 3, got {shape if shape is not None else type(points).__name__}")
@@ -54,6 +60,11 @@ def _query(name, mesh, points, want, ctx=None):
     n = int(np.prod(lead, dtype=np.int64))
     if n > MAX_POINTS:
         raise _lib.PedpError(f"{name}: at most {MAX_POINTS} points, got {n}")
+    return lead, n
+
+
+def _query(name, mesh, points, want, ctx=None):
+    lead, n = _leading_shape(name, points)
     dev = device_of(points)
     m = _mesh_of(name, mesh, ctx, dev)
     if dev is not None and (dev.index or 0) != m.ctx.device:
@@ -80,6 +91,142 @@ def closest_points(mesh, points, ctx=None):
 def compute_distance(mesh, points, ctx=None):
     """RaycastingScene.compute_distance: the distances of closest_points alone."""
     return _query("compute_distance", mesh, points, ("distances",), ctx)[0]["distances"]
+
+
+_SIGNED = ("signed_distances", "occupancy", "features", "normals")
+
+
+def Solid(mesh, ctx=None):
+    """The topology handle (_lib.Solid) of a model: `mesh` is a holder with .vertices / .triangles or a (vertices,
+    triangles) pair in the model frame.  Built once per model, whatever the pose; `.info` reports whether the mesh is
+    closed (boundary_edges, nonmanifold_edges, flipped_edges), its orientation and its volume."""
+    from .defect_map import _model_arrays
+
+    try:
+        v, t = _model_arrays(mesh)
+    except _lib.PedpError as e:
+        raise _lib.PedpError(str(e).replace("DefectMap:", "Solid:")) from None
+    return _lib.Solid(ctx or _lib.default_context(), v, t)
+
+
+def _context_of(ctx, solid):
+    """The context a signed query builds a holder's device mesh on: the caller's, else the solid's, else _mesh_of's choice."""
+    return ctx if ctx is not None or solid is None else solid.ctx
+
+
+def _signed_query(name, mesh, points, want, solid, ctx):
+    lead, n = _leading_shape(name, points)
+    if solid is not None and not isinstance(solid, _lib.Solid):
+        raise _lib.PedpError(f"{name}: solid must be a Solid, got {type(solid).__name__}")
+    if solid is None and isinstance(mesh, _lib.Mesh):
+        raise _lib.PedpError(f"{name}: a _lib.Mesh keeps no model to build the solid from: pass solid=Solid(model)")
+    dev = device_of(points)
+    m = _mesh_of(name, mesh, _context_of(ctx, solid), dev)
+    if dev is not None and (dev.index or 0) != m.ctx.device:
+        raise _lib.PedpError(f"{name}: points are on {dev}, the mesh on cuda:{m.ctx.device}")
+    own = solid is None
+    if own:
+        solid = Solid(mesh, m.ctx)
+    elif solid.ctx is not m.ctx:
+        raise _lib.PedpError(f"{name}: the solid belongs to another context than the mesh")
+    p = as_array(points, dev, np.float64).reshape(n, 3)
+    out = {k: empty(dev, lead + (() if w is None else (w,)), t) for k, (w, t) in _lib.Solid.SIGNED_OUTPUTS.items() if k in want}
+    try:
+        if n:
+            launch(dev, "pedp_signed_distance", lambda lib, h, mem: lib.pedp_signed_distance(
+                h, m._h, solid._h, ptr(p), n, mem, ptr(out.get("signed_distances")), ptr(out.get("occupancy")),
+                ptr(out.get("features")), ptr(out.get("normals"))), m.ctx)
+    finally:
+        if own:                        # the call's solid goes with the call: nothing enqueued may still read it
+            if dev is not None:
+                m.ctx.synchronize()
+            solid.close()
+    return {k: as_kind(v, points) for k, v in out.items()}
+
+
+def compute_signed_distance(mesh, points, solid=None, ctx=None):
+    """RaycastingScene.compute_signed_distance: compute_distance with the sign of the solid, negative inside.  `mesh` and
+    `points` as for closest_points; `solid` is the model's Solid (required when `mesh` is a _lib.Mesh; built for the call
+    from a holder's own vertices and triangles when None).  Exact for a closed, consistently oriented mesh and a point
+    off the surface; a mesh that bounds no solid is refused."""
+    return _signed_query("compute_signed_distance", mesh, points, ("signed_distances",), solid, ctx)["signed_distances"]
+
+
+def compute_occupancy(mesh, points, solid=None, ctx=None):
+    """RaycastingScene.compute_occupancy: int8, 1 where the point is inside the solid (signed distance < 0), else 0."""
+    return _signed_query("compute_occupancy", mesh, points, ("occupancy",), solid, ctx)["occupancy"]
+
+
+def signed_closest_points(mesh, points, solid=None, ctx=None):
+    """closest_points' dict and, with it, signed_distances (float64), occupancy (int8), features (uint8: 0 face, 1 edge,
+    2 vertex, 255 none) and normals (... x 3 float64: the outward unit pseudonormal of the closest feature)."""
+    name = "signed_closest_points"
+    if not isinstance(mesh, _lib.Mesh) and hasattr(mesh, "vertices"):      # one device mesh, one solid for both calls
+        m = _mesh_of(name, mesh, _context_of(ctx, solid), device_of(points))
+        own = Solid(mesh, m.ctx) if solid is None else None
+        try:
+            return signed_closest_points(m, points, own or solid, m.ctx)
+        finally:
+            if own is not None:
+                m.ctx.synchronize()
+                own.close()
+    out = _query(name, mesh, points, _OUTPUTS, _context_of(ctx, solid))[0]
+    out.update(_signed_query(name, mesh, points, _SIGNED, solid, ctx))
+    return out
+
+
+def signed_deviation(depth, K, mesh, solid, unit=1000.0, mask=None, zmin=0.001, ctx=None):
+    """The signed distance of every measured depth point from the posed CAD solid: H x W float64 of the caller's kind,
+    negative where the measured surface lies inside the solid (a dent), positive outside (a bump), NaN where the pixel is
+    invalid by deviation_heatmap's rule (depth < zmin, or `mask` unset).  depth, K, unit, mask and zmin as for
+    deviation_heatmap; `solid` as for compute_signed_distance."""
+    shape = tuple(depth.shape) if hasattr(depth, "shape") else None
+    if shape is None or len(shape) != 2:
+        raise _lib.PedpError(f"signed_deviation: depth must be H x W, got {shape if shape is not None else type(depth).__name__}")
+    if mask is not None and tuple(mask.shape) != shape:
+        raise _lib.PedpError(f"signed_deviation: mask must be {shape[0]} x {shape[1]} like depth, got {tuple(mask.shape)}")
+    from .depth_filters import depth2xyzmap
+
+    if is_torch(depth) and not depth.is_cuda:
+        import torch
+
+        return torch.from_numpy(signed_deviation(depth.numpy(), K, mesh, solid, unit, None if mask is None else np.asarray(mask),
+                                                 zmin, ctx))
+    xyz = depth2xyzmap(depth, K)
+    pts = (xyz.double() if is_torch(xyz) else xyz.astype(np.float64)) * unit
+    sd = compute_signed_distance(mesh, pts, solid, ctx)
+    if is_torch(sd):
+        import torch
+
+        keep = depth >= zmin
+        if mask is not None:
+            keep = keep & torch.as_tensor(mask, device=sd.device).bool()
+        return torch.where(keep, sd, torch.full_like(sd, float("nan")))
+    keep = np.asarray(depth) >= zmin
+    if mask is not None:
+        keep &= np.asarray(mask).astype(bool)
+    return np.where(keep, sd, np.nan)
+
+
+def split_deviation(sd, saturation, gate):
+    """(excess, missing): the two heat maps of a frame's signed distances `sd` (signed_deviation's), deviation_heatmap's
+    arithmetic on |sd| -- min(|sd| / saturation, 1) where |sd| <= gate, 0 elsewhere and where sd is NaN -- kept where
+    sd > 0 (outside the solid: excess material) and where sd < 0 (inside: missing material).  Each is ready for
+    project_heatmap / DefectMap.add_projection, and excess + missing is deviation_heatmap of the same frame."""
+    if not (saturation > 0 and gate >= 0):
+        raise _lib.PedpError(f"split_deviation: saturation must be positive and gate non-negative, got {saturation} and {gate}")
+    if is_torch(sd):
+        import torch
+
+        dist = sd.abs()
+        heat = torch.where(dist <= gate, torch.clamp(dist / saturation, max=1.0), torch.zeros_like(dist))
+        zero = torch.zeros_like(heat)
+        return torch.where(sd > 0, heat, zero), torch.where(sd < 0, heat, zero)
+    sd = np.asarray(sd, dtype=np.float64)
+    dist = np.abs(sd)
+    with np.errstate(invalid="ignore"):
+        heat = np.where(dist <= gate, np.minimum(dist / saturation, 1.0), 0.0)
+        return np.where(sd > 0, heat, 0.0), np.where(sd < 0, heat, 0.0)
 
 
 def align_to_mesh(defect_points, mesh, offset=0.1, ctx=None):

@@ -427,7 +427,7 @@ int pedp_icp(pedp_ctx_t ctx, pedp_cloud_t source, pedp_cloud_t target,
  * point-cloud operations and pedp_preprocess_source, pedp_cloud_create(_device), the renderer, crops, pose arithmetic,
  * statistics and the network kernels -- and may be used on the context in between: it gives the bits it gives on a fresh
  * context, and the registration ends with pedp_icp's bits (tests/test_call_history_gpu.py runs each of them in that
- * window; DESIGN.md s4.18 lists what each touches).  A PEDP_HOST call among them returns after the registration's passes,
+ * window; DESIGN.md s4.19 lists what each touches).  A PEDP_HOST call among them returns after the registration's passes,
  * so only PEDP_DEVICE calls overlap with it.  Destroying the context or either cloud with a registration pending is an
  * error of the caller.  want_trace: pedp_icp_end's `trace` may be non-null.  The reference has no counterpart (registration_icp is one blocking call,
  * src/pose_estimation.py:447-453). */
@@ -911,6 +911,72 @@ int pedp_defect_map_faces(pedp_defect_map_t map, int mem, double *peak, int64_t 
 int pedp_defect_map_stats(pedp_defect_map_t map, int64_t *observations, int64_t *rows_added, int64_t *rows_ignored);
 int pedp_defect_map_regions(pedp_defect_map_t map, double threshold, int32_t min_frames, int32_t grow, int mem, int32_t *labels,
                             int64_t capacity, pedp_defect_region *table, int64_t *n_regions);
+
+/* ---------------------------------------------------------------- the solid: signed distance and occupancy
+ * RaycastingScene.compute_signed_distance / compute_occupancy on the mesh handle: whether a point lies inside the CAD
+ * solid (a dent, missing material) or outside it (a burr, excess material), which `side` above cannot tell away from
+ * the inside of a face.  The contract is DESIGN.md s4.18.
+ *
+ * pedp_solid_create: the topology of the model, built once from verts V x 3 float64 and tris F x 3 on the host (the
+ * arrays a mesh handle or a defect map is made from), independent of any pose.  Bounds and errors as
+ * pedp_defect_map_create; the weld and the edge slots are the defect map's (one implementation):
+ *   weld         as above: == on the positions, -0 equals +0, a vertex with a NaN welds to nothing
+ *   edge slot    3 f + k joins corners k and (k + 1) % 3 of face f.  The slots of one unordered pair of welded vertices
+ *                form an edge: one slot is a BOUNDARY edge, three or more a NON-MANIFOLD edge, two are TWINS if the two
+ *                faces run through the edge in opposite directions and a FLIPPED edge if in the same
+ *   volume       the sum over the faces of a . (b x c) / 6 on the float64 vertices (cross and dot as above), in a fixed
+ *                order: thread t of a block of 256 adds its faces t, t + 256, ... of the block's 4096 one after the
+ *                other, the threads' sums are added pairwise (t with t + 128, t + 64, ... t + 1), and one block adds
+ *                the blocks' sums in the same way.  No floating-point atomic
+ * Creation succeeds on any mesh; `closed` says whether the mesh bounds a solid (a check of a CAD export on its own).
+ * The handle keeps the index buffer, the welded id of every corner, the twin of every edge slot and, per welded vertex,
+ * its corners sorted by (face, corner).  The call waits on the context's stream (PEDP_ERR_BAD_ARG while a registration
+ * is pending on ctx).
+ *
+ * pedp_signed_distance: the closest point c of every point p is the one of the search above (the same kernels, the same
+ * cull, the same expressions), and the rule 1 ... 7 that decided (v, w) for the chosen triangle names the closest
+ * FEATURE, whose angle-weighted pseudonormal N (Baerentzen & Aanaes 2005) is formed from the mesh's records AS POSED,
+ * with n(f) = (ab x ac) / |ab x ac| as pedp_mesh_face_normals forms it:
+ *   rule 7           the face: N = n(f)
+ *   rules 3, 6, 5    the edge slots 0, 1, 2: N = n(f) + n(face of the twin slot) componentwise
+ *   rules 1, 2, 4    the corners 0, 1, 2: N = the sum, over the corners of the welded vertex in (face, corner) order
+ *                    starting from 0, of n(g) angle, with angle = atan2(|q x s|, q . s) between the record's two edges
+ *                    that leave the corner: (ab, ac), (ac - ab, -ab), (-ac, ab - ac) for corner 0, 1, 2
+ *   A record that the search skips, or whose ab x ac has no length, adds nothing to an edge's or a vertex's N.
+ *   sign             s = ((p - c) . N) orientation; sdist = s < 0 ? -dist : dist, so s == 0 counts as outside;
+ *                    |sdist| has the bits of pedp_closest_points' dist.  occupancy = sdist < 0.  feature = 0 / 1 / 2
+ *                    for face / edge / vertex.  normal = (N / sqrt(N . N)) orientation: the outward unit pseudonormal
+ *                    (NaN where N is zero)
+ *   non-finite       a point with a NaN / infinite coordinate: sdist NaN, occupancy 0, feature 255, normal NaN; no
+ *                    triangle left (F = 0, all skipped): sdist +inf, occupancy 0, feature 255, normal NaN
+ *   determinism      as pedp_closest_points: a point's outputs depend on that point, the records and the solid alone
+ * The sign is exact -- it IS the inside / outside of the solid -- for a closed, consistently oriented mesh and a point
+ * that is not on the surface; where rounding moves a point from one of Ericson's regions to a neighbouring one the two
+ * features' pseudonormals give the same sign, by continuity.  For a point within rounding of the surface itself
+ * (dist of the order of the records' float32 resolution) the sign is a convention, as `side` is on edges and vertices.
+ * PEDP_ERR_BAD_ARG: the solid is not closed (boundary, non-manifold or flipped edges) or has orientation 0, unless
+ * F = 0; solid F != mesh F; a posable mesh, which keeps its index buffer, whose indices differ from the solid's
+ * (compared on the device at the first call with that mesh, which therefore waits on the stream); a mesh or a solid
+ * of another context; N > 2^24; a registration pending on ctx -- in either memory: the workspace (the vertices' table
+ * and the search's outputs) is the solid's own and is sized by V and N, so that the call may have to wait for the
+ * device to grow it.  Never the pinned result block, never the ICP workspace.  pts N x 3; every output may be null;
+ * all pointers host or device memory by `mem`; PEDP_DEVICE only enqueues on the context's stream (after the first call). */
+typedef struct pedp_solid_s *pedp_solid_t;
+typedef struct pedp_solid_info {
+    int64_t V, F, welded_vertices, edges;
+    int64_t boundary_edges;     /* edges with one face */
+    int64_t nonmanifold_edges;  /* edges with three or more faces */
+    int64_t flipped_edges;      /* two-face edges that both faces run through in the same direction */
+    int64_t degenerate_faces;   /* two corners weld to one vertex */
+    int32_t closed;             /* 1 iff the three edge counts above are all zero and F > 0 */
+    int32_t orientation;        /* sign of volume: +1 normals point out, -1 in, 0 */
+    double  volume;             /* sum over faces of a . (b x c) / 6, float64, fixed order */
+} pedp_solid_info;
+int pedp_solid_create(pedp_ctx_t ctx, const double *verts, int64_t V, const uint32_t *tris, int64_t F, pedp_solid_t *out);
+int pedp_solid_destroy(pedp_solid_t solid);
+int pedp_solid_get_info(pedp_solid_t solid, pedp_solid_info *out);
+int pedp_signed_distance(pedp_ctx_t ctx, pedp_mesh_t mesh, pedp_solid_t solid, const double *pts, int64_t N, int mem,
+                         double *sdist, int8_t *occupancy, uint8_t *feature, double *normal);
 
 /* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
  * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
