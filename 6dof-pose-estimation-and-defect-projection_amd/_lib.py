@@ -124,6 +124,7 @@ PROTOTYPES = {
     "pedp_icp_last_head_closed": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_certified": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_steady": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
+    "pedp_icp_last_steady_followers": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "pedp_debug_icp_path": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
@@ -884,13 +885,21 @@ def icp_last_steady(ctx):
     return a.value, b.value
 
 
+def icp_last_steady_followers(ctx):
+    """Workgroups of the last single icp()'s last steady launch that took a closed pass's state from a closer's record
+    instead of closing the pass themselves (pedp_icp_last_steady_followers); PEDP_ICP_STEADY_CLOSERS sets the closers."""
+    a = C.c_int64(0)
+    check(load().pedp_icp_last_steady_followers(ctx._h, C.byref(a)), "pedp_icp_last_steady_followers")
+    return a.value
+
+
 ICP_SWITCHES = ("nn_f32", "unfused_finish", "no_visit_plan", "serial_close", "copy_bracket", "head_close", "cert", "steady")
 ICP_PATH_FIELDS = ("fused", "dev_result", "copy_bracket", "head", "certify", "plan", "serial_close", "unfused_finish", "exchange",
                    "steady", "steady_from")
 
 
 class IcpSwitches(C.Structure):     # pedp_icp_switches
-    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order")]
+    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order", "steady_closers")]
 
 
 class IcpPathInputs(C.Structure):   # pedp_icp_path_inputs

@@ -109,7 +109,8 @@ struct IcpState {
     int n_wide;                // passes of this registration closed by the wide close (statistics: tests check it was in force)
     int n_head;                // passes of this registration closed at the head of the next launch (statistics, as n_wide)
     int n_steady;              // passes of this registration run inside a steady launch (steady_pass.h; statistics)
-    int reserved_;
+    int n_followed;            // workgroups that followed a closer in the last steady launch (statistics; the word was a spare one:
+                               // the state did not grow, and only the launch's service workgroup writes it, once, at exit)
     double T_init[16];         // the start transformation: slot 0 of the update history (arrives with the state, no copy of its own)
     long long sum_cert, sum_searched;  // candidate slots whose search a certificate replaced / that searched, summed over passes (statistics)
 };

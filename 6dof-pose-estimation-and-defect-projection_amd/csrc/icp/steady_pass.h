@@ -10,10 +10,19 @@
 //                sixteen counters (a line each; the sign-off counters of the generic kernel, cumulative, base in the
 //                state); lanes 0-15 poll them with sc1 loads and s_sleep until all have arrived -- at most
 //                STEADY_SPIN_CAP looks, then the registration fails loudly (done = -1).  No fence.
-//   the close    EVERY workgroup then closes pass p itself: icp_finish_body in its coherent head mode (MODE 3) -- the
-//                head close's sequence on sc1 loads of the partials -- and goes on with pass p + 1 from the state in
-//                its LDS.  One workgroup (the last rank: it has the fewest chunks) also writes what a head close leaves
-//                behind: the row of the trace, the history slot, the packet.
+//   the close    the ranks below C = min(ranks, closers) -- the CLOSERS; `closers` is the device's CU count unless
+//                PEDP_ICP_STEADY_CLOSERS says otherwise -- then close pass p themselves: icp_finish_body in its coherent
+//                head mode (MODE 3) -- the head close's sequence on sc1 loads of the partials -- and go on with pass
+//                p + 1 from the state in their LDS.  The last closer also writes what a head close leaves behind: the
+//                row of the trace, the history slot, the packet.
+//   followers    The other ranks FOLLOW: with more ranks than CUs the dispatcher puts rank n_cu + k on the CU of rank k,
+//                and a second close there pulls the same partial sums through the same vector memory path and runs the
+//                same solve for the same bits, late for both.  A closer that has a follower (rank + C is a rank)
+//                publishes what it goes on with -- the state in its LDS and the searched / certified word -- before it
+//                begins its chunk: write-through stores by one wave, which drains them, then the tag (nonce + pass + 1),
+//                write-through as well.  No fence.  Follower r polls the tag of closer r % C (sc1 loads, s_sleep, the
+//                same cap and the same failure), copies the record into its LDS with sc1 loads and takes the branches
+//                the closer took.  Where the dispatcher places a workgroup decides the gain only, never the result.
 //   two copies   of the partial sums suffice: a workgroup stores pass p + 2 only after all have arrived for p + 1,
 //                which they do after reading p.
 //
@@ -47,13 +56,51 @@ namespace {
 
 constexpr unsigned STEADY_SPIN_CAP = 1u << 21;  // looks at the counters before a hand-over gives up
 constexpr int STEADY_HANDBACK = 2;              // `done` of the page-locked copy of a state that was handed back
+// A closer's record for its followers: the state (SWORDS doubles), the searched / certified word behind it, and the tag in
+// a line of its own.  Each closer has one slot in each of two copies by the parity of the pass the record closes.  Two
+// copies suffice, as for the partial sums: a closer writes copy (p + 1) & 1 only behind the hand-over of pass p + 1; that
+// hand-over counts its followers; and the followers arrive there only after they have read copy p & 1 -- so nobody still
+// reads the copy of pass p - 1 that the record of pass p + 1 replaces.  The tag names the registration (its nonce) and
+// the pass: a record that an earlier registration or an earlier pass left in the slot never matches.
+constexpr int FOLLOW_STRIDE = 128;  // doubles per slot
+constexpr int FOLLOW_TAG = 112;     // the tag's double inside the slot (byte 896: the slot's last 128-byte line)
+static_assert(sizeof(IcpState) / sizeof(double) + 1 <= FOLLOW_TAG, "the record ends in front of the tag's line");
 
 __device__ __forceinline__ float load_sc1(const float *p) {
     return __uint_as_float(__hip_atomic_load((g_u32 *)(uintptr_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
+// A follower's close: wave 0 polls the tag of its closer's record, then the workgroup copies the record -- the state into
+// `cur`, the searched / certified word to where the close leaves it.  false: the tag did not come within the cap.
+// (Inlined: as a function of its own it cost the kernel more spilled registers than it saved)
+__device__ __forceinline__ bool steady_follow(IcpState *cur, double *word, int *failed, const double *rec, unsigned tag) {
+    constexpr int SWORDS = (int)(sizeof(IcpState) / sizeof(double));
+    typedef double __attribute__((may_alias)) state_word;
+    if (threadIdx.x < 64) {
+        for (unsigned spins = 0;; ++spins) {
+            const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load((g_u32 *)(uintptr_t)(rec + FOLLOW_TAG), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            if (t == tag) break;
+            if (spins > STEADY_SPIN_CAP) {  // bounded, as the hand-over is
+                if (threadIdx.x == 0) *failed = 1;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(2);
+        }
+    }
+    __syncthreads();
+    if (*failed != 0) return false;  // (workgroup-uniform)
+    if (threadIdx.x <= SWORDS) {
+        const double v = load_sc1(&rec[threadIdx.x]);
+        if (threadIdx.x < SWORDS) ((state_word *)cur)[threadIdx.x] = v;
+        else *word = v;
+    }
+    __syncthreads();
+    return true;
+}
+
 // a0.launch: the first pass this launch may run (what a generic launch of that index would run)
-__global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0, const PassArgs a0) {
+// follow: the closers' records, [2][follow_cap] slots (null: every rank closes); closers: see above (< 1: every rank)
+__global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0, const PassArgs a0, double *follow, int follow_cap, int closers) {
     constexpr int W = BK_W;
     static_assert(W == 8 && CH == 128, "a chunk is two halves of four 16-slot sub-blocks");
     __shared__ IcpState cur;
@@ -66,6 +113,7 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
     __shared__ float wcs[W][3][16], wrho[W][16], wcert[W][16];
     __shared__ int wpi[W][16], wkk[W][16], wfj[W][16], misc[4];
     __shared__ float4 wsph0[64];
+    __shared__ double *role_rec[2];  // this workgroup's record in either copy: its own (a closer) or its closer's (a follower)
     // The workgroup's first chunk stays resident from its first pass in this launch on, by position in the chunk: the
     // point (two copies by pass parity, like Pk: the four waves of a half read a pass's input while quarter 0 writes
     // its output), last pass's neighbour with its normal, the certificate, the neighbour's and the point's index.  Of
@@ -107,7 +155,23 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
         if (threadIdx.x == 0) __hip_atomic_fetch_add(counters + 32 * (blockIdx.x & 15), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    const bool service = (int)blockIdx.x == n_part - 1;
+    // Closer or follower, and where this workgroup's record lies: decided once and parked in LDS -- the kernel is at its
+    // register cap, and a close needs these once per pass.
+    bool service;
+    {
+        int C = follow != nullptr && closers >= 1 && closers < n_part ? closers : n_part;
+        C = C > follow_cap ? n_part : C;  // (the host sizes the slots for every grid it launches)
+        const bool closer = (int)blockIdx.x < C;
+        const bool publishes = closer && (int)blockIdx.x + C < n_part;  // some follower's rank % C is this rank
+        service = (int)blockIdx.x == C - 1;  // (a closer: what it writes comes out of the close's LDS)
+        if (threadIdx.x == 0) {
+            misc[1] = (closer ? 1 : 0) | (publishes ? 2 : 0);
+            misc[2] = n_part - C;
+            for (int k = 0; k < 2; ++k)
+                role_rec[k] = C < n_part ? follow + ((size_t)k * follow_cap + (size_t)((int)blockIdx.x % C)) * FOLLOW_STRIDE : nullptr;
+        }
+        __syncthreads();
+    }
     // the visit plan of the launch's first pass, where there is one, holds for all of them (one chunk per workgroup)
     const bool planned = a0.visit != nullptr && n_live <= G && vis[2] == uni(cur.nonce) + a0.launch + 1 && vis[3] == n_live;
     const double dinf = __longlong_as_double(0x7FF0000000000000ll);
@@ -153,6 +217,8 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
     auto leave = [&](bool handback) {
         if (!service) return;
         const int tid = threadIdx.x;
+        if (tid == 0) cur.n_followed = misc[2];
+        __syncthreads();
         const int next = uni(cur.done) != 0 ? uni(cur.pass) + 1 : uni(cur.pass);  // (a stop leaves `pass` at the pass it closed)
         if (tid < SWORDS) ((PEDP_GLOBAL state_word *)(uintptr_t)(st0 + (next & 1)))[tid] = ((const state_word *)&cur)[tid];
         if (tid == 0 && handback) as_global(&(st0 + ((next + 1) & 1))->pass)[0] = -1;
@@ -168,12 +234,18 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
         if (need_close) {
             // ---- the close of pass p - 1, by every workgroup: same inputs, same float64 sequence, same bits
             const int q = p - 1;
-            FinishArgs f;
-            f.live = nullptr; f.live_list = nullptr; f.n_lw = 0; f.partials = a0.partials + (size_t)(q & 1) * a0.part_stride; f.packet = nullptr; f.phase = 0;
-            f.estimator = a0.estimator; f.trace = nullptr; f.hist = nullptr; f.bcx = a0.bc[0]; f.bcy = a0.bc[1]; f.bcz = a0.bc[2];
-            f.serial = 0;
-            f.known = 1; f.k_pass = q; f.k_rebuild = 0; f.k_n_live = n_live;
-            icp_finish_body<W * 64, 1, true, 3>(&cur, f, fin, threadIdx.x);  // (ends behind a barrier)
+            const bool closer = (uni(misc[1]) & 1) != 0;
+            if (closer) {
+                FinishArgs f;
+                f.live = nullptr; f.live_list = nullptr; f.n_lw = 0; f.partials = a0.partials + (size_t)(q & 1) * a0.part_stride; f.packet = nullptr; f.phase = 0;
+                f.estimator = a0.estimator; f.trace = nullptr; f.hist = nullptr; f.bcx = a0.bc[0]; f.bcy = a0.bc[1]; f.bcz = a0.bc[2];
+                f.serial = 0;
+                f.known = 1; f.k_pass = q; f.k_rebuild = 0; f.k_n_live = n_live;
+                icp_finish_body<W * 64, 1, true, 3>(&cur, f, fin, threadIdx.x);  // (ends behind a barrier)
+            } else if (!steady_follow(&cur, &fin.pk[PACKET + 2], &misc[0], role_rec[q & 1], (unsigned)(uni(cur.nonce) + q + 1))) {
+                if (threadIdx.x == 0 && a0.down) *(int *)((char *)a0.down + offsetof(IcpState, done)) = -1;
+                return;
+            }
             PEDP_RT(p, 7);
             // candidate slots of pass q that searched / that a certificate served (all workgroups agree: the same sums)
             const double pk31 = fin.pk[PACKET + 2];
@@ -183,7 +255,7 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
             // (a pass a generic launch ran counts its slots by waves -- a wave with one uncertified slot searches all sixteen --
             // and says little about the next pass here: the share decides only behind a pass of this launch)
             const bool handback = !stopped && (uni(cur.rebuild) != 0 || (q >= a0.launch && searched * 8 > searched + certified));
-            if (threadIdx.x == 0) {
+            if (closer && threadIdx.x == 0) {  // (a follower's state has all of this in it)
                 if (q >= a0.launch) cur.n_steady += 1;  // (the pass ran in this launch)
                 if (q >= max_iter) cur.n_head -= 1;  // the last pass counts as closed in its launch, as it is without this kernel
                 cur.idle_base = base0 + arrivals;
@@ -197,6 +269,13 @@ __global__ __launch_bounds__(BK_W * 64, 4) void icp_steady_kernel(IcpState *st0,
                 if (!stopped && tid < PACKET) as_global(sa.packet)[tid] = fin.pk[tid];
             }
             __syncthreads();
+            if ((uni(misc[1]) & 2) != 0 && threadIdx.x < 64) {  // one wave: the record, its drain, the tag
+                double *const rec = role_rec[q & 1];
+                const unsigned tag = (unsigned)(uni(cur.nonce) + q + 1);
+                for (int k = threadIdx.x; k <= SWORDS; k += 64) store_sc1(&rec[k], k < SWORDS ? ((const state_word *)&cur)[k] : pk31);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (threadIdx.x == 0) __hip_atomic_store((g_u32 *)(uintptr_t)(rec + FOLLOW_TAG), tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             if (stopped || handback) {
                 if (handovers == 0 && !hand_over(31)) return;
                 if (threadIdx.x == 0) cur.idle_base = base0 + arrivals;

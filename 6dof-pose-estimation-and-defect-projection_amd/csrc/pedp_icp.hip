@@ -115,6 +115,8 @@ struct IcpWorkspace {
     int qt;  // MFMA tiles per target unit for this call (1: culled registration, 4: dense sweep)
     // fused pass (qt == 1 inside a registration)
     double *Pk, *hist, *cpart, *Tprev;
+    double *follow;  // the records of a steady launch's closers, [2][follow_cap] slots of FOLLOW_STRIDE doubles (steady_pass.h)
+    int follow_cap;
     float *cert;   // certificates, two copies by pass parity (see PassArgs)
     unsigned *ticket;
     unsigned long long *live;
@@ -161,7 +163,7 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
     // Every buffer is named once: take() lays it behind the ones before it, 256-byte aligned, and notes where its
     // pointer lives in w; the pointers are set once the executor's scratch buffer is known to be large enough.
     size_t off = 0;
-    constexpr int MAX_SLOTS = 32;  // (31 buffers below)
+    constexpr int MAX_SLOTS = 32;  // (32 buffers below)
     struct { size_t member, off; } slot[MAX_SLOTS];  // byte offset of the pointer inside w, of the buffer inside the block
     int n_slots = 0;
     auto take = [&](auto *&p, size_t bytes) {
@@ -204,6 +206,9 @@ int carve_workspace(pedp_ctx_t c, int64_t Ns, int64_t Nt, int max_iter, int qt, 
         take(w.cert, sizeof(float) * (size_t)w.Ns_pad * (poses <= 1 ? 2 : 0));  // likewise (a batch keeps none)
         take(w.hist, sizeof(double) * 16 * (size_t)iter_capacity(max_iter));
         take(w.cpart, sizeof(double) * PSTRIDE * (size_t)w.blocks_cap * 2);  // two copies by pass parity (head close; else the first)
+        // a steady launch's ranks are live chunks and workgroups of its grid, at most two per CU: a slot for each, both parities
+        w.follow_cap = poses <= 1 ? (int)(w.blocks_cap < 2 * c->num_cus ? w.blocks_cap : 2 * c->num_cus) : 0;
+        take(w.follow, sizeof(double) * FOLLOW_STRIDE * 2 * (size_t)w.follow_cap);
         // the ticket and the sixteen sign-off counters, a line each, and the live masks right behind them: one span
         // that starts every registration at zero (zeroed_span_bytes) -- nothing may come between these two
         take(w.ticket, 17 * 128);
@@ -291,6 +296,7 @@ inline const IcpSwitches &icp_switches() {
         s.copy_bracket = flag("PEDP_ICP_COPY_BRACKET", 0); s.head_close = flag("PEDP_ICP_HEAD_CLOSE", 1);
         s.cert = flag("PEDP_ICP_CERT", 1); s.steady = flag("PEDP_ICP_STEADY", 1);
         s.steady_from = num("PEDP_ICP_STEADY_FROM", 5); s.steady_grid = num("PEDP_ICP_STEADY_GRID", 0);
+        s.steady_closers = num("PEDP_ICP_STEADY_CLOSERS", 0);
         s.target_order = order && !strcmp(order, "hilbert") ? PEDP_TARGET_ORDER_HILBERT
                          : order && !strcmp(order, "compact") ? PEDP_TARGET_ORDER_COMPACT : PEDP_TARGET_ORDER_AUTO;
         return s;
@@ -476,8 +482,12 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpJob &job, const PassLaunch &l) {
     if (g < 1) g = 1;
     if (pa.head) g += 1;  // head close: one workgroup more than the chunks can fill (the service workgroup)
     if (l.ev0) PEDP_HIP_CHECK(hipEventRecord(l.ev0, c->stream));
-    if (l.steady_launch)
-        hipLaunchKernelGGL(icp_steady_kernel, dim3((unsigned)steady_grid(c)), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
+    if (l.steady_launch) {
+        // ranks below `closers` close a pass, the others follow one of them: one closer per CU unless the switch says otherwise
+        const int asked = icp_switches().steady_closers;
+        hipLaunchKernelGGL(icp_steady_kernel, dim3((unsigned)steady_grid(c)), dim3(BK_W * 64), 0, c->stream, job.w.st, pa,
+                           job.w.follow_cap > 0 ? job.w.follow : nullptr, job.w.follow_cap, asked > 0 ? asked : c->num_cus);
+    }
     else if (job.in.poses > 1)
         hipLaunchKernelGGL((icp_pass_kernel<BK_W, true>), dim3((unsigned)g, (unsigned)job.in.poses), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
     else
@@ -988,6 +998,7 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     x->icp_last_searched = hp->sum_searched;
     x->icp_last_steady = hp->n_steady;
     x->icp_last_handbacks = handbacks;
+    x->icp_last_followed = hp->n_followed;
     x->icp_last_rebuilds = hp->n_rebuilds;
     x->icp_last_bracket = (job.path.copy_bracket ? 0 : 1) + (job.path.dev_result ? 2 : 0);
     x->icp_last_nt = job.in.n_target;
@@ -1518,6 +1529,12 @@ int pedp_icp_last_steady(pedp_ctx_t c, int64_t *passes, int64_t *handbacks) {
     PEDP_REQUIRE(c && passes, "pedp_icp_last_steady: null argument");
     *passes = c->icp_last_steady;
     if (handbacks) *handbacks = c->icp_last_handbacks;
+    return PEDP_OK;
+}
+
+int pedp_icp_last_steady_followers(pedp_ctx_t c, int64_t *followers) {
+    PEDP_REQUIRE(c && followers, "pedp_icp_last_steady_followers: null argument");
+    *followers = c->icp_last_followed;
     return PEDP_OK;
 }
 

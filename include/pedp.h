@@ -554,7 +554,7 @@ int pedp_icp_last_certified(pedp_ctx_t ctx, int64_t *slots, int64_t *searched_sl
  * a launch handed the registration back to the generic pass kernel (`handbacks`, may be null).  A registration that closes
  * its passes at the head of the next launch and keeps certificates (the two read-outs above) runs its passes from
  * PEDP_ICP_STEADY_FROM (default 5) on in ONE launch of a resident grid: per pass a bounded device-wide hand-over of the
- * partial sums replaces the launch boundary, every workgroup closes the pass itself, and a slot without a certificate runs
+ * partial sums replaces the launch boundary, one workgroup per CU closes the pass itself (below), and a slot without a certificate runs
  * the exact search.  The launch hands back when a close asks for a rebuild of the live set or more than 1/8 of a pass's
  * candidate slots searched; pedp_icp_end / pedp_icp then run two generic launches and the steady launch again.
  * PEDP_ICP_STEADY=0 (read once per process): 0 passes; so do batches, sharded registrations, captured graphs, a timed_pass
@@ -565,6 +565,13 @@ int pedp_icp_last_certified(pedp_ctx_t ctx, int64_t *slots, int64_t *searched_sl
  * PEDP_ICP_STEADY_GRID=n caps the launch's workgroups (tests).  Results do not change in any bit
  * (tests/test_icp_steady_gpu.py compares). */
 int pedp_icp_last_steady(pedp_ctx_t ctx, int64_t *passes, int64_t *handbacks);
+
+/* Workgroups of the last steady launch of the last single registration collected on `ctx` that FOLLOWED: they closed no pass
+ * themselves but took the closed state from a record one of the closers published (csrc/icp/steady_pass.h).  The ranks below
+ * min(ranks, closers) close, the others follow; `closers` is the device's CU count, or PEDP_ICP_STEADY_CLOSERS=n (read once
+ * per process; unset or 0: the CU count; n at least the launch's grid: every rank closes, 0 followers; small n: tests).
+ * 0 where no steady launch ran.  Results do not change in any bit (tests/test_icp_steady_followers_gpu.py compares). */
+int pedp_icp_last_steady_followers(pedp_ctx_t ctx, int64_t *followers);
 
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
@@ -586,6 +593,7 @@ typedef struct pedp_icp_switches {  /* the environment switches, read once per p
     int steady_from;  /* default 5 */
     int steady_grid;  /* cap of a steady launch's workgroups (tests); 0: none */
     int target_order; /* PEDP_TARGET_ORDER_*: hilbert | compact decide for every cloud in automatic mode */
+    int steady_closers; /* ranks of a steady launch that close a pass themselves; 0: the device's CU count */
 } pedp_icp_switches;
 typedef struct pedp_icp_path_inputs {
     int64_t n_source, n_target; /* source points, finite target rows */

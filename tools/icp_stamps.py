@@ -14,8 +14,10 @@ PKG = os.path.join(ROOT, "6dof-pose-estimation-and-defect-projection_amd")
 spec = importlib.util.spec_from_file_location("pedp_build", os.path.join(PKG, "build.py"))
 b = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(b)
-out = os.path.join(PKG, "libpedp_hip_stamps.so")
-b.build(force=not os.path.exists(out), verbose=False, extra_flags=["-DPEDP_ICP_STAMPS=1"], out=out)
+out = os.environ.get("PEDP_STAMPS_LIB")  # a stamps library built beforehand (of another revision, say): used as it is
+if not out:
+    out = os.path.join(PKG, "libpedp_hip_stamps.so")
+    b.build(force=not os.path.exists(out), verbose=False, extra_flags=["-DPEDP_ICP_STAMPS=1"], out=out)
 os.environ["PEDP_LIB"] = out
 import numpy as np
 from pedp_hip import _lib, synth
@@ -29,6 +31,12 @@ src = _lib.Cloud(ctx, f.scene(depth)); tgt = _lib.Cloud(ctx, f.model_points, f.n
 for _ in range(3):
     _lib.icp(ctx, src, tgt, 10.0, f.icp_init(), max_iteration=iters, relative_fitness=-1, relative_rmse=-1)
 lib = C.CDLL(out)
+n_cu = C.c_int(0)
+if C.CDLL("libamdhip64.so").hipDeviceGetAttribute(C.byref(n_cu), 63, 0) != 0:  # hipDeviceAttributeMultiprocessorCount
+    n_cu = C.c_int(0)
+n_cu = int(os.environ.get("PEDP_N_CU", n_cu.value))
+if hasattr(lib, "pedp_icp_last_steady_followers"):
+    print(f"steady launch: {_lib.icp_last_steady(ctx)[0]} passes, {_lib.icp_last_steady_followers(ctx)} workgroups followed ({n_cu} CUs)")
 buf = np.zeros((3, 4096, 8), np.int64)
 assert lib.pedp_debug_icp_stamps(C.c_void_p(buf.ctypes.data)) == 0
 cal = buf[2][1]
@@ -103,10 +111,53 @@ if hasattr(lib, "pedp_debug_icp_rt") and lib.pedp_debug_icp_rt(C.c_void_p(rt.cty
         line = (f"steady pass {p:2d}: {on.sum():3d} workgroups; begun spread {us(r[on,0].max()):5.2f}; chunks done median {np.median(us(r[on,2])):5.2f} max {us(r[on,2].max()):5.2f}; "
                 f"arrived median {np.median(us(r[on,3])):5.2f} max {us(r[on,3].max()):5.2f}; all seen median {np.median(us(r[on,4])):5.2f} max {us(r[on,4].max()):5.2f}")
         nx = on & (n[:, 7] > r[:, 4])
-        if nx.any():
-            line += (f"; close: loads back median {np.median(us(n[nx,5])):5.2f} max {us(n[nx,5].max()):5.2f}, sums {np.median(us(n[nx,6])):5.2f}, "
+        cl = nx & (n[:, 5] > r[:, 4])  # (a workgroup that followed has no stamps of a close)
+        if cl.any():
+            line += (f"; close: loads back median {np.median(us(n[cl,5])):5.2f} max {us(n[cl,5].max()):5.2f}, sums {np.median(us(n[cl,6])):5.2f}, "
                      f"U median {np.median(us(n[nx,7])):5.2f} max {us(n[nx,7].max()):5.2f}; next pass begun first {us(n[nx,0].min()):5.2f}")
         print(line)
+    # The same passes split by where the dispatcher puts a workgroup: with more ranks than CUs, rank n_cu + k lands on the
+    # CU of rank k.  "alone": ranks below the CU count with a CU to themselves; "shared low": ranks below it that share
+    # theirs (closers in every setting); "high": ranks at or above it (followers by default).  A rank that followed has no
+    # stamps [5], [6] of the pass; its [7] is the moment the closer's record was in its LDS.
+    if n_cu > 0:
+        ranks = np.arange(512)
+        tenth_shared, tenth_all = 0, 0
+        for p in range(1, min(iters + 1, 31)):
+            r, n = rt[p], rt[p + 1]
+            on = (r[:, 0] > 0) & (r[:, 4] > r[:, 0]) & (r[:, 0] >= r[:, 0].max() - 5000)
+            nx = on & (n[:, 7] > r[:, 4])
+            if not nx.any():
+                continue
+            e0 = r[on, 0].min()
+            us = lambda t: (t - e0) / 100.0
+            partner = np.zeros(512, bool)
+            partner[:512 - n_cu] = on[n_cu:]
+            groups = (("alone", on & (ranks < n_cu) & ~partner), ("shared low", on & (ranks < n_cu) & partner), ("high", on & (ranks >= n_cu)))
+            print(f"steady pass {p:2d} by placement ({n_cu} CUs):")
+            for name, m in groups:
+                if not m.any():
+                    continue
+                line = (f"   {name:10s} {m.sum():3d}: begun median {np.median(us(r[m,0])):5.2f} max {us(r[m,0].max()):5.2f}; chunks done median {np.median(us(r[m,2])):5.2f} "
+                        f"max {us(r[m,2].max()):5.2f}; all seen median {np.median(us(r[m,4])):5.2f}")
+                c = m & nx & (n[:, 5] > r[:, 4])   # closed the pass itself
+                fo = m & nx & ~(n[:, 5] > r[:, 4])  # followed
+                if c.any():
+                    line += (f"; closed ({c.sum()}): loads back median {np.median(us(n[c,5])):5.2f} max {us(n[c,5].max()):5.2f}, sums median {np.median(us(n[c,6])):5.2f}, "
+                             f"U median {np.median(us(n[c,7])):5.2f} max {us(n[c,7].max()):5.2f}")
+                if fo.any():
+                    line += f"; followed ({fo.sum()}): record in LDS median {np.median(us(n[fo,7])):5.2f} max {us(n[fo,7].max()):5.2f}"
+                print(line)
+            u = np.where(nx, n[:, 7], 0)
+            late = np.argsort(-u)[: max(int(nx.sum()) // 10, 1)]
+            sh = (ranks >= n_cu) | partner
+            tenth_shared += int(sh[late].sum()); tenth_all += len(late)
+            d = np.where(on, r[:, 2], 0)
+            late_d = np.argsort(-d)[: max(int(on.sum()) // 10, 1)]
+            print(f"   latest tenth of U: {int(sh[late].sum())} of {len(late)} on shared CUs; latest tenth of chunk ends: {int(sh[late_d].sum())} of {len(late_d)}"
+                  f" ({int((sh & on).sum())} of {int(on.sum())} workgroups share a CU)")
+        if tenth_all:
+            print(f"over all steady passes: {tenth_shared} of {tenth_all} entries in the latest tenth of U are workgroups on shared CUs")
 # per-wave view of the last pass
 wvb = np.zeros((512, 8, 16), np.int64)
 if hasattr(lib, "pedp_debug_icp_wave") and lib.pedp_debug_icp_wave(C.c_void_p(wvb.ctypes.data)) == 0:
