@@ -14,6 +14,7 @@ Layout
   icp_refine.py    host mirror of src/pose_estimation.py's refinement functions
   ray_projection.py host mirror of src/defect_projection.py's projection functions
   defect_map.py    DefectMap: per-face accumulation of projected heat maps on the model, and the defect regions
+  coverage.py      CoverageMap: which faces of the model the camera has seen, and how well, over a DefectMap's faces
   compat.py        `from pedp_hip.compat import *` in place of `from src import *` (run.py:3)
   dist.py          one-process-per-GPU sharding over torch.distributed (RCCL)
   synth.py         deterministic synthetic inputs of the benchmark configurations
@@ -21,5 +22,6 @@ Layout
 from . import _lib
 from ._lib import PedpError, LIB_PATH
 from .defect_map import DefectMap
+from .coverage import CoverageMap
 
-__all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap"]
+__all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap", "CoverageMap"]

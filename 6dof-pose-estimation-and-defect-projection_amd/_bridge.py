@@ -41,6 +41,14 @@ def stream_context(device, stream_handle):
     return _stream_ctx[key]
 
 
+def on_torch_stream(ctx, dev):
+    """ctx runs on torch's current stream of `dev`: its launches are ordered with torch's work there and nothing waits."""
+    import torch
+
+    handle = torch.cuda.current_stream(dev).cuda_stream
+    return ctx.stream_handle not in (None, 0) and ctx.stream_handle == handle
+
+
 def launch(dev, fn_name, call, ctx=None):
     """call(lib, ctx_handle, mem) on the device's context ordered with torch's current stream, or on host memory.  `ctx`:
     the caller's context instead of the stream's (host memory: instead of the default one)."""
@@ -51,10 +59,9 @@ def launch(dev, fn_name, call, ctx=None):
     import torch
 
     cur = torch.cuda.current_stream(dev)
-    handle = cur.cuda_stream
     if ctx is None:
-        ctx = stream_context(dev.index or 0, handle)
-    shared = ctx.stream_handle not in (None, 0) and ctx.stream_handle == handle
+        ctx = stream_context(dev.index or 0, cur.cuda_stream)
+    shared = on_torch_stream(ctx, dev)
     if not shared:
         cur.synchronize()  # the context runs on another stream: the inputs must be complete
     _lib.check(call(lib, ctx._h, _lib.DEVICE), fn_name)

@@ -175,6 +175,16 @@ PROTOTYPES = {
     "pedp_defect_map_stats": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]),
     "pedp_defect_map_regions": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                           _P(C.c_int64)]),
+    "pedp_coverage_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "pedp_coverage_destroy": (C.c_int, [C.c_void_p]),
+    "pedp_coverage_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_void_p]),
+    "pedp_coverage_clear": (C.c_int, [C.c_void_p]),
+    "pedp_coverage_faces": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_coverage_stats": (C.c_int, [C.c_void_p, _P(C.c_int64), C.c_void_p]),
+    "pedp_coverage_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_coverage_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                        _P(C.c_int64)]),
     "pedp_solid_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_void_p)]),
     "pedp_solid_destroy": (C.c_int, [C.c_void_p]),
     "pedp_solid_get_info": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -426,6 +436,18 @@ class ProjectOpts(C.Structure):
     """pedp_project_opts (include/pedp.h)."""
     _fields_ = [("heat_f32", C.c_int32), ("heat_mem", C.c_int32), ("jet_lut", C.c_void_p), ("colors", C.c_void_p),
                 ("post", C.c_void_p)]
+
+
+class CoverageView(C.Structure):      # pedp_coverage_view
+    _fields_ = [("depth_scale", C.c_double), ("depth_tol", C.c_double), ("min_cos", C.c_double), ("z_min", C.c_float)]
+
+
+class CoverageCriteria(C.Structure):  # pedp_coverage_criteria
+    _fields_ = [("min_views", C.c_int32), ("min_pixels", C.c_int64), ("min_cos", C.c_double), ("max_footprint", C.c_double)]
+
+
+class CoverageTotals(C.Structure):    # pedp_coverage_totals
+    _fields_ = [("covered_faces", C.c_int64), ("faces", C.c_int64), ("covered_area", C.c_double), ("total_area", C.c_double)]
 
 
 class Mesh:

@@ -33,6 +33,7 @@ SOURCES = {
     "pedp_metrics.hip": [],
     "pedp_closest.hip": [],
     "pedp_defectmap.hip": [],
+    "pedp_coverage.hip": [],
     "pedp_solid.hip": [],
     "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

@@ -7,32 +7,18 @@
 // No floating-point atomic anywhere: the maximum goes through an order-preserving 64-bit integer key, the counts are
 // integers, and a region's floating-point sums are formed in a fixed order (below), so every output is a function of
 // the inputs alone.
-#include "pedp_internal.h"
+#include "defectmap/shared.h"
 #include "mesh/topology.h"
 #include <cmath>
 #include <rocprim/device/device_scan.hpp>
 
 namespace {
 
-constexpr int DT = 256;                  // threads per block of the lane-per-item kernels
+using namespace defectmap;
+
 constexpr int64_t MAX_FACES = 1 << 28;   // 3 F edge slots are sorted with int32 positions
 constexpr int64_t MAX_ROWS = (int64_t)1 << 31;
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int SUM_BLOCK = 4096;          // faces of a region one wave sums (64 per lane); longer runs are split
-constexpr int MAX_GROW = 64;
-
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + DT - 1) / DT); }
-
-struct Carver {
-    char *base;
-    size_t off = 0;
-    template <class T> T *take(size_t n) {
-        T *p = (T *)(base + off);
-        off = a256(off + sizeof(T) * n);
-        return p;
-    }
-};
 
 #define PEDP_ROCPRIM(expr)                                                                     \
     do {                                                                                       \
@@ -42,20 +28,6 @@ struct Carver {
             return PEDP_ERR_HIP;                                                               \
         }                                                                                      \
     } while (0)
-
-// ------------------------------------------------------------------ the order-preserving key of a double
-// key(x) < key(y) <=> x < y for non-NaN x, y, with -0 below +0; no non-NaN value has key 0 (-inf has 0x000F...F), so
-// 0 stands for "nothing yet".
-using topology::bits_of;
-__host__ __device__ inline double double_of(uint64_t b) { double x; memcpy(&x, &b, 8); return x; }
-__host__ __device__ inline bool is_nan_bits(uint64_t b) { return (b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull; }
-__host__ __device__ inline uint64_t key_of(double x) {
-    const uint64_t b = bits_of(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__host__ __device__ inline double value_of(uint64_t k) { return double_of((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k); }
-constexpr uint64_t KEY_PINF = 0xFFF0000000000000ull;  // key_of(+inf)
-constexpr uint64_t KEY_NINF = 0x000FFFFFFFFFFFFFull;  // key_of(-inf)
 
 // ------------------------------------------------------------------ creation
 // area, centroid and box of every face; float64, no contraction, in the order of the contract
@@ -108,10 +80,6 @@ __global__ __launch_bounds__(DT) void run_fill_kernel(const unsigned long long *
 }
 
 // ------------------------------------------------------------------ accumulating
-__device__ __forceinline__ unsigned long long shfl_down_u64(unsigned long long v, int off) {
-    const unsigned lo = __shfl_down((unsigned)v, off, 64), hi = __shfl_down((unsigned)(v >> 32), off, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
 // One observation's rows.  Integer atomics only: the key's maximum, the 64-bit count, and the observation stamp whose
 // maximum tells the first arrival of this observation on a face (the one that sees an older stamp come back) from the rest.
 __global__ __launch_bounds__(DT) void add_kernel(const uint32_t *__restrict__ id, const double *__restrict__ inten, int64_t n, int64_t F,
@@ -133,20 +101,12 @@ __global__ __launch_bounds__(DT) void add_kernel(const uint32_t *__restrict__ id
     // Hits arrive in row-major pixel order, so neighbouring lanes often carry one face: a run of equal ids in
     // neighbouring lanes sends its maximum and its length through its first lane alone.  Measured: a frame's 35,863
     // hits take the same 12 us either way, 368,640 rows piled onto 64 faces 0.08 ms in the place of 2.5 ms.
-    const uint32_t fid = used ? f : NONE, prev = __shfl_up(fid, 1, 64);
-    const bool head = used && (lane == 0 || prev != fid);
-    const unsigned long long bounds = __builtin_amdgcn_ballot_w64(head || !used);
-    if (bounds != ~0ull) {  // wave-uniform: some run is longer than one lane
-        const unsigned long long above = lane == 63 ? 0ull : (bounds >> (lane + 1)) << (lane + 1);
-        const int end = above ? __builtin_ctzll(above) - 1 : 63;  // the last lane of this lane's run
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {  // the maximum of lanes [lane, end]
-            const unsigned long long k2 = shfl_down_u64(key, off);
-            if (lane + off <= end) key = k2 > key ? k2 : key;
-        }
-        count = (unsigned long long)(end - lane + 1);
+    const LaneRun run = lane_run(used ? f : NONE, lane);
+    if (run.wide) {
+        key = run_max(key, lane, run.end);
+        count = (unsigned long long)(run.end - lane + 1);
     }
-    if (head) {
+    if (run.head) {
         atomicMax(&peak[f], key);
         atomicAdd(&hits[f], count);
         if (atomicMax(&stamp[f], obs) < obs) atomicAdd(&frames[f], 1);
@@ -290,10 +250,6 @@ __device__ __forceinline__ void part_init(Part &a) {
     a.area = 0.0; a.hits = 0; a.n_seed = 0; a.max_frames = 0; a.peak = 0;
     for (int d = 0; d < 3; ++d) { a.m[d] = 0.0; a.lo[d] = KEY_PINF; a.hi[d] = KEY_NINF; }
 }
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int off) {
-    const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 // this lane's value and its partner's of the butterfly step `off`: a + b is the same on both sides, bit for bit
 __device__ __forceinline__ void part_butterfly(Part &a) {
 #pragma unroll
@@ -405,32 +361,9 @@ __global__ __launch_bounds__(DT) void region_row_kernel(SumArgs a, pedp_defect_r
 
 }  // namespace
 
-struct pedp_defect_map_s {
-    pedp_ctx_t ctx = nullptr;
-    int device = 0;
-    int64_t V = 0, F = 0;
-    char *store = nullptr;  // one allocation: everything below
-    double *area = nullptr, *cen = nullptr, *box = nullptr;
-    int32_t *pos_face = nullptr, *pos_run = nullptr, *face_run = nullptr;  // 3 F each
-    unsigned long long *peak = nullptr, *hits = nullptr, *counters = nullptr;
-    int32_t *frames = nullptr;
-    uint32_t *stamp = nullptr;
-    size_t state_off = 0, state_bytes = 0;  // peak ... counters: what pedp_defect_map_clear zeroes
-    int64_t observations = 0;
-    int64_t ignored_host = 0;  // F = 0: the ignored rows (there are no device counters)
-    pedp_scratch ws;   // regions: marks, the union-find, the scans, the sorted order
-    pedp_scratch io;   // staging of host-memory calls; regions: the block sums and a host-memory call's table
-};
-
 namespace {
 
-struct RegionWs {
-    uint8_t *seed, *mark[2];
-    uint32_t *run_first, *is_root, *rank, *n_blocks, *block_off;
-    int32_t *parent, *root, *label, *order, *begin, *end;
-    void *tmp;
-    size_t tmp_bytes;
-};
+using RegionWs = pedp_region_ws;
 int region_ws(pedp_defect_map_s *m, RegionWs &w) {
     const size_t F = (size_t)m->F, E = 3 * F;
     size_t t1 = 0, t2 = 0;
@@ -663,6 +596,19 @@ int pedp_defect_map_stats(pedp_defect_map_t m, int64_t *observations, int64_t *r
 int pedp_defect_map_regions(pedp_defect_map_t m, double threshold, int32_t min_frames, int32_t grow, int mem, int32_t *labels,
                             int64_t capacity, pedp_defect_region *table, int64_t *n_regions) {
     const char *who = "pedp_defect_map_regions";
+    pedp_region_ws w;
+    const int rc = pedp_defect_regions_begin(m, who, grow, mem, capacity, table, n_regions, w);
+    if (rc || !w.seed) return rc;
+    hipLaunchKernelGGL(seed_kernel, dim3(blocks_for(m->F)), dim3(DT), 0, m->ctx->stream, m->peak, m->hits, m->frames, m->F, threshold,
+                       min_frames, w.seed, w.mark[0]);
+    const pedp_region_columns col{m->peak, m->hits, m->frames};
+    return pedp_defect_regions_finish(m, who, w, col, grow, mem, labels, capacity, table, n_regions);
+}
+
+}  // extern "C"
+
+int pedp_defect_regions_begin(pedp_defect_map_s *m, const char *who, int32_t grow, int mem, int64_t capacity, const pedp_defect_region *table,
+                              int64_t *n_regions, pedp_region_ws &w) {
     PEDP_REQUIRE(m && n_regions, "%s: null map / n_regions", who);
     pedp_ctx_t c = m->ctx;
     PEDP_REQUIRE(mem == PEDP_HOST || mem == PEDP_DEVICE, "%s: bad mem flag %d", who, mem);
@@ -671,15 +617,20 @@ int pedp_defect_map_regions(pedp_defect_map_t m, double threshold, int32_t min_f
                  table ? "a" : "no");
     PEDP_REQUIRE(!c->icp_pending, "%s: a registration is pending on this context (the call waits for the stream)", who);
     *n_regions = 0;
+    w.seed = nullptr;
     if (m->F == 0) return PEDP_OK;
     PEDP_HIP_CHECK(hipSetDevice(c->device));
+    return region_ws(m, w);
+}
+
+int pedp_defect_regions_finish(pedp_defect_map_s *m, const char *who, const pedp_region_ws &w, const pedp_region_columns &col, int32_t grow,
+                               int mem, int32_t *labels, int64_t capacity, pedp_defect_region *table, int64_t *n_regions) {
+    pedp_ctx_t c = m->ctx;
     const int64_t F = m->F, E = 3 * F;
-    RegionWs w;
-    int rc = region_ws(m, w);
-    if (rc) return rc;
+    int rc = PEDP_OK;
+    size_t tmp_bytes = w.tmp_bytes;  // rocprim takes it by reference
     hipStream_t s = c->stream;
     const dim3 gF(blocks_for(F)), gE(blocks_for(E)), bt(DT);
-    hipLaunchKernelGGL(seed_kernel, gF, bt, 0, s, m->peak, m->hits, m->frames, F, threshold, min_frames, w.seed, w.mark[0]);
     int cur = 0;
     for (int round = 0; round <= grow; ++round) {  // the last fill of run_first serves the union
         PEDP_HIP_CHECK(hipMemsetAsync(w.run_first, 0xFF, 4 * (size_t)E, s));
@@ -692,7 +643,7 @@ int pedp_defect_map_regions(pedp_defect_map_t m, double threshold, int32_t min_f
     hipLaunchKernelGGL(parent_init_kernel, gF, bt, 0, s, mark, F, w.parent);
     hipLaunchKernelGGL(union_kernel, gE, bt, 0, s, m->pos_face, m->pos_run, E, mark, w.run_first, w.parent);
     hipLaunchKernelGGL(root_kernel, dim3(blocks_for(F + 1)), bt, 0, s, mark, F, w.parent, w.root, w.is_root);
-    PEDP_ROCPRIM(rocprim::exclusive_scan(w.tmp, w.tmp_bytes, w.is_root, w.rank, 0u, (size_t)F + 1, rocprim::plus<uint32_t>(), s));
+    PEDP_ROCPRIM(rocprim::exclusive_scan(w.tmp, tmp_bytes, w.is_root, w.rank, 0u, (size_t)F + 1, rocprim::plus<uint32_t>(), s));
     int32_t *d_labels = mem == PEDP_DEVICE ? labels : nullptr;
     hipLaunchKernelGGL(label_kernel, gF, bt, 0, s, w.root, w.rank, F, w.label, d_labels);
     PEDP_HIP_CHECK(hipGetLastError());
@@ -716,10 +667,10 @@ int pedp_defect_map_regions(pedp_defect_map_t m, double threshold, int32_t min_f
     if (rc) return rc;
     hipLaunchKernelGGL(region_range_kernel, gF, bt, 0, s, w.label, w.order, F, w.begin, w.end);
     hipLaunchKernelGGL(region_blocks_kernel, dim3(blocks_for(R + 1)), bt, 0, s, w.begin, w.end, R, w.n_blocks);
-    PEDP_ROCPRIM(rocprim::exclusive_scan(w.tmp, w.tmp_bytes, w.n_blocks, w.block_off, 0u, (size_t)R + 1, rocprim::plus<uint32_t>(), s));
+    PEDP_ROCPRIM(rocprim::exclusive_scan(w.tmp, tmp_bytes, w.n_blocks, w.block_off, 0u, (size_t)R + 1, rocprim::plus<uint32_t>(), s));
     SumArgs a;
     a.order = w.order; a.begin = w.begin; a.end = w.end; a.block_off = w.block_off; a.R = R;
-    a.area = m->area; a.cen = m->cen; a.box = m->box; a.peak_key = m->peak; a.hits = m->hits; a.frames = m->frames; a.seed = w.seed;
+    a.area = m->area; a.cen = m->cen; a.box = m->box; a.peak_key = col.peak_key; a.hits = col.hits; a.frames = col.frames; a.seed = w.seed;
     const int64_t blocks_max = F / SUM_BLOCK + R;  // every region has at most one block that is not full
     // the block sums and a host-memory call's table, sized by R: in the staging scratch
     rc = m->io.reserve(a256(sizeof(Part) * (size_t)blocks_max) + a256(sizeof(pedp_defect_region) * (size_t)R));
@@ -734,5 +685,3 @@ int pedp_defect_map_regions(pedp_defect_map_t m, double threshold, int32_t min_f
     PEDP_HIP_CHECK(hipStreamSynchronize(s));
     return PEDP_OK;
 }
-
-}  // extern "C"

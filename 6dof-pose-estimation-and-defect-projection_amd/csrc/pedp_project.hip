@@ -11,17 +11,16 @@
 // that redoes the block-local scan in LDS.  All of it is HBM-bound streaming over at most
 // width * height elements (8 B per pixel in, 24 B per selected ray out).
 #include "pedp_internal.h"
+#include "camera/pixel_ray.h"
 
 namespace {
+
+using camera::Cam;
+using camera::pixel_direction;
 
 constexpr int CP_THREADS = 256;
 constexpr int CP_PER_THREAD = 8;
 constexpr int CP_BLOCK = CP_THREADS * CP_PER_THREAD;
-
-struct Cam {
-    double fx, fy, cx, cy;
-    int width;
-};
 
 // MODE 0: element i is pixel i of the heat map, kept when heatmap[i] > threshold in the map's own type: numpy compares
 //         a float32 map with a Python number in float32 (the number rounded to it), so an entry equal to float32(0.3)
@@ -124,16 +123,6 @@ __global__ __launch_bounds__(1024) void compact_scan_kernel(int *__restrict__ bl
     __syncthreads();
     int run = part[threadIdx.x];
     for (int i = lo; i < hi; ++i) { int v = block_tot[i]; block_tot[i] = run; run += v; }
-}
-
-__device__ __forceinline__ void pixel_direction(const Cam &cam, int64_t pix, double d[3]) {
-    const int64_t y = pix / cam.width, x = pix - y * cam.width;
-    const double xn = __ddiv_rn(__dsub_rn((double)x, cam.cx), cam.fx);
-    const double yn = __ddiv_rn(__dsub_rn((double)y, cam.cy), cam.fy);
-    const double len = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(xn, xn), __dmul_rn(yn, yn)), 1.0));
-    d[0] = __ddiv_rn(xn, len);
-    d[1] = __ddiv_rn(yn, len);
-    d[2] = __ddiv_rn(1.0, len);
 }
 
 // stage 1: selected pixels -> pixel list + float32 [origin | direction] rows

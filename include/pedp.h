@@ -920,6 +920,94 @@ int pedp_defect_map_stats(pedp_defect_map_t map, int64_t *observations, int64_t 
 int pedp_defect_map_regions(pedp_defect_map_t map, double threshold, int32_t min_frames, int32_t grow, int mem, int32_t *labels,
                             int64_t capacity, pedp_defect_region *table, int64_t *n_regions);
 
+/* ---------------------------------------------------------------- the coverage map: which faces were seen, and how well
+ * The defect map says which faces are defective; it cannot say whether the whole part was looked at: a face with
+ * peak 0, hits 0, frames 0 is either clean or never seen.  The coverage map keeps, per face of the model, the evidence
+ * that the camera observed it.  The reference has no counterpart (run.py shows hit clouds and never says what was not
+ * inspected); the contract is DESIGN.md s4.20.
+ *
+ * pedp_coverage_create lays the coverage state over the faces of a defect map and borrows its areas, centroids, boxes,
+ * adjacency and region scratch: one weld and one adjacency per model.  The map must outlive the coverage handle; the
+ * handle lives on the map's context.  The map's own per-face state is neither read nor written by any call here.
+ * PEDP_ERR_BAD_ARG while a registration is pending on the context.
+ *
+ * pedp_coverage_add is one VIEW (one camera frame).  mesh: a handle of the map's context with the map's F, posed as the
+ * frame sees it, in the camera's frame.  cam: the pinhole whose pixel rays from the origin were cast against it (fx, fy
+ * positive); t_hit height x width float32 and prim_id height x width uint32 are that cast's results, row-major, pixel
+ * i = y width + x.  depth (nullable): height x width float32, the sensor's image; mask (nullable): height x width
+ * uint8; status (nullable): height x width uint8, the class of every pixel.  prm (NULL without depth: depth_scale 1,
+ * min_cos 0, z_min 0.001): depth_tol, in mesh units, is the sensor's and has no default.  Per pixel, float64, no
+ * contraction, every expression in the order written:
+ *   d        the ray that was cast: (xn, yn, 1) / sqrt((xn xn + yn yn) + 1), xn = (x - cx) / fx, yn = (y - cy) / fy
+ *            (pedp_project_heatmap's arithmetic), each component rounded to float32 and widened again
+ *   z_hit    t_hit d_z;   z_meas = (double)depth depth_scale
+ *   n        the unit normal (ab x ac) / |ab x ac| of record prim_id as posed, as pedp_mesh_face_normals forms it
+ *   cos      min(|(n_x d_x + n_y d_y) + n_z d_z|, 1); 0 for a record that no ray can hit or a normal that is NaN
+ *   footprint  ((z_hit z_hit) d_z) / ((fx fy) cos): the area of surface one pixel covers, t^2 dOmega / cos with
+ *            dOmega = d_z^3 / (fx fy); +inf at cos = 0
+ * The pixel gets exactly one class, the first of these rules that holds:
+ *   0 MASKED    a mask is given and mask[i] == 0
+ *   1 MISS      prim_id >= F (0xFFFFFFFF included), or t_hit is not finite
+ *   2 NO_DEPTH  depth is given and it is not true that depth[i] >= z_min (float32, as pedp_depth_to_scene compares),
+ *               or the depth is infinite; NaN falls here
+ *   3 OCCLUDED  depth is given and z_meas - z_hit < -depth_tol: something stands in front of the surface
+ *   4 BEHIND    depth is given and z_meas - z_hit > depth_tol: the sensor looked through where the model has surface
+ *   5 GRAZING   cos < min_cos
+ *   6 SEEN      otherwise; a difference of exactly depth_tol is SEEN
+ * For the SEEN pixels on face f: pixels[f] += 1 (64-bit); views[f] += 1 ONCE per view; best_cos[f] is raised to cos;
+ * min_footprint[f] is lowered to the footprint (a NaN footprint -- t_hit = 0 at cos = 0 -- takes no part).  For the
+ * OCCLUDED pixels on f: blocked[f] += 1.  Seven 64-bit class counters and the view count are kept per handle.  Integer
+ * atomics only, as for pedp_defect_map_add: the maximum on the order-preserving key, the minimum on the bits of the
+ * non-negative double, counts, and the view stamp; runs of equal faces in neighbouring pixels are combined inside a
+ * wave before the atomics.  The state after a sequence of views is a function of each view's pixels alone: not of their
+ * order, of how they sit in memory, or of the handle's history before the last pedp_coverage_clear.
+ * PEDP_DEVICE only enqueues on the context's stream, has no workspace and is allowed while a registration is pending on
+ * the context (pedp_icp_begin); PEDP_HOST copies in and out, returns after completion and is PEDP_ERR_BAD_ARG then.
+ * PEDP_ERR_BAD_ARG also when the mesh's F is not the map's, when the mesh is of another context, when depth is given
+ * and depth_tol is negative or NaN (or prm is NULL), and when min_cos is outside [0, 1].
+ *
+ * pedp_coverage_faces: F values each, every pointer nullable, host or device memory by `mem`; a face never seen reads
+ * pixels 0, views 0, best_cos 0.0, min_footprint +inf, blocked 0.  pedp_coverage_stats: the views and the pixels of each
+ * class since the last clear (classes nullable; with it the call waits on the stream: PEDP_ERR_BAD_ARG while a
+ * registration is pending).
+ *
+ * A face is COVERED under criteria c iff views >= c.min_views && pixels >= c.min_pixels && best_cos >= c.min_cos &&
+ * min_footprint <= c.max_footprint on the values pedp_coverage_faces reads; NULL means 1, 1, 0, +inf.
+ * pedp_coverage_summary: the covered faces, their area and the model's area.  The two areas are summed in s4.17's
+ * block-and-butterfly order over the faces in face order (blocks of 4096 consecutive faces): the same bits on every call
+ * for the same per-face state.  It waits on the stream (PEDP_ERR_BAD_ARG while a registration is pending).
+ * pedp_coverage_regions: the connected regions of the UNCOVERED faces (covered = 0: where to point the camera next) or of
+ * the covered ones (covered != 0), through the body of pedp_defect_map_regions: growth, numbering by the lowest face,
+ * the table's sums, the overflow rule (R > capacity) and the pending rule are that call's.  In a row, hits is the sum of
+ * the faces' pixels, max_frames the largest views, peak the largest best_cos over the faces with pixels (0 if none). */
+typedef struct pedp_coverage_s *pedp_coverage_t;
+typedef struct pedp_coverage_view {
+    double depth_scale;    /* z_meas = (double)depth * depth_scale: 1000 for metres against a mesh in millimetres */
+    double depth_tol;      /* mesh units; >= 0 whenever depth is given */
+    double min_cos;        /* 0 ... 1 */
+    float z_min;           /* validity of a depth: 0.001 */
+} pedp_coverage_view;
+typedef struct pedp_coverage_criteria {
+    int32_t min_views;
+    int64_t min_pixels;
+    double min_cos, max_footprint;
+} pedp_coverage_criteria;
+typedef struct pedp_coverage_totals {
+    int64_t covered_faces, faces;
+    double covered_area, total_area;
+} pedp_coverage_totals;
+int pedp_coverage_create(pedp_defect_map_t map, pedp_coverage_t *out);
+int pedp_coverage_destroy(pedp_coverage_t cov);
+int pedp_coverage_add(pedp_coverage_t cov, pedp_mesh_t mesh, const pedp_pinhole *cam, const float *t_hit, const uint32_t *prim_id,
+                      const float *depth, const uint8_t *mask, const pedp_coverage_view *prm, int mem, uint8_t *status);
+int pedp_coverage_clear(pedp_coverage_t cov);
+int pedp_coverage_faces(pedp_coverage_t cov, int mem, int64_t *pixels, int32_t *views, double *best_cos, double *min_footprint,
+                        int64_t *blocked);
+int pedp_coverage_stats(pedp_coverage_t cov, int64_t *views, int64_t classes[7]);
+int pedp_coverage_summary(pedp_coverage_t cov, const pedp_coverage_criteria *c, pedp_coverage_totals *out);
+int pedp_coverage_regions(pedp_coverage_t cov, const pedp_coverage_criteria *c, int covered, int32_t grow, int mem, int32_t *labels,
+                          int64_t capacity, pedp_defect_region *table, int64_t *n_regions);
+
 /* ---------------------------------------------------------------- the solid: signed distance and occupancy
  * RaycastingScene.compute_signed_distance / compute_occupancy on the mesh handle: whether a point lies inside the CAD
  * solid (a dent, missing material) or outside it (a burr, excess material), which `side` above cannot tell away from
