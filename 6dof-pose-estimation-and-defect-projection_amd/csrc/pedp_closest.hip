@@ -19,12 +19,12 @@
 // exhaustive one as long as it never drops a triangle that could win, which the margin of sphere_culls() is there for.
 // tests/_closest_ref.py restates the contract in numpy.
 #include "pedp_internal.h"
+#include "mesh/cluster.h"              // CL_TRIS: triangles per cluster sphere
 #include "mesh/record.h"
 #include <cmath>
 
 namespace {
 
-constexpr int CL_TRIS = 16;            // triangles per cluster sphere (pedp_ray.hip)
 constexpr int SUPER_CL = 64;           // clusters per super-cluster sphere
 constexpr int CT = 256;                // threads per workgroup
 constexpr unsigned NONE = 0xFFFFFFFFu;

@@ -639,3 +639,89 @@ def test_resident_ray_set_equals_the_per_call_cast(ctx, oracle):
         refp = oracle.raycast(oracle.pose_vertices(T, f.model_points), f.tris, f.rays6, bvh=True)
         gotp = pm.cast_rayset(rs, want_uv=False)
         assert np.array_equal(gotp["primitive_ids"], refp["primitive_ids"]) and np.array_equal(gotp["t_hit"].view(np.uint32), refp["t_hit"].view(np.uint32))
+
+
+_PARITY = {}
+
+
+def _parity_case(oracle):
+    """The parity frame, its rays with every third origin moved, a moved copy of its mesh and the oracle's answers
+    for them: computed once, read by the two tests below."""
+    if not _PARITY:
+        from pedp_hip import synth
+
+        f = synth.Frame("parity")
+        mixed = f.rays6.copy()
+        mixed[::3, :3] += np.array([5.0, -3.0, 2.0], np.float32)
+        moved = (f.verts_posed + np.array([12.0, -7.0, 25.0], np.float32)).astype(np.float32)
+        _PARITY.update(f=f, mixed=mixed, moved=moved,
+                       ref=oracle.raycast(f.verts_posed, f.tris, f.rays6, bvh=True),
+                       ref_moved=oracle.raycast(moved, f.tris, f.rays6, bvh=True),
+                       ref_mixed=oracle.raycast(f.verts_posed, f.tris, mixed, bvh=True))
+    return _PARITY
+
+
+def _same_t_id(res, ref, n=None):
+    assert np.array_equal(res["primitive_ids"], ref["primitive_ids"][:n])
+    assert np.array_equal(res["t_hit"].view(np.uint32), ref["t_hit"][:n].view(np.uint32))
+
+
+@pytest.mark.parametrize("configured", [0, 1, 2, 5])
+def test_rayset_fallback_and_debug_cast_leave_the_configuration_alone(ctx, oracle, configured):
+    """A ray set the grid cannot serve is cast by variant 3 when 0 (or 4) is configured, otherwise by the configured
+    variant -- into host memory with and without uv and into device memory, the oracle's bits each time -- and
+    neither that cast nor pedp_debug_rast_rects' variant-4 cast changes what the next pedp_raycast chooses."""
+    torch = pytest.importorskip("torch")
+    from pedp_hip import _lib
+
+    case = _parity_case(oracle)
+    f, mixed, ref = case["f"], case["mixed"], case["ref_mixed"]
+    n = len(mixed)
+    expect_set = 3 if configured == 0 else configured
+    expect_call = 2 if configured == 0 else configured   # 64 rays: the auto choice is variant 2
+    _lib.raycast_configure(ctx, 0, configured)
+    try:
+        mesh = _lib.Mesh(ctx, f.verts_posed, f.tris)
+        rs = _lib.RaySet(ctx, mixed)
+        got = mesh.cast_rayset(rs, want_uv=True)
+        assert rs.last_variant()[0] == expect_set
+        _same(got, ref)
+        got = mesh.cast_rayset(rs, want_uv=False)
+        assert rs.last_variant()[0] == expect_set
+        _same_t_id(got, ref)
+        t = torch.empty(n, dtype=torch.float32, device="cuda")
+        ids = torch.empty(n, dtype=torch.int32, device="cuda")
+        uv = torch.empty((n, 2), dtype=torch.float32, device="cuda")
+        mesh.cast_rayset_device(rs, t.data_ptr(), ids.data_ptr(), uv.data_ptr())
+        ctx.synchronize()
+        assert rs.last_variant()[0] == expect_set
+        _same({"t_hit": t.cpu().numpy(), "primitive_ids": ids.cpu().numpy().view(np.uint32), "primitive_uvs": uv.cpu().numpy()}, ref)
+        _same(mesh.cast_rays(mixed[:64]), {k: v[:64] for k, v in ref.items()})
+        assert _lib.raycast_last_variant(ctx)[0] == expect_call
+        _lib.debug_rast_rects(ctx, mesh, mixed[:64])
+        _same(mesh.cast_rays(mixed[:64]), {k: v[:64] for k, v in ref.items()})
+        assert _lib.raycast_last_variant(ctx)[0] == expect_call
+    finally:
+        _lib.raycast_configure(ctx, 0, 0)
+
+
+def test_per_call_grid_and_rayset_grid_interleaved(ctx, oracle):
+    """The per-call grid (variant 4, the context's scratch and its two headers) and a ray set's grid (its own
+    allocation and headers) in turn on one context, against two meshes: every cast the oracle's bits, every cast
+    answered by its grid."""
+    from pedp_hip import _lib
+
+    case = _parity_case(oracle)
+    f = case["f"]
+    _lib.raycast_configure(ctx, 0, 4)
+    try:
+        meshes = [(_lib.Mesh(ctx, f.verts_posed, f.tris), case["ref"]), (_lib.Mesh(ctx, case["moved"], f.tris), case["ref_moved"])]
+        rs = _lib.RaySet(ctx, f.rays6)
+        for rnd in range(3):
+            for mesh, ref in meshes:
+                _same(mesh.cast_rays(f.rays6), ref)
+                assert _lib.raycast_last_variant(ctx) == (4, 0)
+                _same(mesh.cast_rayset(rs), ref)
+                assert rs.last_variant() == (4, 0)
+    finally:
+        _lib.raycast_configure(ctx, 0, 0)
