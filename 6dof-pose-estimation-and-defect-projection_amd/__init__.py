@@ -15,6 +15,7 @@ Layout
   ray_projection.py host mirror of src/defect_projection.py's projection functions
   defect_map.py    DefectMap: per-face accumulation of projected heat maps on the model, and the defect regions
   coverage.py      CoverageMap: which faces of the model the camera has seen, and how well, over a DefectMap's faces
+  surface_fit.py   fit_to_surface: robust best fit of a scene cloud to the posed surface itself; refit_pose, fit_frame_to_surface
   compat.py        `from pedp_hip.compat import *` in place of `from src import *` (run.py:3)
   dist.py          one-process-per-GPU sharding over torch.distributed (RCCL)
   synth.py         deterministic synthetic inputs of the benchmark configurations

@@ -164,6 +164,8 @@ PROTOTYPES = {
     "pedp_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "pedp_mesh_face_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "pedp_fit_to_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_double,
+                                      C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_closest_configure": (C.c_int, [C.c_void_p, C.c_int]),
     "pedp_closest_last_stats": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_defect_map_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_void_p)]),

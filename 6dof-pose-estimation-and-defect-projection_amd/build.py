@@ -35,6 +35,7 @@ SOURCES = {
     "pedp_defectmap.hip": [],
     "pedp_coverage.hip": [],
     "pedp_solid.hip": [],
+    "pedp_surface_fit.hip": [],
     "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_linear.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

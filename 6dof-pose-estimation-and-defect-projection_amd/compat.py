@@ -10,7 +10,8 @@ loops (`FoundationPose`, `PoseRefinePredictor`, `ScorePredictor`, estimator.py),
 checkpoint loaders (`RefineNet`, `ScoreNetMultiPair`, `load_refiner`, `load_scorer`, networks.py), and the evaluation
 metrics (`add_err`, `adds_err`, their batch forms, `compute_auc_sklearn`, `symmetry_tfs_from_info`, metrics.py), and the
 exact cloud-to-mesh distance with the deviation heat map (`closest_points`, `compute_distance`, `align_to_mesh`,
-`deviation_heatmap`, surface_distance.py), and the defect map on the model in the place of run.py:196-201's list of
+`deviation_heatmap`, surface_distance.py), and the robust best fit of the scene to that surface, the pose the deviation
+is measured in (`fit_to_surface`, `refit_pose`, `fit_frame_to_surface`, surface_fit.py), and the defect map on the model in the place of run.py:196-201's list of
 hit clouds (`DefectMap`, defect_map.py), and the inspection coverage over its faces, which the reference has no
 counterpart of (`CoverageMap`, coverage.py); the Dash app, sensor
 code and the networks' weights stay the reference's own.
@@ -61,6 +62,7 @@ from .metrics import (add_err, add_err_batch, adds_err, adds_err_batch, compute_
 from .surface_distance import align_to_mesh, closest_points, compute_distance, deviation_heatmap  # noqa: E402,F401  (run.py:64's heat map)
 from .surface_distance import (Solid, compute_occupancy, compute_signed_distance, signed_closest_points,  # noqa: E402,F401
                                signed_deviation, split_deviation)
+from .surface_fit import fit_frame_to_surface, fit_to_surface, refit_pose  # noqa: E402,F401  (between refine_pose_with_icp and the heat map)
 from .defect_map import DefectMap  # noqa: E402,F401  (run.py:61, :119, :196-201: the history of hits, kept per face)
 from .coverage import CoverageMap  # noqa: E402,F401  (no counterpart: run.py never says what was not inspected)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
@@ -98,5 +100,6 @@ __all__ = [
     "add_err", "adds_err", "add_err_batch", "adds_err_batch", "compute_auc_sklearn", "symmetry_tfs_from_info",
     "closest_points", "compute_distance", "align_to_mesh", "deviation_heatmap",
     "Solid", "compute_signed_distance", "compute_occupancy", "signed_closest_points", "signed_deviation", "split_deviation",
+    "fit_to_surface", "refit_pose", "fit_frame_to_surface",
     "DefectMap", "CoverageMap",
 ]

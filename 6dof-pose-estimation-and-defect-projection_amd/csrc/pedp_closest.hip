@@ -18,10 +18,16 @@
 // (d^2, triangle index), which does not depend on the order of the tests: the culled path returns the bits of the
 // exhaustive one as long as it never drops a triangle that could win, which the margin of sphere_culls() is there for.
 // tests/_closest_ref.py restates the contract in numpy.
+//
+// pedp_fit_to_surface (pedp_surface_fit.hip) runs the same three kernels instantiated with FIT = true,
+// which read two more arguments: T, a pose the finite rows go through as they are loaded, and done, a device flag that
+// makes a launch return at once.  pedp_closest_points runs them with FIT = false and reads neither.
 #include "pedp_internal.h"
 #include "mesh/cluster.h"              // CL_TRIS: triangles per cluster sphere
 #include "mesh/record.h"
+#include "closest/move_point.h"
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -92,6 +98,13 @@ struct Args {
     unsigned long long *pairs;
 };
 
+// what the kernels get as pedp_fit_to_surface runs them (FIT); pedp_closest_points' kernels keep Args as it was
+struct FitArgs : Args {
+    const double *T;   // a row-major 4 x 4 the finite rows are moved by as they are loaded
+    const int *done;   // a device flag: non-zero turns the launch into an early exit
+};
+template <bool FIT> using ArgsOf = std::conditional_t<FIT, FitArgs, Args>;
+
 // the outputs of point i from its chosen triangle: the same point_triangle() as the search
 __device__ __forceinline__ void store_result(const Args &a, int64_t i, bool finite, const double p[3], double best, unsigned bid) {
     double c[3] = {quiet_nan(), quiet_nan(), quiet_nan()}, v = quiet_nan(), w = quiet_nan();
@@ -118,22 +131,29 @@ __device__ __forceinline__ void store_result(const Args &a, int64_t i, bool fini
     if (a.region) a.region[i] = (uint8_t)rule;
 }
 
-__device__ __forceinline__ bool load_point(const Args &a, int64_t i, double p[3]) {
+template <bool FIT> __device__ __forceinline__ bool load_point(const ArgsOf<FIT> &a, int64_t i, double p[3]) {
     p[0] = p[1] = p[2] = 0.0;
     if (i >= a.n) return false;
     if (!pedp_row_finite(a.pts, i)) return false;
     p[0] = a.pts[3 * i]; p[1] = a.pts[3 * i + 1]; p[2] = a.pts[3 * i + 2];
+    if constexpr (FIT) surface_fit::move_point(a.T, p);
     return true;
+}
+
+template <bool FIT> __device__ __forceinline__ bool finished(const ArgsOf<FIT> &a) {
+    if constexpr (FIT) return *a.done != 0;
+    return false;
 }
 
 __device__ __forceinline__ void add_pairs(const Args &a, unsigned long long n) {
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(a.pairs, n);
 }
 
-__global__ __launch_bounds__(CT) void closest_exhaustive_kernel(Args a) {
+template <bool FIT> __global__ __launch_bounds__(CT) void closest_exhaustive_kernel(ArgsOf<FIT> a) {
+    if (finished<FIT>(a)) return;
     const int64_t i = (int64_t)blockIdx.x * CT + threadIdx.x;
     double p[3];
-    const bool live = load_point(a, i, p);
+    const bool live = load_point<FIT>(a, i, p);
     double best = pos_inf();
     unsigned bid = NONE;
     unsigned long long tested = 0;  // the same in every lane
@@ -183,10 +203,11 @@ __device__ __forceinline__ int visit_cluster(const Args &a, int64_t c, bool want
     return tested;
 }
 
-__global__ __launch_bounds__(CT) void closest_culled_kernel(Args a) {
+template <bool FIT> __global__ __launch_bounds__(CT) void closest_culled_kernel(ArgsOf<FIT> a) {
+    if (finished<FIT>(a)) return;
     const int64_t i = (int64_t)blockIdx.x * CT + threadIdx.x;
     double p[3];
-    const bool live = load_point(a, i, p);
+    const bool live = load_point<FIT>(a, i, p);
     double best = pos_inf();
     unsigned bid = NONE;
     unsigned long long pairs = 0;  // the same in every lane
@@ -270,12 +291,13 @@ __device__ __forceinline__ int test_quad(const Args &a, int64_t c, const double 
     return __popcll(__ballot(on));
 }
 
-__global__ __launch_bounds__(CT) void closest_wave_kernel(Args a) {
+template <bool FIT> __global__ __launch_bounds__(CT) void closest_wave_kernel(ArgsOf<FIT> a) {
+    if (finished<FIT>(a)) return;
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * (CT / 64) + (threadIdx.x >> 6);
     if (i >= a.n) return;  // the whole wave
     double p[3];
-    const bool live = load_point(a, i, p);
+    const bool live = load_point<FIT>(a, i, p);
     double best = pos_inf();  // the same in every lane from here on
     unsigned bid = NONE;
     unsigned long long pairs = 0;
@@ -339,6 +361,28 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
+namespace {
+
+// one search on device memory, enqueued on the context's stream; `pairs` is the caller's counter, already zero
+template <bool FIT> int launch_search(pedp_ctx_t c, pedp_mesh_t mesh, ArgsOf<FIT> &a, int64_t N) {
+    a.tri = mesh->tri;
+    a.sph = (const float4 *)mesh->spheres;
+    a.ssph = (const float4 *)mesh->super_spheres;
+    a.F = mesh->F;
+    a.n_clusters = mesh->n_clusters;
+    a.n_super = mesh->n_super;
+    a.n = N;
+    const dim3 grid((unsigned)((N + CT - 1) / CT));
+    const int mode = c->closest_mode != MODE_AUTO ? c->closest_mode : (N <= WAVE_POINTS_MAX ? MODE_WAVE : MODE_LANE);
+    if (mode == MODE_EXHAUSTIVE) hipLaunchKernelGGL(closest_exhaustive_kernel<FIT>, grid, dim3(CT), 0, c->stream, a);
+    else if (mode == MODE_LANE) hipLaunchKernelGGL(closest_culled_kernel<FIT>, grid, dim3(CT), 0, c->stream, a);
+    else hipLaunchKernelGGL(closest_wave_kernel<FIT>, dim3((unsigned)((N + CT / 64 - 1) / (CT / 64))), dim3(CT), 0, c->stream, a);
+    PEDP_HIP_CHECK(hipGetLastError());
+    return PEDP_OK;
+}
+
+}  // namespace
+
 // The search of pedp_closest_points on device memory, enqueued on the context's stream: what the public call and
 // pedp_signed_distance (pedp_solid.hip) both run.  region (nullable): the rule of pedp.h's table, 1 ... 7, that
 // point_triangle took for the chosen triangle (0: no triangle); with it null every other output keeps its bits.
@@ -347,24 +391,24 @@ int pedp_closest_launch(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64
     int rc = c->closest_ws.reserve(256);
     if (rc) return rc;
     Args a;
-    a.tri = mesh->tri;
-    a.sph = (const float4 *)mesh->spheres;
-    a.ssph = (const float4 *)mesh->super_spheres;
-    a.F = mesh->F;
-    a.n_clusters = mesh->n_clusters;
-    a.n_super = mesh->n_super;
     a.pts = pts;
-    a.n = N;
     a.closest = closest; a.dist = dist; a.prim = prim_id; a.uv = uv; a.side = side; a.region = region;
     a.pairs = (unsigned long long *)c->closest_ws.ptr;
     PEDP_HIP_CHECK(hipMemsetAsync(a.pairs, 0, sizeof(unsigned long long), c->stream));
-    const dim3 grid((unsigned)((N + CT - 1) / CT));
-    const int mode = c->closest_mode != MODE_AUTO ? c->closest_mode : (N <= WAVE_POINTS_MAX ? MODE_WAVE : MODE_LANE);
-    if (mode == MODE_EXHAUSTIVE) hipLaunchKernelGGL(closest_exhaustive_kernel, grid, dim3(CT), 0, c->stream, a);
-    else if (mode == MODE_LANE) hipLaunchKernelGGL(closest_culled_kernel, grid, dim3(CT), 0, c->stream, a);
-    else hipLaunchKernelGGL(closest_wave_kernel, dim3((unsigned)((N + CT / 64 - 1) / (CT / 64))), dim3(CT), 0, c->stream, a);
-    PEDP_HIP_CHECK(hipGetLastError());
-    return PEDP_OK;
+    return launch_search<false>(c, mesh, a, N);
+}
+
+// The same search for pedp_fit_to_surface (pedp_surface_fit.hip): every finite row of pts goes through T (device, 4 x 4)
+// as it is loaded, the whole launch exits at once when *done is set, and the pair counter is the caller's (the fit zeroes
+// it once per call, so pedp_closest_last_stats keeps answering for the last pedp_closest_points).
+int pedp_closest_launch_posed(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64_t N, const double *T, const int *done,
+                              unsigned long long *pairs, double *closest, double *dist, uint32_t *prim_id) {
+    FitArgs a;
+    a.pts = pts;
+    a.T = T; a.done = done;
+    a.closest = closest; a.dist = dist; a.prim = prim_id; a.uv = nullptr; a.side = nullptr; a.region = nullptr;
+    a.pairs = pairs;
+    return launch_search<true>(c, mesh, a, N);
 }
 
 extern "C" {

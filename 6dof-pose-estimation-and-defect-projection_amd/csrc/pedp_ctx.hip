@@ -288,6 +288,8 @@ void pedp_ctx_destroy(pedp_ctx_t c) {
     c->metrics_io.release();
     c->closest_ws.release();
     c->closest_io.release();
+    c->fit_ws.release();
+    c->fit_io.release();
     c->stats_ws.release();
     c->stats_io.release();
     if (c->pinned) (void)hipHostFree(c->pinned);

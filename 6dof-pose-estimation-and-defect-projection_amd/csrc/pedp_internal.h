@@ -171,6 +171,8 @@ struct pedp_ctx_s {
     pedp_scratch metrics_io; // pose errors: inputs and outputs of host-memory calls
     pedp_scratch closest_ws; // closest points: the counter of tested point-triangle pairs (pedp_closest.hip)
     pedp_scratch closest_io; // closest points: inputs and outputs of host-memory calls
+    pedp_scratch fit_ws;     // surface fit: the state, the search's outputs, the blocks' partial sums, the trace (pedp_surface_fit.hip)
+    pedp_scratch fit_io;     // surface fit: the points of a host-memory call
     int closest_mode = 0;    // pedp_closest_configure: 0 culled (the kernel by N), 1 exhaustive, 2 / 3 one culled kernel
 };
 
@@ -242,6 +244,11 @@ struct pedp_cloud_s {
 // (nullable): the rule 1 ... 7 of pedp.h's table that decided the chosen triangle's closest point, 0 where there is none
 int pedp_closest_launch(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64_t N, double *closest, double *dist, uint32_t *prim_id,
                         double *uv, int8_t *side, uint8_t *region);
+
+// the same search for pedp_fit_to_surface: the finite rows go through T (device, row-major 4 x 4) as they are loaded, the launch
+// exits at once when *done (device) is set, and `pairs` (device, zeroed by the caller) counts the pairs tested
+int pedp_closest_launch_posed(pedp_ctx_t c, pedp_mesh_t mesh, const double *pts, int64_t N, const double *T, const int *done,
+                              unsigned long long *pairs, double *closest, double *dist, uint32_t *prim_id);
 
 // pedp_icp.hip: frees the job of a pedp_icp_begin that was never ended (called by pedp_ctx_destroy)
 void pedp_icp_drop_pending(pedp_ctx_t c);

@@ -844,6 +844,48 @@ int pedp_closest_last_stats(pedp_ctx_t ctx, int64_t *pairs_tested);
  * Memory, bounds and the pending-registration rule as pedp_closest_points. */
 int pedp_mesh_face_normals(pedp_ctx_t ctx, pedp_mesh_t mesh, const uint32_t *prim_id, int64_t N, int mem, double *normals);
 
+/* ---------------------------------------------------------------- robust best fit of a cloud to the mesh's surface
+ * Iteratively re-weighted Gauss-Newton of N points onto the mesh as posed: the pose correction T (row-major 4 x 4) that
+ * brings the points onto the surface itself, with a loss that keeps a defect from pulling the pose.  The whole loop runs
+ * on the device; the contract is DESIGN.md s4.21.  State: T, float64, starting from `init` (HOST memory whatever `mem` is,
+ * read before the call returns; null: the identity).  Pass p = 0, 1, ...:
+ *   search     for every finite row p_i of pts (never rewritten): q_i = R p_i + t of the current T, each component
+ *              ((T[4k] x + T[4k+1] y) + T[4k+2] z) + T[4k+3]; (c_i, d_i, face_i) of q_i from the search of
+ *              pedp_closest_points (the same point_triangle, selection and culling margin).  A non-finite row, and a row
+ *              with no triangle, takes no part
+ *   row        an inlier has d_i <= gate; every other row adds nothing to any sum.  r = q - c (the bits the search formed),
+ *              n = r / d componentwise when d > 0, else the unit normal of face_i as pedp_mesh_face_normals forms it.
+ *              weight w: PEDP_FIT_L2 1; PEDP_FIT_HUBER 1 if d <= scale, else scale / d; PEDP_FIT_TUKEY
+ *              t t with t = 1 - u u, u = d / scale, if d < scale, else 0.  J = [q x n, n] (the cross product as above),
+ *              wJ = w J componentwise
+ *   sums       the packet: [0, 21) wJ_a J_b for a <= b row by row of the upper triangle, [21, 27) wJ_a d, [27] d d,
+ *              [28] 1 (their sum is K), [29] w.  Blocks of 256 consecutive points; inside a block the 64 rows of each
+ *              quarter by a butterfly (l with l ^ 32, then ^ 16, 8, 4, 2, 1), the quarters as (s0 + s1) + (s2 + s3); then
+ *              the blocks in index order, starting from 0.  No floating-point atomics: the packet's bits depend on the
+ *              points, the records and T alone, not on the search kernel, the context's history or `mem`
+ *   close      fitness = K / (finite rows), rmse = sqrt(packet[27] / K), both 0 when K = 0; trace row p (if asked for):
+ *              fitness, rmse, T as the pass found it, 18 doubles like pedp_icp's.  The loop ends when p == max_iteration,
+ *              when K == 0, or when p > 0 and |fitness - previous| < relative_fitness and |rmse - previous| <
+ *              relative_rmse.  Otherwise x = solve(A, -b) by pedp_icp's pivoted LDLT, upd = its T(x) (Rz Ry Rx of x[2],
+ *              x[1], x[0] and the translation x[3..5]), T <- upd T.  A non-finite x or T ends the loop with T unchanged and
+ *              `singular` set; so does a pass whose sums are not finite (a pose thrown far off by a rank-deficient solve):
+ *              T, fitness, rmse and the packet are then those of the last pass that could be closed
+ * scale is in the mesh's units and must be positive for HUBER and TUKEY (ignored for L2); gate >= 0 (+inf: none);
+ * 0 <= max_iteration <= 1000.  pts, T_out (16), stats_out (PEDP_FIT_STATS_DOUBLES) and trace_out (18 x (max_iteration + 1),
+ * rows behind the last pass left as they were (PEDP_DEVICE) or zero (PEDP_HOST)) are host or device memory by `mem`; the
+ * three outputs may be null.  stats_out: [0] fitness and [1] rmse of the last pass, [2] its index (the updates applied),
+ * [3] K, [4] sum of w, [5] 1 if a solve was singular, [6] finite rows, [7] 0, [8, 38) the packet of the last pass, [38, 40) 0.
+ * All passes are enqueued without a host wait (a device flag turns the launches behind the last pass into early exits);
+ * PEDP_DEVICE only enqueues, PEDP_HOST reads the results back once at the end.  N = 0 gives T = init and zero statistics;
+ * N > 2^24 is PEDP_ERR_BAD_ARG.  The workspace is the call's own (not pedp_icp's), but a context holds one of it and the
+ * passes are ordered on its stream: while a registration is pending on ctx (pedp_icp_begin) the call is
+ * PEDP_ERR_BAD_ARG in either memory form. */
+enum { PEDP_FIT_L2 = 0, PEDP_FIT_HUBER = 1, PEDP_FIT_TUKEY = 2 };
+#define PEDP_FIT_STATS_DOUBLES 40
+int pedp_fit_to_surface(pedp_ctx_t ctx, pedp_mesh_t mesh, const double *pts, int64_t N, int mem, const double *init, int loss,
+                        double scale, double gate, int max_iteration, double relative_fitness, double relative_rmse,
+                        double *T_out, double *stats_out, double *trace_out);
+
 /* ---------------------------------------------------------------- the defect map: per-face accumulation and regions
  * What the projected heat maps of many frames say about the CAD model itself: per face the peak intensity, the hits and
  * the frames that saw it, and the connected regions of the marked faces with their sizes.  It stands in the place of
