@@ -187,6 +187,16 @@ PROTOTYPES = {
     "pedp_coverage_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_coverage_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                         _P(C.c_int64)]),
+    "pedp_view_plan_create": (C.c_int, [C.c_void_p, C.c_int64, _P(C.c_void_p)]),
+    "pedp_view_plan_destroy": (C.c_int, [C.c_void_p]),
+    "pedp_view_plan_clear": (C.c_int, [C.c_void_p]),
+    "pedp_view_plan_observe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, _P(C.c_int64)]),
+    "pedp_view_plan_candidate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_view_plan_reset": (C.c_int, [C.c_void_p]),
+    "pedp_view_plan_commit": (C.c_int, [C.c_void_p, C.c_int64]),
+    "pedp_view_plan_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "pedp_view_plan_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int64),
+                                        C.c_void_p]),
     "pedp_solid_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, _P(C.c_void_p)]),
     "pedp_solid_destroy": (C.c_int, [C.c_void_p]),
     "pedp_solid_get_info": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -34,6 +34,7 @@ SOURCES = {
     "pedp_closest.hip": [],
     "pedp_defectmap.hip": [],
     "pedp_coverage.hip": [],
+    "pedp_viewplan.hip": [],
     "pedp_solid.hip": [],
     "pedp_surface_fit.hip": [],
     "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

@@ -13,7 +13,8 @@ exact cloud-to-mesh distance with the deviation heat map (`closest_points`, `com
 `deviation_heatmap`, surface_distance.py), and the robust best fit of the scene to that surface, the pose the deviation
 is measured in (`fit_to_surface`, `refit_pose`, `fit_frame_to_surface`, surface_fit.py), and the defect map on the model in the place of run.py:196-201's list of
 hit clouds (`DefectMap`, defect_map.py), and the inspection coverage over its faces, which the reference has no
-counterpart of (`CoverageMap`, coverage.py); the Dash app, sensor
+counterpart of (`CoverageMap`, coverage.py), and the next camera poses that coverage asks for (`ViewPlanner`,
+`orbit_views`, view_plan.py); the Dash app, sensor
 code and the networks' weights stay the reference's own.
 """
 import numpy as np
@@ -65,6 +66,7 @@ from .surface_distance import (Solid, compute_occupancy, compute_signed_distance
 from .surface_fit import fit_frame_to_surface, fit_to_surface, refit_pose  # noqa: E402,F401  (between refine_pose_with_icp and the heat map)
 from .defect_map import DefectMap  # noqa: E402,F401  (run.py:61, :119, :196-201: the history of hits, kept per face)
 from .coverage import CoverageMap  # noqa: E402,F401  (no counterpart: run.py never says what was not inspected)
+from .view_plan import ViewPlanner, orbit_views  # noqa: E402,F401  (no counterpart: where to point the camera next)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
 
@@ -101,5 +103,5 @@ __all__ = [
     "closest_points", "compute_distance", "align_to_mesh", "deviation_heatmap",
     "Solid", "compute_signed_distance", "compute_occupancy", "signed_closest_points", "signed_deviation", "split_deviation",
     "fit_to_surface", "refit_pose", "fit_frame_to_surface",
-    "DefectMap", "CoverageMap",
+    "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views",
 ]

@@ -6,11 +6,10 @@
 //     smallest footprint of a pixel on it, and the pixels where something stood in front of it.
 // Integer atomics only, as in pedp_defectmap.hip: the cosine's maximum through the order-preserving key, the footprint's
 // minimum on the bits of a non-negative double, counts and the view stamp.  The areas, centroids, boxes, the welded
-// adjacency and the regions' body are the defect map's (defectmap/shared.h): one weld and one adjacency per model.
-#include "defectmap/shared.h"
-#include "camera/pixel_ray.h"
-#include "mesh/record.h"
-#include <cmath>
+// adjacency and the regions' body are the defect map's (defectmap/shared.h): one weld and one adjacency per model.  The
+// per-pixel rule, the state's criteria, the summary's sums and the handle are in coverage/shared.h, which the view
+// planner (pedp_viewplan.hip) includes too.
+#include "coverage/shared.h"
 
 #ifndef PEDP_COVERAGE_COMBINE
 #define PEDP_COVERAGE_COMBINE 1  // 0: every pixel goes to the atomics itself (the A/B of profiles/coverage_time.json)
@@ -18,69 +17,17 @@
 
 namespace {
 
-using namespace defectmap;
+using namespace coverage;
 
-constexpr int64_t MAX_PIXELS = (int64_t)1 << 31;
-constexpr int SUM_BLOCK = 4096;  // faces one wave sums (64 per lane): pedp_defectmap.hip's block
-constexpr int SUM_WPB = DT / 64;
-constexpr unsigned long long NEVER = ~0ull;  // min_footprint's bits of a face never seen
-constexpr int COUNTER_SLOTS = 64;            // copies of the seven class counters: a block adds to copy blockIdx % 64
+constexpr int COUNTER_SLOTS = 64;  // copies of the seven class counters: a block adds to copy blockIdx % 64
 
-enum : int { MASKED = 0, MISS = 1, NO_DEPTH = 2, OCCLUDED = 3, BEHIND = 4, GRAZING = 5, SEEN = 6, N_CLASSES = 7 };
-
-struct AddArgs {
-    const float *t;
-    const uint32_t *id;
-    const float *depth;   // nullable
-    const uint8_t *mask;  // nullable
-    uint8_t *status;      // nullable
-    const float *tri;     // the mesh's records as posed
-    int64_t n, F;
-    camera::Cam cam;
-    double fxfy, depth_scale, depth_tol, min_cos;
-    float z_min;
-    uint32_t view;  // this view's stamp, 1 ...
+struct AddArgs : View {
+    uint8_t *status;  // nullable
+    uint32_t view;    // this view's stamp, 1 ...
     unsigned long long *pixels, *blocked, *best, *minfp, *counters;
     int32_t *views;
     uint32_t *stamp;
 };
-
-// The class of pixel i (the table of pedp.h, first rule that holds); for OCCLUDED and SEEN the face, for SEEN the key
-// of the cosine and the bits of the footprint (NEVER: a NaN footprint, t = 0 on an edge-on face, takes no part).
-__device__ __forceinline__ int classify(const AddArgs &a, int64_t i, uint32_t &f, unsigned long long &key, unsigned long long &fp) {
-    if (a.mask && a.mask[i] == 0) return MASKED;
-    const uint32_t id = a.id[i];
-    const float tf = a.t[i];
-    if ((int64_t)id >= a.F || (__float_as_uint(tf) & 0x7F800000u) == 0x7F800000u) return MISS;
-    float dm = 0.0f;
-    if (a.depth) {
-        dm = a.depth[i];
-        if (!(dm >= a.z_min) || dm == __builtin_inff()) return NO_DEPTH;
-    }
-    double d[3];
-    camera::pixel_direction(a.cam, i, d);
-    for (int k = 0; k < 3; ++k) d[k] = (double)(float)d[k];  // the ray that was cast
-    const double z_hit = (double)tf * d[2];
-    f = id;
-    if (a.depth) {
-        const double diff = (double)dm * a.depth_scale - z_hit;
-        if (diff < -a.depth_tol) return OCCLUDED;
-        if (diff > a.depth_tol) return BEHIND;
-    }
-    double cosine = 0.0;  // a record no ray can hit, or a normal that is NaN: edge on
-    record::Tri tr;
-    if (record::load_tri(a.tri + (size_t)id * PEDP_TRI_STRIDE, tr)) {
-        double n[3];
-        record::unit_normal(tr, n);
-        const double dp = fabs(record::dot3(n, d));
-        if (dp > 0.0) cosine = dp < 1.0 ? dp : 1.0;
-    }
-    if (cosine < a.min_cos) return GRAZING;
-    const double foot = ((z_hit * z_hit) * d[2]) / (a.fxfy * cosine);
-    key = key_of(cosine);
-    fp = is_nan_bits(bits_of(foot)) ? NEVER : bits_of(foot);
-    return SEEN;
-}
 
 // One view, a lane per pixel.  A coarse CAD face covers thousands of neighbouring pixels, so a run of equal faces in
 // neighbouring lanes (defectmap/shared.h) sends one maximum, one minimum, its SEEN count, its OCCLUDED count and one
@@ -134,19 +81,6 @@ __global__ __launch_bounds__(DT) void coverage_add_kernel(AddArgs a) {
         atomicAdd(&a.counters[(blockIdx.x % COUNTER_SLOTS) * N_CLASSES + threadIdx.x], (unsigned long long)block_count[threadIdx.x]);
 }
 
-struct State {
-    const unsigned long long *pixels, *blocked, *best, *minfp;
-    const int32_t *views;
-};
-__device__ __forceinline__ double best_cos_of(const State &s, int64_t f) { return s.best[f] ? value_of(s.best[f]) : 0.0; }
-__device__ __forceinline__ double min_footprint_of(const State &s, int64_t f) {
-    return s.minfp[f] == NEVER ? record::pos_inf() : double_of(s.minfp[f]);
-}
-__device__ __forceinline__ bool is_covered(const State &s, const pedp_coverage_criteria &c, int64_t f) {
-    return s.views[f] >= c.min_views && (int64_t)s.pixels[f] >= c.min_pixels && best_cos_of(s, f) >= c.min_cos &&
-           min_footprint_of(s, f) <= c.max_footprint;
-}
-
 __global__ __launch_bounds__(DT) void coverage_faces_kernel(State s, int64_t F, int64_t *__restrict__ pixels, int32_t *__restrict__ views,
                                                            double *__restrict__ best_cos, double *__restrict__ min_footprint,
                                                            int64_t *__restrict__ blocked) {
@@ -169,69 +103,7 @@ __global__ __launch_bounds__(DT) void coverage_seed_kernel(State s, pedp_coverag
     mark[f] = m;
 }
 
-// The summary's two areas in s4.17's block-and-butterfly order over the faces in face order: a wave per block of
-// SUM_BLOCK consecutive faces, lane l adds faces l, l + 64, ... of the block one after the other, the butterfly adds the
-// 64 lanes; then one wave adds the block sums l, l + 64, ... the same way.
-struct Sums {
-    double covered_area, total_area;
-    int64_t covered;
-};
-__device__ __forceinline__ void sums_butterfly(Sums &a) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        a.covered_area = a.covered_area + double_of(shfl_xor_u64(bits_of(a.covered_area), off));
-        a.total_area = a.total_area + double_of(shfl_xor_u64(bits_of(a.total_area), off));
-        a.covered += (int64_t)shfl_xor_u64((uint64_t)a.covered, off);
-    }
-}
-__global__ __launch_bounds__(DT) void summary_block_kernel(State s, pedp_coverage_criteria c, const double *__restrict__ area, int64_t F,
-                                                          int64_t n_blocks, Sums *__restrict__ part) {
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * SUM_WPB + (threadIdx.x >> 6);
-    if (w >= n_blocks) return;  // wave-uniform
-    const int64_t f0 = w * SUM_BLOCK, f1 = f0 + SUM_BLOCK < F ? f0 + SUM_BLOCK : F;
-    Sums a{0.0, 0.0, 0};
-    for (int64_t f = f0 + lane; f < f1; f += 64) {
-        const double ar = area[f];
-        a.total_area = a.total_area + ar;
-        if (is_covered(s, c, f)) {
-            a.covered_area = a.covered_area + ar;
-            a.covered += 1;
-        }
-    }
-    sums_butterfly(a);
-    if (lane == 0) part[w] = a;
-}
-__global__ __launch_bounds__(64) void summary_total_kernel(const Sums *__restrict__ part, int64_t n_blocks, Sums *__restrict__ out) {
-    const int lane = threadIdx.x;
-    Sums a{0.0, 0.0, 0};
-    for (int64_t b = lane; b < n_blocks; b += 64) {
-        a.covered_area = a.covered_area + part[b].covered_area;
-        a.total_area = a.total_area + part[b].total_area;
-        a.covered += part[b].covered;
-    }
-    sums_butterfly(a);
-    if (lane == 0) *out = a;
-}
-
-const pedp_coverage_criteria DEFAULT_CRITERIA = {1, 1, 0.0, HUGE_VAL};
-
 }  // namespace
-
-struct pedp_coverage_s {
-    pedp_defect_map_s *map = nullptr;  // borrowed: it must outlive this handle
-    pedp_ctx_t ctx = nullptr;
-    int device = 0;
-    int64_t F = 0;
-    char *store = nullptr;  // one allocation: everything below
-    unsigned long long *pixels = nullptr, *blocked = nullptr, *best = nullptr, *minfp = nullptr, *counters = nullptr;
-    int32_t *views = nullptr;
-    uint32_t *stamp = nullptr;
-    size_t zero_bytes = 0, ones_off = 0, ones_bytes = 0;  // what clear sets to 0 and to all ones (minfp)
-    int64_t n_views = 0;
-    pedp_scratch io;  // staging of host-memory calls; the summary's block sums
-    State state() const { return State{pixels, blocked, best, minfp, views}; }
-};
 
 namespace {
 int clear_state(pedp_coverage_s *v) {
@@ -426,9 +298,7 @@ int pedp_coverage_summary(pedp_coverage_t v, const pedp_coverage_criteria *crit,
     if (rc) return rc;
     Sums *part = (Sums *)v->io.ptr, *total = part + n_blocks;
     const pedp_coverage_criteria k = crit ? *crit : DEFAULT_CRITERIA;
-    hipLaunchKernelGGL(summary_block_kernel, dim3((unsigned)((n_blocks + SUM_WPB - 1) / SUM_WPB)), dim3(DT), 0, c->stream, v->state(), k,
-                       v->map->area, v->F, n_blocks, part);
-    hipLaunchKernelGGL(summary_total_kernel, dim3(1), dim3(64), 0, c->stream, part, n_blocks, total);
+    launch_summary(c->stream, v->state(), k, v->map->area, v->F, part, total);
     PEDP_HIP_CHECK(hipGetLastError());
     Sums s;
     rc = pedp_download(c, &s, total, sizeof(s));

@@ -1050,6 +1050,67 @@ int pedp_coverage_summary(pedp_coverage_t cov, const pedp_coverage_criteria *c, 
 int pedp_coverage_regions(pedp_coverage_t cov, const pedp_coverage_criteria *c, int covered, int32_t grow, int mem, int32_t *labels,
                           int64_t capacity, pedp_defect_region *table, int64_t *n_regions);
 
+/* ---------------------------------------------------------------- next-best-view planning over the coverage map
+ * pedp_coverage_regions says where the part was not looked at; the view plan turns that into the next camera poses: it
+ * keeps what each of a set of CANDIDATE views would add to the coverage map, scores all of them against a working copy of
+ * the map's state, and picks greedily.  The coverage map itself is never written by any call here.  The contract is
+ * DESIGN.md s4.22.
+ *
+ * pedp_view_plan_create: room for `capacity` (>= 1) candidates over the faces of `cov`, on its context: one allocation of
+ * capacity F 20 bytes of observation columns plus the working state and the sums' scratch; a failed allocation is
+ * PEDP_ERR_HIP.  The plan starts without candidates and with the working state of a map that saw nothing.  The coverage
+ * handle must outlive the plan.  PEDP_ERR_BAD_ARG while a registration is pending on the context.
+ * pedp_view_plan_clear forgets the candidates (the working state stays).
+ *
+ * pedp_view_plan_observe appends one candidate and returns its index: mesh, cam, t_hit, prim_id and min_cos are those of
+ * a pedp_coverage_add WITHOUT depth and mask, and the candidate's row holds, per face f, what that view would add:
+ *   cpix[f]  the SEEN pixels on f (uint32)      ckey[f]  the largest key of their cosines (0: none)
+ *   cfp[f]   the bits of their smallest footprint (all ones: none)
+ * by the per-pixel rule of pedp_coverage_add, bit for bit (one routine serves both).  Integer atomics only.  The checks
+ * are pedp_coverage_add's, and the plan must not be full.  PEDP_DEVICE only enqueues and is allowed while a registration
+ * is pending; PEDP_HOST copies in, returns after completion and is PEDP_ERR_BAD_ARG then.
+ * pedp_view_plan_candidate reads row v back in the units of pedp_coverage_faces (pixels, best_cos 0.0 / min_footprint
+ * +inf where the view sees nothing of the face); every pointer nullable, host or device memory by `mem`.
+ *
+ * The WORKING STATE w is the plan's own copy of the map's per-face pixels, views, best and minfp.
+ * pedp_view_plan_reset: w := the coverage map's state now.  pedp_view_plan_commit: candidate v is MERGED into w, per face
+ *   pixels += cpix;  views += (cpix > 0);  key = max(key, ckey);  fp = min(fp, cfp) on the bits
+ * which is the state pedp_coverage_add of that view would leave.  Both only enqueue.
+ *
+ * PROGRESS of a face under criteria c (NULL: 1, 1, 0, +inf) is the integer
+ *   n = (pixels >= c.min_pixels && best_cos >= c.min_cos && min_footprint <= c.max_footprint)
+ *         ? (c.min_views <= 0 ? 1 : min(views, c.min_views)) : 0,      m = max(c.min_views, 1)
+ * so n == m exactly when the face is covered.  The GAIN of candidate v against w: per face D = n(w merged with v) - n(w)
+ * (>= 0; 0 wherever cpix is 0), the term (area[f] (double)D) / (double)m (+0 where D is 0), and
+ *   gain_area[v]   the sum of the terms in s4.17's block-and-butterfly order over the faces in face order (blocks of
+ *                  4096 consecutive faces, lane l adds l, l + 64, ... one after the other from +0, the butterfly xor
+ *                  32 ... 1 adds the lanes, one wave adds the block sums the same way); no floating-point atomic
+ *   gain_faces[v]  the faces with n(w) < m and n(merged) == m
+ * With min_views 1 the gain is the area pedp_coverage_add at that pose would newly cover; with min_views 2 a first
+ * qualifying view earns half a face's area.  pedp_view_plan_score: both for every candidate (n values each, either
+ * pointer nullable), host or device memory; PEDP_DEVICE only enqueues.
+ *
+ * pedp_view_plan_select: w := the map's state, no candidate chosen; then at most k rounds: score the candidates not yet
+ * chosen; among those whose gain_area is > min_gain take the largest, the lowest index among equals (a NaN never wins);
+ * if there is none, stop; else record (index, gain_area, gain_faces), merge the candidate into w and mark it chosen.  The
+ * rounds are enqueued back to back, the choice and the stop are made on the device, and the host waits once.  order,
+ * gain_area and gain_faces (room for min(k, candidates) entries each, nullable) get the *n_selected recorded rounds;
+ * totals (nullable) the summary of w afterwards, as pedp_coverage_summary forms it.  w stays as the rounds left it.
+ * pedp_view_plan_select, and _candidate / _score / _observe with PEDP_HOST, wait on the stream: PEDP_ERR_BAD_ARG while a
+ * registration is pending. */
+typedef struct pedp_view_plan_s *pedp_view_plan_t;
+int pedp_view_plan_create(pedp_coverage_t cov, int64_t capacity, pedp_view_plan_t *out);
+int pedp_view_plan_destroy(pedp_view_plan_t plan);
+int pedp_view_plan_clear(pedp_view_plan_t plan);
+int pedp_view_plan_observe(pedp_view_plan_t plan, pedp_mesh_t mesh, const pedp_pinhole *cam, const float *t_hit, const uint32_t *prim_id,
+                           double min_cos, int mem, int64_t *index);
+int pedp_view_plan_candidate(pedp_view_plan_t plan, int64_t v, int mem, int64_t *pixels, double *best_cos, double *min_footprint);
+int pedp_view_plan_reset(pedp_view_plan_t plan);
+int pedp_view_plan_commit(pedp_view_plan_t plan, int64_t v);
+int pedp_view_plan_score(pedp_view_plan_t plan, const pedp_coverage_criteria *c, int mem, double *gain_area, int64_t *gain_faces);
+int pedp_view_plan_select(pedp_view_plan_t plan, const pedp_coverage_criteria *c, int64_t k, double min_gain, int32_t *order,
+                          double *gain_area, int64_t *gain_faces, int64_t *n_selected, pedp_coverage_totals *totals);
+
 /* ---------------------------------------------------------------- the solid: signed distance and occupancy
  * RaycastingScene.compute_signed_distance / compute_occupancy on the mesh handle: whether a point lies inside the CAD
  * solid (a dent, missing material) or outside it (a burr, excess material), which `side` above cannot tell away from
