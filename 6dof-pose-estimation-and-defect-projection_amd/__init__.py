@@ -16,6 +16,7 @@ Layout
   defect_map.py    DefectMap: per-face accumulation of projected heat maps on the model, and the defect regions
   coverage.py      CoverageMap: which faces of the model the camera has seen, and how well, over a DefectMap's faces
   view_plan.py     ViewPlanner: next-best-view planning, the gain of candidate camera poses over a CoverageMap; orbit_views
+  deviation_map.py DeviationMap: per-face statistics of the signed deviation over frames, regions with their volume
   surface_fit.py   fit_to_surface: robust best fit of a scene cloud to the posed surface itself; refit_pose, fit_frame_to_surface
   compat.py        `from pedp_hip.compat import *` in place of `from src import *` (run.py:3)
   dist.py          one-process-per-GPU sharding over torch.distributed (RCCL)
@@ -26,5 +27,6 @@ from ._lib import PedpError, LIB_PATH
 from .defect_map import DefectMap
 from .coverage import CoverageMap
 from .view_plan import ViewPlanner, orbit_views
+from .deviation_map import DeviationMap
 
-__all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views"]
+__all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap"]

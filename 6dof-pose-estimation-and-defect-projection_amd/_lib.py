@@ -187,6 +187,17 @@ PROTOTYPES = {
     "pedp_coverage_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_coverage_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                         _P(C.c_int64)]),
+    "pedp_deviation_map_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "pedp_deviation_map_destroy": (C.c_int, [C.c_void_p]),
+    "pedp_deviation_map_clear": (C.c_int, [C.c_void_p]),
+    "pedp_deviation_map_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int]),
+    "pedp_deviation_map_add_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double,
+                                                C.c_void_p]),
+    "pedp_deviation_map_faces": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 9),
+    "pedp_deviation_map_stats": (C.c_int, [C.c_void_p] + [_P(C.c_int64)] * 5),
+    "pedp_deviation_map_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pedp_deviation_map_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                             _P(C.c_int64)]),
     "pedp_view_plan_create": (C.c_int, [C.c_void_p, C.c_int64, _P(C.c_void_p)]),
     "pedp_view_plan_destroy": (C.c_int, [C.c_void_p]),
     "pedp_view_plan_clear": (C.c_int, [C.c_void_p]),
@@ -460,6 +471,16 @@ class CoverageCriteria(C.Structure):  # pedp_coverage_criteria
 
 class CoverageTotals(C.Structure):    # pedp_coverage_totals
     _fields_ = [("covered_faces", C.c_int64), ("faces", C.c_int64), ("covered_area", C.c_double), ("total_area", C.c_double)]
+
+
+class DeviationCriteria(C.Structure):  # pedp_deviation_criteria
+    _fields_ = [("threshold", C.c_double), ("z", C.c_double), ("min_samples", C.c_int64), ("min_frames", C.c_int32), ("sign", C.c_int32)]
+
+
+class DeviationTotals(C.Structure):    # pedp_deviation_totals
+    _fields_ = [("faces", C.c_int64), ("measured_faces", C.c_int64), ("marked_faces", C.c_int64), ("max_face", C.c_int64),
+                ("total_area", C.c_double), ("measured_area", C.c_double), ("marked_area", C.c_double), ("mean", C.c_double),
+                ("rms", C.c_double), ("max_abs_mean", C.c_double)]
 
 
 class Mesh:

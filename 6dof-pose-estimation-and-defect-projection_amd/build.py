@@ -35,6 +35,7 @@ SOURCES = {
     "pedp_defectmap.hip": [],
     "pedp_coverage.hip": [],
     "pedp_viewplan.hip": [],
+    "pedp_deviationmap.hip": [],
     "pedp_solid.hip": [],
     "pedp_surface_fit.hip": [],
     "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

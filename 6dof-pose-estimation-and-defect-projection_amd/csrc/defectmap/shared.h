@@ -87,6 +87,16 @@ __device__ __forceinline__ unsigned long long run_min(unsigned long long v, int 
     }
     return v;
 }
+// the sum (modulo 2^64, so two's complement sums too) of `v` over the lanes [lane, end] of a run: step `off` adds the sum
+// of the lanes [lane + off, min(lane + 2 off - 1, end)], so every lane of the run is added once
+__device__ __forceinline__ unsigned long long run_sum(unsigned long long v, int lane, int end) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long v2 = shfl_down_u64(v, off);
+        if (lane + off <= end) v += v2;
+    }
+    return v;
+}
 
 }  // namespace defectmap
 }  // namespace

@@ -10,25 +10,17 @@
 //     edge or vertex: Baerentzen & Aanaes 2005) and signs the distance with (p - c) . N.
 // float64 with no contraction, every expression in the order written, no floating-point atomics: the vertex sums
 // run over the corner lists in their stored order, the volume is a block-tree sum.  tests/_signed_ref.py restates it.
-#include "pedp_internal.h"
-#include "mesh/record.h"
+#include "solid/shared.h"
 #include "mesh/topology.h"
 #include <cmath>
 
 namespace {
 
-using namespace record;
+using namespace solid;
 
-constexpr int ST = 256;                  // threads per block
 constexpr int64_t MAX_FACES = 1 << 28;   // 3 F slots are sorted with int32 positions
-constexpr int64_t MAX_POINTS = (int64_t)1 << 24;
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int VOL_BLOCK = 4096;          // faces of one block's partial volume (16 per thread)
 enum { C_WELDED = 0, C_EDGES, C_BOUNDARY, C_NONMANIFOLD, C_FLIPPED, C_DEGENERATE, C_VOLUME, C_COUNT };
-enum { FEATURE_FACE = 0, FEATURE_EDGE = 1, FEATURE_VERTEX = 2, FEATURE_NONE = 255 };
-
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + ST - 1) / ST); }
 
 // one atomic per wave: the number of lanes whose `flag` is set
 __device__ __forceinline__ void count_lanes(bool flag, unsigned long long *counter) {
@@ -138,51 +130,14 @@ __global__ __launch_bounds__(ST) void volume_final_kernel(const double *__restri
     if (threadIdx.x == 0) *out = total;
 }
 
-__global__ __launch_bounds__(ST) void index_compare_kernel(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, int64_t E,
-                                                          uint32_t *__restrict__ differs) {
-    const int64_t e = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (e < E && a[e] != b[e]) atomicOr(differs, 1u);
-}
-
 // ------------------------------------------------------------------ the query
-// The angle-weighted pseudonormal of every welded vertex from the records as posed: over the vertex's corners in list
-// order, N = N + n angle with n the face's unit normal and angle = atan2(|q x s|, q . s) between the record's two edges
-// q, s that leave the corner.  Records that load_tri refuses, and faces whose normal has no length, add nothing.
-__global__ __launch_bounds__(ST) void vertex_normal_kernel(const float *__restrict__ rec, const uint32_t *__restrict__ vstart,
-                                                          const uint32_t *__restrict__ vcount, const int32_t *__restrict__ corner, int64_t V,
-                                                          double *__restrict__ table) {
-    const int64_t v = (int64_t)blockIdx.x * ST + threadIdx.x;
-    if (v >= V) return;
-    const uint32_t p0 = vstart[v];
-    if (p0 == NONE) return;  // welded to a lower vertex, or in no face: never looked up
-    double N[3] = {0.0, 0.0, 0.0};
-    const uint32_t n = vcount[v];
-    for (uint32_t j = 0; j < n; ++j) {
-        const int32_t e = corner[p0 + j];
-        const int32_t f = e / 3, k = e - 3 * f;
-        Tri t;
-        if (!load_tri(rec + (size_t)f * PEDP_TRI_STRIDE, t)) continue;
-        double nh[3], q[3], s[3], qs[3];
-        unit_normal(t, nh);
-        if (!(nh[0] == nh[0])) continue;
-        for (int d = 0; d < 3; ++d) {
-            q[d] = k == 0 ? t.ab[d] : (k == 1 ? t.ac[d] - t.ab[d] : -t.ac[d]);
-            s[d] = k == 0 ? t.ac[d] : (k == 1 ? -t.ab[d] : t.ab[d] - t.ac[d]);
-        }
-        cross3(q, s, qs);
-        const double angle = atan2(sqrt(dot3(qs, qs)), dot3(q, s));
-        for (int d = 0; d < 3; ++d) N[d] = N[d] + nh[d] * angle;
-    }
-    table[3 * v] = N[0]; table[3 * v + 1] = N[1]; table[3 * v + 2] = N[2];
-}
-
+// the vertex pseudonormals and the sign of a point: solid/shared.h
 struct FinishArgs {
-    const float *rec;
-    const double *pts, *closest, *dist, *table;
-    const uint32_t *prim, *wid, *twin;
+    SignArgs sign;
+    const double *pts, *closest, *dist;
+    const uint32_t *prim;
     const uint8_t *region;
     int64_t n;
-    double orientation;  // +1 / -1
     double *sdist, *normal;
     int8_t *occupancy;
     uint8_t *feature;
@@ -194,37 +149,13 @@ __global__ __launch_bounds__(ST) void finish_kernel(FinishArgs a) {
     const uint32_t f = a.prim[i];
     double sd = a.dist[i];  // no triangle: NaN for a non-finite point, +inf otherwise
     double nrm[3] = {quiet_nan(), quiet_nan(), quiet_nan()};
-    int feature = FEATURE_NONE;
-    Tri t;
-    if (f != NONE && load_tri(a.rec + (size_t)f * PEDP_TRI_STRIDE, t)) {
-        const int rule = a.region[i];
-        double N[3];
-        if (rule == 1 || rule == 2 || rule == 4) {  // corners 0, 1, 2
-            feature = FEATURE_VERTEX;
-            const size_t v = a.wid[3 * (size_t)f + (rule >> 1)];
-            N[0] = a.table[3 * v]; N[1] = a.table[3 * v + 1]; N[2] = a.table[3 * v + 2];
-        } else {
-            unit_normal(t, N);
-            if (rule != 7) {  // rules 3, 6, 5: the edge slots 0 (ab), 1 (bc), 2 (ca)
-                feature = FEATURE_EDGE;
-                const uint32_t tw = a.twin[3 * (size_t)f + (rule == 3 ? 0 : (rule == 6 ? 1 : 2))];
-                Tri u;
-                double m[3];
-                if (tw != NONE && load_tri(a.rec + (size_t)(tw / 3) * PEDP_TRI_STRIDE, u)) {
-                    unit_normal(u, m);
-                    if (m[0] == m[0])
-                        for (int d = 0; d < 3; ++d) N[d] = N[d] + m[d];
-                }
-            } else {
-                feature = FEATURE_FACE;
-            }
-        }
-        double r[3];
-        for (int d = 0; d < 3; ++d) r[d] = a.pts[3 * i + d] - a.closest[3 * i + d];
-        const double s = dot3(r, N) * a.orientation;
-        if (s < 0.0) sd = -sd;  // s == 0 counts as outside
+    double N[3];
+    const double p[3] = {a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2]};
+    const double c[3] = {a.closest[3 * i], a.closest[3 * i + 1], a.closest[3 * i + 2]};
+    const int feature = sign_of_point(a.sign, f, f != NONE ? a.region[i] : 0, p, c, sd, N);
+    if (feature != FEATURE_NONE) {
         const double len = sqrt(dot3(N, N));
-        for (int d = 0; d < 3; ++d) nrm[d] = (N[d] / len) * a.orientation;
+        for (int d = 0; d < 3; ++d) nrm[d] = (N[d] / len) * a.sign.orientation;
     }
     if (a.sdist) a.sdist[i] = sd;
     if (a.occupancy) a.occupancy[i] = (int8_t)(sd < 0.0);
@@ -233,21 +164,6 @@ __global__ __launch_bounds__(ST) void finish_kernel(FinishArgs a) {
 }
 
 }  // namespace
-
-struct pedp_solid_s {
-    pedp_ctx_t ctx = nullptr;
-    int device = 0;
-    pedp_solid_info info = {};
-    char *store = nullptr;  // one allocation: everything below
-    uint32_t *tri = nullptr;     // 3 F: the index buffer (what a posable mesh's own is compared with)
-    uint32_t *wid = nullptr;     // 3 F: the welded id of every corner
-    uint32_t *twin = nullptr;    // 3 F: the twin of every edge slot, or NONE
-    int32_t *corner = nullptr;   // 3 F: the corners sorted by (welded id, face, corner)
-    uint32_t *vstart = nullptr, *vcount = nullptr;  // V: a welded vertex's run in `corner` (NONE, 0: it has none)
-    uint64_t verified_gen = 0;   // the posable mesh whose index buffer was found equal
-    pedp_scratch ws;  // a query: the vertex table and the search's outputs; the build's scratch
-    pedp_scratch io;  // staging of host-memory calls
-};
 
 namespace {
 
@@ -370,39 +286,22 @@ int pedp_solid_get_info(pedp_solid_t s, pedp_solid_info *out) {
 int pedp_signed_distance(pedp_ctx_t c, pedp_mesh_t mesh, pedp_solid_t solid, const double *pts, int64_t N, int mem, double *sdist,
                          int8_t *occupancy, uint8_t *feature, double *normal) {
     const char *who = "pedp_signed_distance";
-    PEDP_REQUIRE(c && mesh && solid, "%s: null context/mesh/solid", who);
-    PEDP_REQUIRE(mesh->ctx == c && solid->ctx == c, "%s: the %s belongs to another context", who, mesh->ctx == c ? "solid" : "mesh");
-    PEDP_REQUIRE(mem == PEDP_HOST || mem == PEDP_DEVICE, "%s: bad mem flag %d", who, mem);
-    PEDP_REQUIRE(N >= 0 && N <= MAX_POINTS, "%s: N = %lld, at most %lld points", who, (long long)N, (long long)MAX_POINTS);
+    int rc = check_query(who, c, mesh, solid, N, mem);
+    if (rc) return rc;
     const pedp_solid_info &info = solid->info;
-    PEDP_REQUIRE(info.F == mesh->F, "%s: the solid has %lld faces, the mesh %lld", who, (long long)info.F, (long long)mesh->F);
-    PEDP_REQUIRE(info.F == 0 || (info.closed && info.orientation != 0),
-                 "%s: the mesh bounds no solid (%lld boundary, %lld non-manifold, %lld flipped edges, volume %g)", who,
-                 (long long)info.boundary_edges, (long long)info.nonmanifold_edges, (long long)info.flipped_edges, info.volume);
-    // the workspace is sized by N and V: growing it waits for the device, as the staging of a host-memory call does
-    PEDP_REQUIRE(!c->icp_pending, "%s: a registration is pending on this context (the call may wait for the stream)", who);
     if (N == 0) return PEDP_OK;
     PEDP_REQUIRE(pts, "%s: null points", who);
     PEDP_HIP_CHECK(hipSetDevice(c->device));
-    const int64_t V = info.V, F = info.F, E = 3 * F;
+    const int64_t V = info.V, F = info.F;
     const size_t n = (size_t)N;
-    int rc = PEDP_OK;
     // the vertex table, the search's outputs, the flag of the index comparison
     const size_t o_table = 0, o_cl = o_table + a256(24 * (size_t)V), o_d = o_cl + a256(24 * n), o_id = o_d + a256(8 * n),
                  o_reg = o_id + a256(4 * n), o_flag = o_reg + a256(n), ws_bytes = o_flag + 256;
     rc = solid->ws.reserve(ws_bytes);
     if (rc) return rc;
     char *ws = (char *)solid->ws.ptr;
-    if (F > 0 && mesh->idx && solid->verified_gen != mesh->gen) {  // a posable mesh keeps its index buffer: once per mesh
-        uint32_t *d_flag = (uint32_t *)(ws + o_flag), differs = 0;
-        PEDP_HIP_CHECK(hipMemsetAsync(d_flag, 0, 4, c->stream));
-        hipLaunchKernelGGL(index_compare_kernel, dim3(blocks_for(E)), dim3(ST), 0, c->stream, mesh->idx, solid->tri, E, d_flag);
-        PEDP_HIP_CHECK(hipGetLastError());
-        rc = pedp_download(c, &differs, d_flag, 4);
-        if (rc) return rc;
-        PEDP_REQUIRE(!differs, "%s: the mesh's triangles are not the ones the solid was built from", who);
-        solid->verified_gen = mesh->gen;
-    }
+    rc = verify_indices(who, c, mesh, solid, (uint32_t *)(ws + o_flag));
+    if (rc) return rc;
     const double *d_pts = pts;
     double *d_sd = sdist, *d_nrm = normal;
     int8_t *d_occ = occupancy;
@@ -422,20 +321,20 @@ int pedp_signed_distance(pedp_ctx_t c, pedp_mesh_t mesh, pedp_solid_t solid, con
         d_nrm = normal ? (double *)(io + o_nrm) : nullptr;
     }
     FinishArgs a;
-    a.rec = mesh->tri;
+    a.sign.rec = mesh->tri;
     a.pts = d_pts;
     a.closest = (double *)(ws + o_cl); a.dist = (double *)(ws + o_d); a.prim = (uint32_t *)(ws + o_id); a.region = (uint8_t *)(ws + o_reg);
-    a.table = (double *)(ws + o_table);
-    a.wid = solid->wid; a.twin = solid->twin;
+    a.sign.table = (double *)(ws + o_table);
+    a.sign.wid = solid->wid; a.sign.twin = solid->twin;
     a.n = N;
-    a.orientation = info.orientation < 0 ? -1.0 : 1.0;
+    a.sign.orientation = info.orientation < 0 ? -1.0 : 1.0;
     a.sdist = d_sd; a.normal = d_nrm; a.occupancy = d_occ; a.feature = d_feat;
     rc = pedp_closest_launch(c, mesh, d_pts, N, (double *)a.closest, (double *)a.dist, (uint32_t *)a.prim, nullptr, nullptr,
                              (uint8_t *)a.region);
     if (rc) return rc;
     if (F > 0)
         hipLaunchKernelGGL(vertex_normal_kernel, dim3(blocks_for(V)), dim3(ST), 0, c->stream, mesh->tri, solid->vstart, solid->vcount,
-                           solid->corner, V, (double *)a.table);
+                           solid->corner, V, (double *)a.sign.table);
     hipLaunchKernelGGL(finish_kernel, dim3(blocks_for(N)), dim3(ST), 0, c->stream, a);
     PEDP_HIP_CHECK(hipGetLastError());
     if (mem == PEDP_HOST) {

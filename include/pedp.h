@@ -1177,6 +1177,91 @@ int pedp_solid_get_info(pedp_solid_t solid, pedp_solid_info *out);
 int pedp_signed_distance(pedp_ctx_t ctx, pedp_mesh_t mesh, pedp_solid_t solid, const double *pts, int64_t N, int mem,
                          double *sdist, int8_t *occupancy, uint8_t *feature, double *normal);
 
+/* ---------------------------------------------------------------- the deviation map: per-face statistics of signed deviation
+ * How far off is the part on this face, measured over everything the camera saw, and how certain is that?  The defect
+ * map keeps a PEAK per face, which a noisy measurement biases upwards with every frame; the deviation map keeps the
+ * count, sum, sum of squares, extremes and frames of the SIGNED distance per face, so that noise shrinks with sqrt(n),
+ * the sign and the millimetres are kept, and a region has a volume of excess or missing material.  The reference has no
+ * counterpart; the contract is DESIGN.md s4.23.
+ *
+ * pedp_deviation_map_create lays the state over the faces of a defect map and borrows its areas, adjacency and region
+ * scratch, as pedp_coverage_create does; the map must outlive the handle.  It allocates device memory (PEDP_ERR_BAD_ARG
+ * while a registration is pending on the context).
+ *
+ * pedp_deviation_map_add is one OBSERVATION: one frame's rows (prim_id, d), d the signed distance in the mesh's unit,
+ * negative inside the solid.  A row is TAKEN iff prim_id < F, d is not NaN and |d| <= gate; gate is per call,
+ * 0 <= gate <= 1024, anything else (NaN included) is PEDP_ERR_BAD_ARG.  Rows with a bad id or a NaN d are IGNORED,
+ * the other rows with |d| > gate (+-inf included) are GATED; both are counted.  n = 0 still counts as an observation.
+ * A taken row is quantised, q = rint(d 2^20) as int64, round half to even (the product is exact in float64, |q| <= 2^30),
+ * and the face's state takes it with integer atomics alone:
+ *   n += 1 (int64)   S1 += q (int64)   S2 += q q, exact in 128 bits, kept as two uint64 sums of (q q & 0xFFFFFFFF) and
+ *   (q q >> 32)   qmin = min(qmin, q)   qmax = max(qmax, q)   frames += 1 ONCE per observation (the defect map's stamp)
+ * Runs of equal ids in neighbouring rows are combined inside a wave before the atomics (integer sums are exact and
+ * associative: no bit changes).  The state after any sequence of calls is a function of the multiset of taken rows of
+ * each observation alone: not of the rows' order, of how they sit in memory, of host or device memory, or of the
+ * handle's history before the last pedp_deviation_map_clear.  PEDP_DEVICE only enqueues and is allowed while a
+ * registration is pending; PEDP_HOST is PEDP_ERR_BAD_ARG then.
+ *
+ * pedp_deviation_map_add_points is one observation made from a frame's points with ONE search: pedp_closest_launch on
+ * pts (N x 3 float64, the mesh's frame), the solid's vertex pseudonormals, and one kernel that signs the distance of
+ * every point exactly as pedp_signed_distance does (one routine) and feeds the row (prim_id, sdist) to the accumulation
+ * above; no N-sized result is written.  The checks are pedp_signed_distance's, and the mesh's F must be the map's.
+ * origin (nullable, 3 doubles in HOST memory whatever `mem` is): the camera centre in the mesh's frame; a row with a
+ * closest feature of pseudonormal N is then taken only if ((origin - c) . N) orientation > 0 -- a depth point cannot
+ * have been measured on a surface that faces away -- and is otherwise counted as BACKFACING, before the gate.  The
+ * workspace is the handle's own, sized by V and N: PEDP_ERR_BAD_ARG while a registration is pending, in either memory.
+ *
+ * pedp_deviation_map_faces: F values each, every pointer nullable, host or device memory by `mem`:
+ *   n, frames, s1 = S1, s2_hi / s2_lo = S2 as (hi64, lo64)
+ *   min = qmin 2^-20, max = qmax 2^-20 (exact);  mean = ((double)S1 / (double)n) 2^-20
+ *   std = sqrt(var), var = (D(n S2 - S1 S1) / ((double)n (double)n)) 2^-40 with the integer formed exactly in 128 bits
+ *   and D the double nearest to it, ties to even; valid for n < 2^33, above that std is NaN
+ * A face with n = 0 reads n 0, frames 0 and NaN for mean, std, min and max.
+ * pedp_deviation_map_stats: observations, rows taken, ignored, gated and backfacing since the last clear (waits on the
+ * stream unless only observations is asked for).
+ *
+ * Criteria (NULL: threshold 0, z 0, min_samples 1, min_frames 1, sign 0).  A face is MARKED iff n >= min_samples and
+ * frames >= min_frames and the sign test holds -- sign 0: |mean| > threshold; +1: mean > threshold (excess material);
+ * -1: mean < -threshold (missing material); another sign is PEDP_ERR_BAD_ARG -- and, when z > 0, also
+ * |mean| sqrt((double)n) > z std: significance against the face's own spread.  A face with n = 0 is never marked.
+ * pedp_deviation_map_regions: growth, components, numbering, labels and the capacity rule are pedp_defect_map_regions'
+ * (one body), with hits = n, frames, and peak = the largest |mean| over the faces with n > 0.  A row is a
+ * pedp_defect_region followed by measured_area (sum of area over the region's faces with n > 0), volume (sum of
+ * area mean over the same faces: unit^3, signed), mean = volume / measured_area, min_mean and max_mean (NaN when no face
+ * of the region has n > 0).  The two sums are formed in the order in which the body sums `area`.
+ * pedp_deviation_map_summary: over the MEASURED faces (n > 0 and n >= min_samples) their number and area, the
+ * area-weighted mean (sum area mean / measured_area) and RMS (sqrt(sum area mean^2 / measured_area)) of the face means,
+ * the largest |mean| and the lowest face that has it (-1: none); the marked faces and their area; the model's area.  The
+ * sums take their terms in pedp_coverage_summary's order: the same bits on every call.  Both calls wait on the stream
+ * (PEDP_ERR_BAD_ARG while a registration is pending). */
+typedef struct pedp_deviation_map_s *pedp_deviation_map_t;
+typedef struct pedp_deviation_criteria {
+    double threshold, z;
+    int64_t min_samples;
+    int32_t min_frames, sign;
+} pedp_deviation_criteria;
+typedef struct pedp_deviation_region {
+    pedp_defect_region region;
+    double measured_area, volume, mean, min_mean, max_mean;
+} pedp_deviation_region;
+typedef struct pedp_deviation_totals {
+    int64_t faces, measured_faces, marked_faces, max_face;
+    double total_area, measured_area, marked_area, mean, rms, max_abs_mean;
+} pedp_deviation_totals;
+int pedp_deviation_map_create(pedp_defect_map_t map, pedp_deviation_map_t *out);
+int pedp_deviation_map_destroy(pedp_deviation_map_t dev);
+int pedp_deviation_map_clear(pedp_deviation_map_t dev);
+int pedp_deviation_map_add(pedp_deviation_map_t dev, const uint32_t *prim_id, const double *d, int64_t n, double gate, int mem);
+int pedp_deviation_map_add_points(pedp_deviation_map_t dev, pedp_mesh_t mesh, pedp_solid_t solid, const double *pts, int64_t N, int mem,
+                                  double gate, const double *origin);
+int pedp_deviation_map_faces(pedp_deviation_map_t dev, int mem, int64_t *n, int32_t *frames, int64_t *s1, uint64_t *s2_hi, uint64_t *s2_lo,
+                             double *min, double *max, double *mean, double *std);
+int pedp_deviation_map_stats(pedp_deviation_map_t dev, int64_t *observations, int64_t *rows_taken, int64_t *rows_ignored,
+                             int64_t *rows_gated, int64_t *rows_backfacing);
+int pedp_deviation_map_summary(pedp_deviation_map_t dev, const pedp_deviation_criteria *c, pedp_deviation_totals *out);
+int pedp_deviation_map_regions(pedp_deviation_map_t dev, const pedp_deviation_criteria *c, int32_t grow, int mem, int32_t *labels,
+                               int64_t capacity, pedp_deviation_region *table, int64_t *n_regions);
+
 /* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
  * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
  * The contract is DESIGN.md s4.11.  With pos = mask > 0, truthy = mask.astype(bool) (for a float32 mask they differ on
