@@ -22,6 +22,7 @@
 //     oracle's order.
 // Neighbourhood queries (DBSCAN) walk a uniform grid with cell >= eps built by a sort on the cell id.
 #include "pedp_internal.h"
+#include "features/acos_cr.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -924,6 +925,16 @@ __global__ __launch_bounds__(HYB_WPB * 64) void hybrid_list_wave_kernel(Grid g, 
     if (lane == 0) nbr_n[i] = have;
 }
 
+// Feature.cpp's ordering test acos(x1) > acos(x2).  Two arguments a few ulp apart (two points with one neighbourhood,
+// hence one normal; a lattice) ask whether adjacent doubles round to the same angle: the fast acos (1-2 ulp) cannot say,
+// so within 16 ulp of a tie the correctly rounded one decides (features/acos_cr.h), as the host's libm does.  Equal
+// arguments never swap, an argument above 1 (NaN angle) never does.
+__device__ __forceinline__ bool pair_order_swaps(double x1, double x2) {
+    const double c1 = acos(x1), c2 = acos(x2);
+    if (x1 != x2 && fabs(c1 - c2) <= 16.0 * 2.220446049250313e-16 * fmax(c1, c2)) return acos_cr(x1) > acos_cr(x2);
+    return c1 > c2;
+}
+
 // Feature.cpp ComputePairFeatures, operation for operation (oracle/features.c pair_features)
 __device__ __forceinline__ void pair_features_dev(const double *p1, const double *n1, const double *p2, const double *n2,
                                                   double r[4]) {
@@ -933,7 +944,7 @@ __device__ __forceinline__ void pair_features_dev(const double *p1, const double
     if (r[3] == 0.0) return;
     double a[3] = {n1[0], n1[1], n1[2]}, b[3] = {n2[0], n2[1], n2[2]};
     const double angle1 = dot3(a, dp) / r[3], angle2 = dot3(b, dp) / r[3];
-    if (acos(fabs(angle1)) > acos(fabs(angle2))) {
+    if (pair_order_swaps(fabs(angle1), fabs(angle2))) {
         for (int k = 0; k < 3; ++k) { a[k] = n2[k]; b[k] = n1[k]; dp[k] = -dp[k]; }
         r[2] = -angle2;
     } else {
@@ -1104,6 +1115,9 @@ __host__ __device__ inline double plane_dist(const double pl[4], const double *p
 // so the cloud is read once per RS_PLANES iterations (a workgroup per iteration streaming the whole cloud
 // moved 228 MB through L2 for 9.5 k points x 1000 iterations: 166 us).  Integer adds: any order, same counts.
 constexpr int RS_PLANES = 64;
+// ransac_count_kernel takes a slab of RS_PLANES iterations per blockIdx.y, and a launch holds 65535 blocks in y
+// (hipDeviceProp_t::maxGridSize[1] is 65536 on gfx950): the most iterations one call accepts
+constexpr int RS_MAX_ITERATIONS = RS_PLANES * 65535;  // 4,194,240
 __global__ void ransac_plane_kernel(const double *__restrict__ pts, long long N, unsigned long long seed, int n_iter,
                                     double *__restrict__ planes, int *__restrict__ counts) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1426,19 +1440,24 @@ int check_cloud(pedp_ctx_t c, const double *pts, int64_t N, const char *who) {
 }
 
 // Bounding box of device-resident points: per-workgroup partial minima / maxima (the host loop's
-// comparisons, so NaN coordinates are passed over the same way), folded on the host from the pinned block.
-// One small read-back instead of a host pass over the caller's array (0.5 ms for 365 k points).
+// comparisons), folded on the host from the pinned block.  One small read-back instead of a host pass over
+// the caller's array (0.5 ms for 365 k points).  The comparisons pass over a NaN, so the same sweep keeps a
+// flag: a workgroup that met a NaN or infinite coordinate writes NaN as its first partial (poisoned), and the
+// fold hands the caller a NaN box -- every consumer refuses that (make_grid, voxel_core).
 constexpr int BND_BLOCKS = 256;
 __global__ __launch_bounds__(256) void bounds_kernel(const double *__restrict__ pts, int64_t N, double *__restrict__ part) {
     const double inf = __longlong_as_double(0x7FF0000000000000ll);
     double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+    int bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const double v = pts[3 * i + k];
             if (v < lo[k]) lo[k] = v;
             if (v > hi[k]) hi[k] = v;
+            bad |= !(fabs(v) < inf);  // NaN or +-inf
         }
+    bad = __syncthreads_or(bad);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1)
 #pragma unroll
@@ -1457,7 +1476,7 @@ __global__ __launch_bounds__(256) void bounds_kernel(const double *__restrict__ 
             const double o = red[w][threadIdx.x];
             if (threadIdx.x < 3 ? o < v : o > v) v = o;
         }
-        part[6 * blockIdx.x + threadIdx.x] = v;
+        part[6 * blockIdx.x + threadIdx.x] = (bad && threadIdx.x == 0) ? __longlong_as_double(0x7FF8000000000000ll) : v;
     }
 }
 
@@ -1467,23 +1486,31 @@ int bounds_device(pedp_ctx_t c, const double *d_pts, int64_t N, double *d_part /
     double *h = (double *)((char *)c->pinned + 16384);
     PEDP_HIP_CHECK(hipMemcpyAsync(h, d_part, sizeof(double) * 6 * BND_BLOCKS, hipMemcpyDeviceToHost, c->stream));
     PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    bool bad = h[0] != h[0];
     for (int k = 0; k < 3; ++k) { lo[k] = h[k]; hi[k] = h[3 + k]; }
-    for (int b = 1; b < BND_BLOCKS; ++b)
+    for (int b = 1; b < BND_BLOCKS; ++b) {
+        bad |= h[6 * b] != h[6 * b];  // a poisoned partial
         for (int k = 0; k < 3; ++k) {
             if (h[6 * b + k] < lo[k]) lo[k] = h[6 * b + k];
             if (h[6 * b + 3 + k] > hi[k]) hi[k] = h[6 * b + 3 + k];
         }
+    }
+    if (bad) lo[0] = std::nan("");
     return PEDP_OK;
 }
 
-void bounds(const double *pts, int64_t N, double lo[3], double hi[3]) {
-    for (int k = 0; k < 3; ++k) lo[k] = hi[k] = pts[k];
+// the host pass: the box, and whether every coordinate is finite (the comparisons alone pass over a NaN)
+bool bounds(const double *pts, int64_t N, double lo[3], double hi[3]) {
+    bool bad = false;
+    for (int k = 0; k < 3; ++k) { lo[k] = hi[k] = pts[k]; bad |= !std::isfinite(pts[k]); }
     for (int64_t i = 1; i < N; ++i)
         for (int k = 0; k < 3; ++k) {
             const double v = pts[3 * i + k];
             if (v < lo[k]) lo[k] = v;
             if (v > hi[k]) hi[k] = v;
+            bad |= !std::isfinite(v);
         }
+    return !bad;
 }
 
 // Large clouds: the points go up first (into their own scratch, so the workspace can still be sized by the grid)
@@ -1491,7 +1518,10 @@ void bounds(const double *pts, int64_t N, double lo[3], double hi[3]) {
 constexpr int64_t BND_DEVICE_MIN = 32768;
 int bounds_of(pedp_ctx_t c, const double *pts, int64_t N, double lo[3], double hi[3], double **d_in) {
     *d_in = nullptr;
-    if (N < BND_DEVICE_MIN) { bounds(pts, N, lo, hi); return PEDP_OK; }
+    if (N < BND_DEVICE_MIN) {
+        if (!bounds(pts, N, lo, hi)) lo[0] = std::nan("");  // (make_grid refuses, like the device pass's poisoned box)
+        return PEDP_OK;
+    }
     PEDP_HIP_CHECK(hipSetDevice(c->device));
     int st = c->ops_in.reserve(a256(sizeof(double) * 3 * (size_t)N) + a256(sizeof(double) * 6 * BND_BLOCKS));
     if (st) return st;
@@ -1549,16 +1579,18 @@ int small_block(pedp_ctx_t c, double **d_part) {
 }
 
 int voxel_core(pedp_ctx_t c, const double *d_pts, const double *d_nrm, int64_t N, double voxel_size, double **out_pts,
-               double **out_nrm, int64_t *n_out, double *box_lo = nullptr, double *box_hi = nullptr) {
+               double **out_nrm, int64_t *n_out, double *box_lo = nullptr, double *box_hi = nullptr,
+               const char *who = "pedp_voxel_down_sample") {
     double lo[3], hi[3], *d_part = nullptr;
     int rc = small_block(c, &d_part);
     if (rc) return rc;
     rc = bounds_device(c, d_pts, N, d_part, lo, hi);
     if (rc) return rc;
     for (int k = 0; k < 3 && box_lo && box_hi; ++k) { box_lo[k] = lo[k]; box_hi[k] = hi[k]; }  // the averages lie inside it
+    for (int k = 0; k < 3; ++k)  // before any key is formed (bounds_device hands a NaN box for a NaN / infinite row)
+        PEDP_REQUIRE(std::isfinite(lo[k]) && std::isfinite(hi[k]), "%s: non-finite coordinates", who);
     int bits[3];
     for (int k = 0; k < 3; ++k) {
-        PEDP_REQUIRE(std::isfinite(lo[k]) && std::isfinite(hi[k]), "pedp_voxel_down_sample: non-finite coordinates");
         lo[k] = lo[k] - voxel_size * 0.5;
         PEDP_REQUIRE((hi[k] - lo[k]) / voxel_size < 2097151.0, "pedp_voxel_down_sample: voxel_size is too small");
         // the largest cell index of the axis, one to spare for the division's rounding
@@ -2057,7 +2089,7 @@ int pedp_cluster_dbscan(pedp_ctx_t c, const double *pts, int64_t N, double eps, 
     if (N == 0) return PEDP_OK;
     PEDP_REQUIRE(labels, "pedp_cluster_dbscan: null labels");
     double lo[3], hi[3];
-    bounds(pts, N, lo, hi);
+    PEDP_REQUIRE(bounds(pts, N, lo, hi), "pedp_cluster_dbscan: non-finite coordinates");
     PEDP_HIP_CHECK(hipSetDevice(c->device));
     double *d_pts = nullptr;
     rc = upload_in(c, pts, nullptr, N, &d_pts, nullptr);
@@ -2077,7 +2109,7 @@ int pedp_knn_mean_distance(pedp_ctx_t c, const double *pts, int64_t N, int k, do
     if (N == 0) return PEDP_OK;
     PEDP_REQUIRE(avg, "pedp_knn_mean_distance: null output");
     double lo[3], hi[3];
-    bounds(pts, N, lo, hi);
+    PEDP_REQUIRE(bounds(pts, N, lo, hi), "pedp_knn_mean_distance: non-finite coordinates");  // (N <= KNN_SMALL_MAX takes no grid)
     PEDP_HIP_CHECK(hipSetDevice(c->device));
     double *d_pts = nullptr;
     rc = upload_in(c, pts, nullptr, N, &d_pts, nullptr);
@@ -2099,13 +2131,12 @@ int pedp_estimate_normals(pedp_ctx_t c, const double *pts, int64_t N, double rad
     if (N == 0) return PEDP_OK;
     PEDP_REQUIRE(normals, "pedp_estimate_normals: null output");
     PEDP_HIP_CHECK(hipSetDevice(c->device));
+    double lo[3], hi[3];
+    if (N < BND_DEVICE_MIN) PEDP_REQUIRE(bounds(pts, N, lo, hi), "pedp_estimate_normals: non-finite coordinates");
     double *d_pts = nullptr, *d_prior = nullptr;
     rc = upload_in(c, pts, prior, N, &d_pts, &d_prior);
     if (rc) return rc;
-    double lo[3], hi[3];
-    if (N < BND_DEVICE_MIN) {
-        bounds(pts, N, lo, hi);
-    } else {  // the box of a large cloud from its device copy: no host pass over the caller's array
+    if (N >= BND_DEVICE_MIN) {  // the box of a large cloud from its device copy: no host pass over the caller's array
         double *d_part = nullptr;
         rc = small_block(c, &d_part);
         if (rc) return rc;
@@ -2225,9 +2256,14 @@ int pedp_segment_plane(pedp_ctx_t c, const double *pts, int64_t N, double distan
     int rc = check_cloud(c, pts, N, "pedp_segment_plane");
     if (rc) return rc;
     PEDP_REQUIRE(plane && n_inliers, "pedp_segment_plane: null outputs");
-    PEDP_REQUIRE(num_iterations >= 0 && num_iterations <= 10000000, "pedp_segment_plane: num_iterations out of range");
+    PEDP_REQUIRE(num_iterations >= 0 && num_iterations <= RS_MAX_ITERATIONS, "pedp_segment_plane: num_iterations out of range (0..%d)",
+                 RS_MAX_ITERATIONS);
     plane[0] = plane[1] = plane[2] = plane[3] = 0.0;
     *n_inliers = 0;
+    if (N > 0) {  // no box is taken here: the same host pass, for its flag alone
+        double lo[3], hi[3];
+        PEDP_REQUIRE(bounds(pts, N, lo, hi), "pedp_segment_plane: non-finite coordinates");
+    }
     if (N < 3 || num_iterations == 0) return PEDP_OK;
     PEDP_REQUIRE(inliers, "pedp_segment_plane: null inlier array");
     PEDP_HIP_CHECK(hipSetDevice(c->device));
@@ -2268,7 +2304,8 @@ int pedp_preprocess_source_ex(pedp_ctx_t c, const double *pts, int64_t N, int pt
     if (rc) return rc;
     PEDP_REQUIRE(prm && n_out && status && out_pts, "pedp_preprocess_source: null argument");
     PEDP_REQUIRE(prm->voxel_size > 0.0, "pedp_preprocess_source: voxel_size <= 0");
-    PEDP_REQUIRE(prm->plane_iterations >= 1 && prm->plane_iterations <= 10000000, "pedp_preprocess_source: plane_iterations out of range");
+    PEDP_REQUIRE(prm->plane_iterations >= 1 && prm->plane_iterations <= RS_MAX_ITERATIONS,
+                 "pedp_preprocess_source: plane_iterations out of range (1..%d)", RS_MAX_ITERATIONS);
     PEDP_REQUIRE(prm->cluster_eps > 0.0 && std::isfinite(prm->cluster_eps), "pedp_preprocess_source: cluster_eps must be positive");
     PEDP_REQUIRE(prm->outlier_neighbors >= 1 && prm->outlier_neighbors <= 300, "pedp_preprocess_source: outlier_neighbors must be in 1..300");
     PEDP_REQUIRE(!prm->first_frame || (prm->normal_radius > 0.0 && prm->normal_max_nn >= 1 && prm->normal_max_nn <= 128 && out_normals),
@@ -2290,7 +2327,7 @@ int pedp_preprocess_source_ex(pedp_ctx_t c, const double *pts, int64_t N, int pt
     double *v_pts = nullptr, *v_nrm = nullptr, *d_part = nullptr;
     int64_t m1 = 0;
     double box_lo[3], box_hi[3];  // of the input cloud: every later stage's points lie inside, so it can shape their grids
-    rc = voxel_core(c, d_in, nullptr, N, prm->voxel_size, &v_pts, &v_nrm, &m1, box_lo, box_hi);
+    rc = voxel_core(c, d_in, nullptr, N, prm->voxel_size, &v_pts, &v_nrm, &m1, box_lo, box_hi, "pedp_preprocess_source");
     if (rc) return rc;
     if (stage_counts) stage_counts[0] = m1;
     if (m1 < 3) { *status = PEDP_PREPROCESS_DEGENERATE; return PEDP_OK; }

@@ -245,6 +245,17 @@ int pedp_depth_to_scene(pedp_ctx_t ctx, const float *depth, int H, int W, int de
  * calls return after completion.  Where Open3D's result depends on something that cannot be
  * recovered (hash-map order, random_device seed, thread interleaving) the rule used is stated.
  *
+ *   non-finite   a cloud with a NaN or infinite coordinate, in any row, is refused by every operation of this
+ *                section that takes points -- pedp_voxel_down_sample[_device_in], pedp_cluster_dbscan,
+ *                pedp_knn_mean_distance, pedp_estimate_normals, pedp_fpfh, pedp_segment_plane and
+ *                pedp_preprocess_source[_ex], host or device array alike: PEDP_ERR_BAD_ARG, "<entry point>:
+ *                non-finite coordinates", outputs untouched except counters set to 0, the context stays usable.
+ *                (Open3D's result on such input is undefined -- integer casts of NaN -- and the depth entry never
+ *                produces such rows.)  The test rides on the bounding-box pass every operation starts with and
+ *                comes before any kernel that turns a coordinate into an index.  Normals, `prior` and feature rows
+ *                are NOT checked: a non-finite normal or prior gives non-finite values in the rows that read it;
+ *                for feature rows see pedp_feature_match.
+ *
  * voxel_down_sample (:204-205): voxel index floor((p - (min_bound - voxel/2)) / voxel) per axis;
  * a voxel's points (and normals, nullable) are summed in point order and divided by the count.
  * Output order: ascending (ix, iy, iz) (Open3D: unordered_map order).  capacity = N always fits. */
@@ -260,7 +271,9 @@ int pedp_voxel_down_sample_device_in(pedp_ctx_t ctx, const double *d_pts, int64_
 /* cluster_dbscan (:284): neighbours are points with d^2 < eps^2 (itself included), core points
  * have >= min_points neighbours; labels as Open3D's breadth-first sweep assigns them: clusters
  * numbered by their smallest core index, a border point takes the smallest id among its core
- * neighbours, noise is -1. */
+ * neighbours, noise is -1.  The labels are a function of (pts, eps, min_points) alone: which grid the
+ * library picks for the search (cells below eps / sqrt(3), or cells of eps doubled until they fit the
+ * budget, over the cloud's own box or a larger one) does not change them. */
 int pedp_cluster_dbscan(pedp_ctx_t ctx, const double *pts, int64_t N, double eps, int min_points, int32_t *labels);
 /* Per-point part of remove_statistical_outlier (:308-312): mean distance to the k nearest
  * neighbours (the point itself is one of them), summed in ascending order; the global mean /
@@ -277,18 +290,26 @@ int pedp_estimate_normals(pedp_ctx_t ctx, const double *pts, int64_t N, double r
 /* o3d.pipelines.registration.compute_fpfh_feature(cloud, KDTreeSearchParamHybrid(radius, max_nn))
  * (src/pose_estimation.py:132-137, :175-180, :255-260): out = N x 33 float64 (row i = column i of
  * Open3D's Feature.data).  The cloud's normals are required.  Restated from the published
- * open3d==0.18.0 Feature.cpp (parity unpinned); max_nn <= 128. */
+ * open3d==0.18.0 Feature.cpp (parity unpinned); max_nn <= 128.  Feature.cpp orders a pair of points by
+ * acos(|a1|) > acos(|a2|); where the two arguments are a few ulp apart (points with one normal, lattices)
+ * the order is decided with a correctly rounded acos, so it does not depend on a libm's last bit. */
 int pedp_fpfh(pedp_ctx_t ctx, const double *pts, const double *normals, int64_t N, double radius, int max_nn, double *out);
 
 /* The correspondences of registration_ransac_based_on_feature_matching (src/pose_estimation.py:482-501):
  * idx[i] = the target feature nearest to source feature i (squared L2 over the 33 components in
- * float64, ties to the lower index; -1 when there is no target). */
+ * float64, ties to the lower index; -1 when there is no target).  Feature rows are not checked: a
+ * target row whose squared distance to the source row is NaN or +inf (a NaN or infinite component) is
+ * never the nearest, and a source row for which that holds of every target gets -1 -- the
+ * registration's rule for non-finite rows. */
 int pedp_feature_match(pedp_ctx_t ctx, const double *fs, int64_t Ns, const double *ft, int64_t Nt, int32_t *idx);
 /* segment_plane with ransac_n = 3 (:323-329).  Iteration t samples three distinct indices from a
  * counter-based generator of (seed, t); plane through them; inliers |n.p + d| < threshold; the best
  * iteration has the most inliers (earliest on ties); all iterations are evaluated (Open3D:
- * random_device samples, probabilistic early stop).  Returns, like Open3D, the inliers of the best
- * sampled plane (ascending) and the plane refitted to them (GetPlaneFromPoints). */
+ * random_device samples, probabilistic early stop); num_iterations <= 4,194,240 (65535 slabs of 64
+ * iterations: one launch's blocks in y), likewise pedp_preprocess_source's plane_iterations.
+ * Returns, like Open3D, the inliers of the best sampled plane (ascending) and the plane refitted to
+ * them (GetPlaneFromPoints).  The refit equals Open3D's up to summation rounding: Open3D keeps running
+ * sums, the library adds blocks of 256 points. */
 int pedp_segment_plane(pedp_ctx_t ctx, const double *pts, int64_t N, double distance_threshold, int num_iterations,
                        uint64_t seed, double plane[4], int32_t *inliers, int64_t *n_inliers);
 

@@ -2,7 +2,10 @@
 oracle/cloudops.c: voxel averages, DBSCAN labels, kept indices of the statistical outlier filter,
 RANSAC inliers -- all bit-exact (float64 sums are taken in the oracle's order); the refitted plane
 within 1e-12.  Through the C ABI (pedp_voxel_down_sample, pedp_cluster_dbscan,
-pedp_knn_mean_distance, pedp_segment_plane)."""
+pedp_knn_mean_distance, pedp_segment_plane).
+
+These cases are one kind of input (a millimetre-scale table-and-blob scene).  Other shapes and scales, the sizes at
+which an operation changes kernels, seeded fuzz and non-finite rows: test_cloudops_matrix_gpu.py."""
 import numpy as np
 import pytest
 

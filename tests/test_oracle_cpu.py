@@ -458,56 +458,7 @@ def test_cloud_ops_golden_and_independent_statements(oracle):
 
 # ---------------------------------------------------------------- FPFH / feature matching (features.c)
 
-def _fpfh_numpy(pts, nrm, radius, max_nn):
-    """Independent restatement of Open3D's ComputeFPFHFeature (vector form, numpy's acos / arctan2)."""
-    n = len(pts)
-    d2 = ((pts[:, None, :] - pts[None, :, :]) ** 2).sum(-1)
-    lists = []
-    for i in range(n):
-        cand = np.flatnonzero(d2[i] < radius * radius)
-        cand = cand[np.lexsort((cand, d2[i, cand]))][:max_nn]
-        lists.append(cand)
-    spfh = np.zeros((n, 33))
-    for i, cand in enumerate(lists):
-        if len(cand) <= 1:
-            continue
-        incr = 100.0 / (len(cand) - 1)
-        for j in cand[1:]:
-            dp = pts[j] - pts[i]
-            dist = np.sqrt(dp @ dp)
-            f = np.zeros(3)
-            if dist != 0.0:
-                a, b = nrm[i], nrm[j]
-                a1, a2 = a @ dp / dist, b @ dp / dist
-                if np.arccos(abs(a1)) > np.arccos(abs(a2)):
-                    a, b, dp, f[2] = nrm[j], nrm[i], -dp, -a2
-                else:
-                    f[2] = a1
-                v = np.cross(dp, a)
-                vn = np.sqrt(v @ v)
-                if vn == 0.0:
-                    f[:] = 0.0
-                else:
-                    v = v / vn
-                    w = np.cross(a, v)
-                    f[1] = v @ b
-                    f[0] = np.arctan2(w @ b, a @ b)
-            for k, x in enumerate((11 * (f[0] + np.pi) / (2 * np.pi), 11 * (f[1] + 1) * 0.5, 11 * (f[2] + 1) * 0.5)):
-                spfh[i, 11 * k + min(max(int(np.floor(x)), 0), 10)] += incr
-    out = np.zeros((n, 33))
-    for i, cand in enumerate(lists):
-        if len(cand) <= 1:
-            continue
-        s = np.zeros(3)
-        for j in cand[1:]:
-            if d2[i, j] == 0.0:
-                continue
-            val = spfh[j] / d2[i, j]
-            out[i] += val
-            s += val.reshape(3, 11).sum(1)
-        s = np.where(s != 0.0, 100.0 / np.where(s != 0.0, s, 1.0), 0.0)
-        out[i] = out[i] * np.repeat(s, 11) + spfh[i]
-    return out
+from _cloudops_ref import fpfh as _fpfh_numpy   # (the restatement lives with the other independent statements)
 
 
 def test_fpfh_against_numpy_restatement_and_invariants(oracle):

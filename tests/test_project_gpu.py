@@ -288,3 +288,5 @@ def test_new_entry_points_reject_bad_arguments(ctx):
     assert lib.pedp_estimate_normals(ctx._h, _lib._ptr(p), 5, 1.0, 500, None, _lib._ptr(p)) == -1 and "max_nn" in err()
     bad = p.copy(); bad[2, 1] = np.inf
     assert lib.pedp_cluster_dbscan(ctx._h, _lib._ptr(bad), 5, 1.0, 3, _lib._ptr(lab)) == -1 and "non-finite" in err()
+    bad = p.copy(); bad[1, 0] = np.nan          # (a NaN is passed over by the box's comparisons: the flag of the same pass)
+    assert lib.pedp_cluster_dbscan(ctx._h, _lib._ptr(bad), 5, 1.0, 3, _lib._ptr(lab)) == -1 and "non-finite" in err()
