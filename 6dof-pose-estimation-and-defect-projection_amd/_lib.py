@@ -954,7 +954,7 @@ ICP_PATH_FIELDS = ("fused", "dev_result", "copy_bracket", "head", "certify", "pl
 
 
 class IcpSwitches(C.Structure):     # pedp_icp_switches
-    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order", "steady_closers")]
+    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order", "steady_closers", "steady_groups")]
 
 
 class IcpPathInputs(C.Structure):   # pedp_icp_path_inputs

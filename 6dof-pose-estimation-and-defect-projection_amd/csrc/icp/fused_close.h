@@ -447,16 +447,20 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 const int part = (tid >> 5) + pp * TPARTS;
                 const int l_lo = part * lper < n_live ? part * lper : n_live, l_hi = l_lo + lper < n_live ? l_lo + lper : n_live;
                 double v = 0.0;
-                if (k < PACKET + 2) {
-                    for (int q = l_lo; q < l_hi; q += 16) {
-                        int at[16];
-                        double x[16];
+                // loads per round: inside a steady launch (1,024 threads, a thread per entry and range) ten, as above -- a
+                // range is 9 chunks at the bench frame's 281 live chunks, and the CU's sixteen waves queue their loads on one
+                // vector memory path: every load past the range's end is waited for by all of them
+                constexpr int BW1 = MODE == 3 ? 10 : 16;
+                if (k < PACKET + (LOCAL ? 3 : 2)) {  // (entry 31: as above)
+                    for (int q = l_lo; q < l_hi; q += BW1) {
+                        int at[BW1];
+                        double x[BW1];
 #pragma unroll
-                        for (int u = 0; u < 16; ++u) at[u] = position(q + u < l_hi ? q + u : l_hi - 1);
+                        for (int u = 0; u < BW1; ++u) at[u] = position(q + u < l_hi ? q + u : l_hi - 1);
 #pragma unroll
-                        for (int u = 0; u < 16; ++u) x[u] = load_partial<COHERENT>(&f.partials[(size_t)at[u] * PSTRIDE + k]);
+                        for (int u = 0; u < BW1; ++u) x[u] = load_partial<COHERENT>(&f.partials[(size_t)at[u] * PSTRIDE + k]);
 #pragma unroll
-                        for (int u = 0; u < 16; ++u) v = q + u < l_hi ? v + x[u] : v;
+                        for (int u = 0; u < BW1; ++u) v = q + u < l_hi ? v + x[u] : v;
                     }
                 }
                 L.slice[part][k] = v;

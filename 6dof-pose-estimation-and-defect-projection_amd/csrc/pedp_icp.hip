@@ -296,7 +296,7 @@ inline const IcpSwitches &icp_switches() {
         s.copy_bracket = flag("PEDP_ICP_COPY_BRACKET", 0); s.head_close = flag("PEDP_ICP_HEAD_CLOSE", 1);
         s.cert = flag("PEDP_ICP_CERT", 1); s.steady = flag("PEDP_ICP_STEADY", 1);
         s.steady_from = num("PEDP_ICP_STEADY_FROM", 5); s.steady_grid = num("PEDP_ICP_STEADY_GRID", 0);
-        s.steady_closers = num("PEDP_ICP_STEADY_CLOSERS", 0);
+        s.steady_closers = num("PEDP_ICP_STEADY_CLOSERS", 0); s.steady_groups = num("PEDP_ICP_STEADY_GROUPS", 0);
         s.target_order = order && !strcmp(order, "hilbert") ? PEDP_TARGET_ORDER_HILBERT
                          : order && !strcmp(order, "compact") ? PEDP_TARGET_ORDER_COMPACT : PEDP_TARGET_ORDER_AUTO;
         return s;
@@ -332,23 +332,36 @@ inline IcpPath icp_decide_path(const IcpSwitches &sw, const IcpPathInputs &in) {
     return p;
 }
 
-// Workgroups of a steady launch: all of them must be resident at once, so the grid is what the runtime says fits --
-// hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs -- and at most two per CU.  PEDP_ICP_STEADY_GRID=n caps it (tests: several
-// chunks per workgroup at a few hundred points).  0: the kernel cannot be resident -- the registration keeps to generic launches.
-inline int steady_grid(pedp_ctx_t c) {
-    static std::atomic<int> per_cu[64];  // by device; 0: not asked yet, -1: asked and refused
+// The shape of a steady launch: wave groups per workgroup (the kernel's GROUPS) and workgroups, all of which must be resident at
+// once -- so the grid is what the runtime says fits, hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs, at most two workgroups
+// per CU with one group (512 threads) and one with two (1,024 threads at 128 registers fill a CU).
+// Two groups where a second workgroup per CU would have a rank: the scene has more chunks than the device has CUs (n_chunks
+// bounds the live chunks from above); smaller scenes keep one group, the kernel they always ran.  PEDP_ICP_STEADY_GROUPS=1|2 forces
+// the choice; PEDP_ICP_STEADY_GRID=n caps the workgroups (tests: several chunks per workgroup at a few hundred points) and implies
+// one group where the other switch is unset.  An instantiation that cannot be resident falls back to one group; grid 0: that one
+// cannot be either -- the registration keeps to generic launches.
+struct SteadyShape { int groups, grid; };
+inline int steady_per_cu(pedp_ctx_t c, int groups) {
+    static std::atomic<int> per_cu[2][64];  // by instantiation and device; 0: not asked yet, -1: asked and refused
     const int dev = c->device >= 0 && c->device < 64 ? c->device : 0;
-    int n = per_cu[dev].load(std::memory_order_relaxed);
+    int n = per_cu[groups - 1][dev].load(std::memory_order_relaxed);
     if (n == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel, BK_W * 64, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = -1; }
-        per_cu[dev].store(n = nb, std::memory_order_relaxed);
+        const hipError_t e = groups == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<2>, 2 * BK_W * 64, 0)
+                                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<1>, BK_W * 64, 0);
+        if (e != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = -1; }
+        per_cu[groups - 1][dev].store(n = nb, std::memory_order_relaxed);
     }
-    if (n < 1) return 0;
-    int64_t g = (int64_t)(n < 2 ? n : 2) * c->num_cus;
-    const int cap = icp_switches().steady_grid;
-    if (cap > 0 && g > cap) g = cap;
-    return (int)g;
+    const int most = groups == 2 ? 1 : 2;
+    return n < 1 ? 0 : (n < most ? n : most);
+}
+inline SteadyShape steady_shape(pedp_ctx_t c, int64_t n_chunks) {
+    const IcpSwitches &sw = icp_switches();
+    int groups = sw.steady_groups == 1 || sw.steady_groups == 2 ? sw.steady_groups : (sw.steady_grid <= 0 && n_chunks > c->num_cus ? 2 : 1);
+    if (groups == 2 && steady_per_cu(c, 2) < 1) groups = 1;
+    int64_t g = (int64_t)steady_per_cu(c, groups) * c->num_cus;
+    if (sw.steady_grid > 0 && g > sw.steady_grid) g = sw.steady_grid;
+    return {groups, (int)g};
 }
 // One steady launch at a time per device and process: two resident grids whose ranks together exceed what the device holds
 // could each wait for workgroups the other keeps out (the bounded wait would turn that into PEDP_ERR_HIP).  A registration
@@ -483,10 +496,16 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpJob &job, const PassLaunch &l) {
     if (pa.head) g += 1;  // head close: one workgroup more than the chunks can fill (the service workgroup)
     if (l.ev0) PEDP_HIP_CHECK(hipEventRecord(l.ev0, c->stream));
     if (l.steady_launch) {
-        // ranks below `closers` close a pass, the others follow one of them: one closer per CU unless the switch says otherwise
+        // workgroups below `closers` close a pass, the others follow one of them: one closer per CU unless the switch says otherwise
         const int asked = icp_switches().steady_closers;
-        hipLaunchKernelGGL(icp_steady_kernel, dim3((unsigned)steady_grid(c)), dim3(BK_W * 64), 0, c->stream, job.w.st, pa,
-                           job.w.follow_cap > 0 ? job.w.follow : nullptr, job.w.follow_cap, asked > 0 ? asked : c->num_cus);
+        const SteadyShape sh = steady_shape(c, job.w.n_chunks);
+        double *const follow = job.w.follow_cap > 0 ? job.w.follow : nullptr;
+        if (sh.groups == 2)
+            hipLaunchKernelGGL(icp_steady_kernel<2>, dim3((unsigned)sh.grid), dim3(2 * BK_W * 64), 0, c->stream, job.w.st, pa, follow,
+                               job.w.follow_cap, asked > 0 ? asked : c->num_cus);
+        else
+            hipLaunchKernelGGL(icp_steady_kernel<1>, dim3((unsigned)sh.grid), dim3(BK_W * 64), 0, c->stream, job.w.st, pa, follow,
+                               job.w.follow_cap, asked > 0 ? asked : c->num_cus);
     }
     else if (job.in.poses > 1)
         hipLaunchKernelGGL((icp_pass_kernel<BK_W, true>), dim3((unsigned)g, (unsigned)job.in.poses), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
@@ -923,7 +942,7 @@ int icp_stage(pedp_ctx_t x, const IcpCall &call, IcpJob &job) {
     in.no_steady = (call.how & ICP_NO_STEADY) != 0;
     in.resident = 1;  // (asked of the runtime only where everything else allows the steady launch)
     job.path = icp_decide_path(icp_switches(), in);
-    if (job.path.steady && steady_grid(x) <= 0) { in.resident = 0; job.path = icp_decide_path(icp_switches(), in); }
+    if (job.path.steady && steady_shape(x, (in.n_source + CH - 1) / CH).grid <= 0) { in.resident = 0; job.path = icp_decide_path(icp_switches(), in); }
     int rc = carve_workspace(x, job.in.n_source, job.in.n_target, job.max_iter, job.in.unit_size, job.w, job.path.fused);
     if (rc) return rc;
     bind_clouds(job.w, call.source, call.target, job.in.unit_size);

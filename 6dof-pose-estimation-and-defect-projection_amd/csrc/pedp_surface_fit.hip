@@ -17,6 +17,10 @@
 #include "pedp_internal.h"
 #include "mesh/record.h"
 #include "closest/move_point.h"
+// (the diagnostic build's stamp buffers and their readers, icp/common.h, are pedp_icp.hip's alone: defined here as well,
+// the library of tools/icp_stamps.py does not link)
+#undef PEDP_ICP_STAMPS
+#define PEDP_ICP_STAMPS 0
 #include "icp/solve.h"
 #include <cmath>
 

@@ -591,7 +591,16 @@ int pedp_icp_last_steady(pedp_ctx_t ctx, int64_t *passes, int64_t *handbacks);
  * themselves but took the closed state from a record one of the closers published (csrc/icp/steady_pass.h).  The ranks below
  * min(ranks, closers) close, the others follow; `closers` is the device's CU count, or PEDP_ICP_STEADY_CLOSERS=n (read once
  * per process; unset or 0: the CU count; n at least the launch's grid: every rank closes, 0 followers; small n: tests).
- * 0 where no steady launch ran.  Results do not change in any bit (tests/test_icp_steady_followers_gpu.py compares). */
+ * 0 where no steady launch ran.  Results do not change in any bit (tests/test_icp_steady_followers_gpu.py compares).
+ *
+ * PEDP_ICP_STEADY_GROUPS=1|2 (read once per process) sets the wave groups of a steady launch's workgroups.  1: a workgroup of
+ * eight waves is a rank, up to two workgroups per CU.  2: a workgroup of sixteen waves holds two ranks, one per wave group of
+ * eight, one workgroup per CU; it closes a pass once, on all its threads, and its second group goes on from the state in the
+ * workgroup's LDS -- closer and follower above are then WORKGROUPS, `closers` counts workgroups, and `followers` reads ranks
+ * minus closing workgroups (a second group closes nothing itself).  PEDP_ICP_STEADY_GRID=n stays n workgroups, so the ranks are
+ * min(live chunks, groups x n).  Unset or 0: two groups where the scene has more chunks of 128 points than the device has CUs
+ * -- only there a CU would hold two ranks -- and PEDP_ICP_STEADY_GRID is unset, else one group.  Results do not change in any
+ * bit (tests/test_icp_steady_groups_gpu.py compares). */
 int pedp_icp_last_steady_followers(pedp_ctx_t ctx, int64_t *followers);
 
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
@@ -614,7 +623,8 @@ typedef struct pedp_icp_switches {  /* the environment switches, read once per p
     int steady_from;  /* default 5 */
     int steady_grid;  /* cap of a steady launch's workgroups (tests); 0: none */
     int target_order; /* PEDP_TARGET_ORDER_*: hilbert | compact decide for every cloud in automatic mode */
-    int steady_closers; /* ranks of a steady launch that close a pass themselves; 0: the device's CU count */
+    int steady_closers; /* workgroups of a steady launch that close a pass themselves; 0: the device's CU count */
+    int steady_groups;  /* wave groups (ranks) per workgroup of a steady launch, 1 or 2; 0: by the scene's size (below) */
 } pedp_icp_switches;
 typedef struct pedp_icp_path_inputs {
     int64_t n_source, n_target; /* source points, finite target rows */
