@@ -237,7 +237,7 @@ int pedp_ctx_create(int device, void *stream, pedp_ctx_t *out) {
         pedp_ctx_destroy(c);
         return PEDP_ERR_HIP;
     }
-    c->pinned_cap = 1 << 17;  // [0, 64 K): the registrations' states and the operations' counters; above: preprocess_source's average normal (64 K) and refit plane (65 K), the jet table (68 K)
+    c->pinned_cap = pedp_pinned::CAP;  // (pedp_internal.h has the block's layout)
     if (hipHostMalloc(&c->pinned, c->pinned_cap, hipHostMallocDefault) != hipSuccess) {
         pedp_set_error("pedp_ctx_create: hipHostMalloc failed");
         pedp_ctx_destroy(c);
@@ -521,7 +521,7 @@ int pedp_cloud_create(pedp_ctx_t c, const double *pts, const double *normals, in
         if (ok && N > 0 && pedp_upload(c, cl->normals, normals, sizeof(double) * 3 * (size_t)N) != PEDP_OK) ok = false;
     }
     if (ok) {  // the box on the device too (the spatial order reads it there)
-        double *hb = (double *)((char *)c->pinned + 12288);
+        double *hb = pedp_pinned_at<double>(c, pedp_pinned::SMALL_UPLOAD);
         for (int k = 0; k < 3; ++k) { hb[k] = cl->lo[k]; hb[3 + k] = cl->hi[k]; }
         ok = hipMemcpyAsync(cl->d_box, hb, sizeof(double) * 6, hipMemcpyHostToDevice, c->stream) == hipSuccess;
     }

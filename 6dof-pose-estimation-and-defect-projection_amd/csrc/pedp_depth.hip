@@ -692,7 +692,7 @@ int pedp_depth_to_scene(pedp_ctx_t c, const float *depth, int H, int W, int dept
     if (rc) return rc;
     rc = pedp_bilateral_filter_depth(c, d_er, H, W, prm->bilateral_radius, prm->bilateral_zfar, prm->sigmaD, prm->sigmaR, PEDP_DEVICE, d_fl);
     if (rc) return rc;
-    float *h_K = (float *)((char *)c->pinned + 12288);
+    float *h_K = pedp_pinned_at<float>(c, pedp_pinned::SMALL_UPLOAD);
     for (int k = 0; k < 9; ++k) h_K[k] = prm->K[k];   // (every earlier user of this pinned block has waited for its copy)
     PEDP_HIP_CHECK(hipMemcpyAsync(d_K, h_K, sizeof(float) * 9, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(xyzmap_batch_kernel, dim3((unsigned)((n + 255) / 256), 1u), dim3(256), 0, c->stream, (const float *)d_fl, (int64_t)n, W,
@@ -702,7 +702,7 @@ int pedp_depth_to_scene(pedp_ctx_t c, const float *depth, int H, int W, int dept
     hipLaunchKernelGGL(scene_scatter_kernel, dim3((unsigned)n_blocks), dim3(SC_THREADS), 0, c->stream, (const float *)d_x, (int64_t)n, prm->z_min,
                        prm->scale, (const int *)boff, d_points);
     PEDP_HIP_CHECK(hipGetLastError());
-    int *h_n = (int *)((char *)c->pinned + 8192);
+    int *h_n = pedp_pinned_at<int>(c, pedp_pinned::COUNTERS);
     PEDP_HIP_CHECK(hipMemcpyAsync(h_n, counter, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->stage_busy = false;

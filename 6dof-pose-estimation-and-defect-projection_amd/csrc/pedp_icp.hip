@@ -449,8 +449,8 @@ struct IcpJob {
     bool want_trace = false;
     PassArgs pa{};  // fused path: what a pass kernel's arguments have in common over the job's launches (stage_pass_args)
 };
-constexpr size_t RESULT_OFF = 2048;
-static_assert(sizeof(IcpState) <= RESULT_OFF && sizeof(IcpState) % 8 == 0, "start and final state share the block's first 4 KB, as 8-byte words");
+constexpr size_t RESULT_OFF = pedp_pinned::ICP_RESULT.off;
+static_assert(sizeof(IcpState) <= pedp_pinned::ICP_STATE.bytes && sizeof(IcpState) <= pedp_pinned::ICP_RESULT.bytes && sizeof(IcpState) % 8 == 0, "start and final state share the block's first 4 KB, as 8-byte words");
 
 // The arguments of the job's pass kernels, from its workspace, clouds and path: filled once, copied per launch.
 void stage_pass_args(pedp_ctx_t x, IcpJob &job) {
@@ -842,7 +842,7 @@ int icp_enqueue(pedp_ctx_t x, const pedp_icp_params *prm, bool early_stop, const
     int rc;
     // Open3D: max_correspondence_distance <= 0 or an empty cloud gives an empty result (never on the fused path)
     const bool degenerate = (r <= 0.0 || Ns == 0 || Nt == 0);
-    IcpState *hp = (IcpState *)x->pinned;
+    IcpState *hp = pedp_pinned_at<IcpState>(x, pedp_pinned::ICP_STATE);
     const double r2 = r * r;
     const double ng = n_global > 0 ? n_global : 1.0;
     const bool fused = path.fused, head = path.head;
@@ -912,7 +912,7 @@ int icp_enqueue(pedp_ctx_t x, const pedp_icp_params *prm, bool early_stop, const
         // early exit enabled, look at the flag every 8th pass (one 4-byte read-back, identical
         // on every rank of a sharded run) and stop enqueuing once it is set.
         if (early_stop && prm->relative_fitness >= 0.0 && (pass & 7) == 7 && pass < max_iter) {
-            int *flag = (int *)((char *)x->pinned + 4096);
+            int *flag = pedp_pinned_at<int>(x, pedp_pinned::ICP_DONE);
             // (head close: whoever ends the registration writes `done` into the slot of the pass behind the one it closed,
             // either parity; the other slot's `done` stays 0 -- both are read)
             flag[1] = 0;
@@ -947,7 +947,7 @@ int icp_stage(pedp_ctx_t x, const IcpCall &call, IcpJob &job) {
     if (rc) return rc;
     bind_clouds(job.w, call.source, call.target, job.in.unit_size);
     if (job.path.fused) stage_pass_args(x, job);
-    icp_fill_state((IcpState *)x->pinned, *call.tp, call.init, prm, call.source->N);
+    icp_fill_state(pedp_pinned_at<IcpState>(x, pedp_pinned::ICP_STATE), *call.tp, call.init, prm, call.source->N);
     icp_arm_result(x);
     return PEDP_OK;
 }
@@ -996,7 +996,7 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
         copies = true;
     }
     if (copies || !job.steady_held) PEDP_HIP_CHECK(hipStreamSynchronize(x->stream));
-    const IcpState *hp = (const IcpState *)((const char *)x->pinned + (job.path.dev_result ? RESULT_OFF : 0));
+    const IcpState *hp = (const IcpState *)((const char *)x->pinned + (job.path.dev_result ? RESULT_OFF : pedp_pinned::ICP_STATE.off));
     if (job.path.dev_result && hp->done == 0) {  // (armed by icp_arm_result; the workgroup that sets `done` writes the state)
         pedp_set_error("pedp_icp: the registration's final state did not arrive");
         return PEDP_ERR_HIP;
@@ -1112,7 +1112,8 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
     int G = 1;  // group size: the power of two that holds the batch, at most BATCH_GROUP_MAX (one cached graph per size)
     int slot = 0;
     while (G < B && G < BATCH_GROUP_MAX) { G <<= 1; ++slot; }
-    static_assert(sizeof(IcpState) * BATCH_GROUP_MAX <= 32768, "two pinned halves hold a group's states");
+    static_assert(sizeof(IcpState) * BATCH_GROUP_MAX <= pedp_pinned::ICP_BATCH_UP.bytes && pedp_pinned::ICP_BATCH_DOWN.bytes == pedp_pinned::ICP_BATCH_UP.bytes,
+                  "two pinned halves hold a group's states");
     IcpJob job;
     job.max_iter = prms[0].max_iteration;
     job.tp = tp; job.estimator = prms[0].estimator;
@@ -1149,7 +1150,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
         }
         c->icp_bgraph_key[slot] = key;
     }
-    IcpState *up = (IcpState *)c->pinned, *down = (IcpState *)((char *)c->pinned + 32768);
+    IcpState *up = pedp_pinned_at<IcpState>(c, pedp_pinned::ICP_BATCH_UP), *down = pedp_pinned_at<IcpState>(c, pedp_pinned::ICP_BATCH_DOWN);
     c->icp_last_cand = c->icp_last_fb = c->icp_last_passes = 0;  // statistics: totals over the batch
     c->icp_last_nt = target->N;
     for (int b0 = 0; b0 < B; b0 += G) {
@@ -1378,7 +1379,7 @@ int pedp_nn(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, const double
     rc = ensure_spatial_perm(c, source);
     if (rc) return rc;
     bind_clouds(w, source, target, 4);
-    IcpState *hp = (IcpState *)c->pinned;
+    IcpState *hp = pedp_pinned_at<IcpState>(c, pedp_pinned::ICP_STATE);
     IcpState h{};
     for (int k = 0; k < 16; ++k) { h.T[k] = T[k]; h.upd[k] = T[k]; }
     for (int k = 0; k < 3; ++k) h.centroid[k] = tp.c[k];

@@ -57,6 +57,13 @@ __host__ __device__ inline bool pedp_row_finite(const double *pts, int64_t i) {
         }                                   \
     } while (0)
 
+// call, return its status if it is not PEDP_OK
+#define PEDP_TRY(expr)           \
+    do {                         \
+        int st_ = (expr);        \
+        if (st_) return st_;     \
+    } while (0)
+
 // A growable device scratch buffer owned by the context (no hipMalloc on the hot path
 // once sizes have settled).
 struct pedp_scratch {
@@ -175,6 +182,44 @@ struct pedp_ctx_s {
     pedp_scratch fit_io;     // surface fit: the points of a host-memory call
     int closest_mode = 0;    // pedp_closest_configure: 0 culled (the kernel by N), 1 exhaustive, 2 / 3 one culled kernel
 };
+
+// The layout of the context's page-locked block (pedp_ctx_s::pinned, PEDP_PINNED_CAP bytes): small results on their way
+// to the host and small inputs on their way up.  A context's calls are serial and every user below waits for its copy
+// before it reads, rewrites or returns -- that is what lets slots be shared -- with two exceptions, which have slots of
+// their own: preprocess_source's average normal and refit plane are collected after a LATER wait of the same call, and a
+// registration begun by pedp_icp_begin keeps ICP_STATE / ICP_RESULT until pedp_icp_end (pedp.h: the context must not be
+// used in between).
+struct pedp_pinned_slot { size_t off, bytes; };
+namespace pedp_pinned {
+constexpr pedp_pinned_slot ICP_STATE{0, 2048};        // pedp_icp.hip: a registration's start state up, its final state down
+constexpr pedp_pinned_slot ICP_RESULT{2048, 2048};    // pedp_icp.hip: the final state the closing workgroup writes itself
+constexpr pedp_pinned_slot ICP_DONE{4096, 4096};      // pedp_icp.hip: the two `done` words the early exit reads every 8th pass
+// Counters read back behind a wait of the same function -- pedp_cloudops.hip: voxel runs, kept points, the best plane's
+// 10 doubles; pedp_depth.hip: scene points; pedp_project.hip: selected rays and hits.  One name on purpose: each reader
+// synchronises the stream and takes its value before anything else of the context can be enqueued.
+constexpr pedp_pinned_slot COUNTERS{8192, 4096};
+// A few words on their way UP -- pedp_ctx.hip: a new cloud's box; pedp_depth.hip: the camera matrix.  Shared: both
+// write the words, enqueue the copy and wait for the stream before they return.
+constexpr pedp_pinned_slot SMALL_UPLOAD{12288, 4096};
+constexpr pedp_pinned_slot BOUNDS{16384, 12288};      // pedp_cloudops.hip: 256 workgroups' partial boxes, folded by the host
+// A batched registration's group (pedp_icp.hip, icp_batch_fused) lays its start states over the whole lower half and
+// reads the final ones from the upper: the slots above are overlaid, none of them is live during a batch.
+constexpr pedp_pinned_slot ICP_BATCH_UP{0, 32768};
+constexpr pedp_pinned_slot ICP_BATCH_DOWN{32768, 32768};
+constexpr pedp_pinned_slot AVERAGE_NORMAL{65536, 1024};  // pedp_cloudops.hip: rows, overflow flag of the voxel means (5 doubles)
+constexpr pedp_pinned_slot REFIT{66560, 3072};           // pedp_cloudops.hip: the refit plane and its inlier count (8 doubles)
+constexpr pedp_pinned_slot JET{69632, 6144};             // pedp_project.hip: the 768-double colour table on its way up
+constexpr size_t CAP = 1 << 17;
+constexpr bool before(pedp_pinned_slot a, pedp_pinned_slot b) { return a.off + a.bytes <= b.off; }
+static_assert(before(ICP_STATE, ICP_RESULT) && before(ICP_RESULT, ICP_DONE) && before(ICP_DONE, COUNTERS) &&
+                  before(COUNTERS, SMALL_UPLOAD) && before(SMALL_UPLOAD, BOUNDS) && before(BOUNDS, ICP_BATCH_DOWN),
+              "the lower half's slots follow each other");
+static_assert(before(ICP_BATCH_UP, ICP_BATCH_DOWN) && before(ICP_BATCH_DOWN, AVERAGE_NORMAL) && before(AVERAGE_NORMAL, REFIT) &&
+                  before(REFIT, JET) && JET.off + JET.bytes <= CAP,
+              "the halves and the slots above them follow each other inside the block");
+}  // namespace pedp_pinned
+template <class T>
+inline T *pedp_pinned_at(pedp_ctx_s *c, pedp_pinned_slot s) { return (T *)((char *)c->pinned + s.off); }
 
 // Triangle record: 12 floats (48 B, 16-B aligned so a wave fetches it with scalar
 // dwordx4/x8 loads): v0.xyz, e1.xyz, e2.xyz, 3 pad.

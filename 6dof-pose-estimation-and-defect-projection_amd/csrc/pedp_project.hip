@@ -277,12 +277,12 @@ int project_impl(pedp_ctx_t c, pedp_mesh_t mesh, const pedp_pinhole *cam, const 
     double *d_lut = (double *)(b + sz_heat + 2 * sz_boff + sz_sel + sz_mm);
     int *counters = (int *)(b + sz_heat + 2 * sz_boff + sz_sel + sz_mm + sz_lut);
     if (jet_lut) {  // 6 KB through the pinned block (behind the counters' words)
-        double *h_lut = (double *)((char *)c->pinned + 69632);
+        double *h_lut = pedp_pinned_at<double>(c, pedp_pinned::JET);
         if (c->stage_busy) PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
         memcpy(h_lut, jet_lut, sizeof(double) * 768);
         PEDP_HIP_CHECK(hipMemcpyAsync(d_lut, h_lut, sizeof(double) * 768, hipMemcpyHostToDevice, c->stream));
     }
-    int *h_counters = (int *)((char *)c->pinned + 8192);
+    int *h_counters = pedp_pinned_at<int>(c, pedp_pinned::COUNTERS);
 
     const Cam cm{cam->fx, cam->fy, cam->cx, cam->cy, cam->width};
     hipLaunchKernelGGL((compact_count_kernel<0, H>), dim3(n_blocks1), dim3(CP_THREADS), 0, c->stream, d_heat, (const float *)nullptr,
