@@ -125,7 +125,9 @@ PROTOTYPES = {
     "pedp_icp_last_certified": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_steady": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]),
     "pedp_icp_last_steady_followers": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
+    "pedp_icp_last_lane_solves": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pedp_debug_solve6": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_debug_icp_path": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
     "pedp_icp_end": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int32), C.c_void_p, C.c_void_p]),
@@ -948,13 +950,21 @@ def icp_last_steady_followers(ctx):
     return a.value
 
 
+def icp_last_lane_solves(ctx):
+    """Closes of the last single icp() whose 6x6 system was solved a row per lane (pedp_icp_last_lane_solves);
+    PEDP_ICP_LANE_SOLVE=0 / PEDP_ICP_SERIAL_CLOSE=1 and point-to-point give 0."""
+    a = C.c_int64(0)
+    check(load().pedp_icp_last_lane_solves(ctx._h, C.byref(a)), "pedp_icp_last_lane_solves")
+    return a.value
+
+
 ICP_SWITCHES = ("nn_f32", "unfused_finish", "no_visit_plan", "serial_close", "copy_bracket", "head_close", "cert", "steady")
 ICP_PATH_FIELDS = ("fused", "dev_result", "copy_bracket", "head", "certify", "plan", "serial_close", "unfused_finish", "exchange",
                    "steady", "steady_from")
 
 
 class IcpSwitches(C.Structure):     # pedp_icp_switches
-    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order", "steady_closers", "steady_groups")]
+    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order", "steady_closers", "steady_groups", "lane_solve")]
 
 
 class IcpPathInputs(C.Structure):   # pedp_icp_path_inputs
@@ -963,21 +973,27 @@ class IcpPathInputs(C.Structure):   # pedp_icp_path_inputs
 
 
 class IcpPath(C.Structure):         # pedp_icp_path
-    _fields_ = [(n, C.c_int) for n in ICP_PATH_FIELDS]
+    _fields_ = [(n, C.c_int) for n in ICP_PATH_FIELDS + ("lane_solve",)]
 
 
-def icp_path(switches=None, steady_from=5, n_source=1, n_target=1, radius=1.0, unit_size=1, poses=1, timed_pass=-1, **flags):
+def icp_path(switches=None, steady_from=5, n_source=1, n_target=1, radius=1.0, unit_size=1, poses=1, timed_pass=-1, lane_solve=None,
+             **flags):
     """Which way a registration would run (pedp_debug_icp_path; no context, no GPU): a dict of the ICP_PATH_FIELDS, bools
     and steady_from.  switches: the names out of ICP_SWITCHES that are in force (head_close, cert and steady are the
-    defaults); None: what this process read from its environment.  flags: the 0/1 fields of pedp_icp_path_inputs."""
+    defaults); None: what this process read from its environment.  flags: the 0/1 fields of pedp_icp_path_inputs.
+    lane_solve: the value of PEDP_ICP_LANE_SOLVE to decide with (it counts where `switches` is given); anything but None
+    also adds the path's lane_solve field to the dict."""
     sw = None
     if switches is not None:
-        sw = IcpSwitches(steady_from=int(steady_from), **{n: 1 for n in switches})
+        sw = IcpSwitches(steady_from=int(steady_from), lane_solve=1 if lane_solve is None else int(lane_solve), **{n: 1 for n in switches})
     q = IcpPathInputs(n_source=int(n_source), n_target=int(n_target), radius=float(radius), unit_size=int(unit_size), poses=int(poses),
                       timed_pass=int(timed_pass), **{n: int(bool(v)) for n, v in flags.items()})
     out = IcpPath()
     check(load().pedp_debug_icp_path(C.byref(sw) if sw is not None else None, C.byref(q), C.byref(out)), "pedp_debug_icp_path")
-    return {n: (getattr(out, n) if n == "steady_from" else bool(getattr(out, n))) for n in ICP_PATH_FIELDS}
+    got = {n: (getattr(out, n) if n == "steady_from" else bool(getattr(out, n))) for n in ICP_PATH_FIELDS}
+    if lane_solve is not None:
+        got["lane_solve"] = bool(out.lane_solve)
+    return got
 
 
 def icp_graph_captures(ctx):
@@ -1076,6 +1092,21 @@ def debug_nn_bf16(ctx, src4, tgt4):
     g = np.empty((len(a), len(b)), np.float32)
     check(load().pedp_debug_nn_bf16(ctx._h, _ptr(a), len(a), _ptr(b), len(b), _ptr(g)), "pedp_debug_nn_bf16")
     return g
+
+
+def debug_solve6(ctx, A, b):
+    """Both device forms of the close's 6x6 solve (pedp_debug_solve6) on n systems A (n, 6, 6), b (n, 6): dict(x_lanes,
+    ok_lanes, x_one, ok_one) -- the row-per-lane form and the one-lane form."""
+    A = np.ascontiguousarray(A, np.float64).reshape(-1, 36)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1, 6)
+    n = len(A)
+    if len(b) != n:
+        raise ValueError("debug_solve6: A and b differ in their count")
+    out = {"x_lanes": np.empty((n, 6), np.float64), "ok_lanes": np.empty(n, np.int32),
+           "x_one": np.empty((n, 6), np.float64), "ok_one": np.empty(n, np.int32)}
+    check(load().pedp_debug_solve6(ctx._h, n, _ptr(A), _ptr(b), _ptr(out["x_lanes"]), _ptr(out["ok_lanes"]), _ptr(out["x_one"]),
+                                   _ptr(out["ok_one"])), "pedp_debug_solve6")
+    return out
 
 
 def icp_begin(ctx, source, target, max_correspondence_distance, init, estimator=POINT_TO_PLANE, max_iteration=30,

@@ -85,6 +85,8 @@ struct IcpState {
     int n_cand;   // slots of the compacted candidate list this pass (128 per scene block)
     int n_blocks; // scene blocks (one per transform wave with at least one candidate)
     int n_segs, seg_len;       // sweep segments of this pass and their length in tiles
+    int n_lane;                // closes of this registration whose 6x6 solve ran a row per lane (solve_lanes.h; statistics, as n_wide;
+                               // the word was padding in front of the 8-byte counters: the state did not grow)
     long long sum_tiles;       // surviving (scene block, target tile) pairs, summed over passes
     long long sum_cand;  // statistics over the passes of this registration
     long long sum_fb;
@@ -114,6 +116,7 @@ struct IcpState {
     double T_init[16];         // the start transformation: slot 0 of the update history (arrives with the state, no copy of its own)
     long long sum_cert, sum_searched;  // candidate slots whose search a certificate replaced / that searched, summed over passes (statistics)
 };
+static_assert(sizeof(IcpState) == 83 * sizeof(double), "the state moves as 83 8-byte words; a new statistic takes a spare word");
 
 // Certificates (fused pass, single registration): a chunk's count of certified and of searching slots shares the
 // free 32nd double of its partial, searching slots scaled by CERT_PACK (exact while a pass has fewer than 2^26 of either)

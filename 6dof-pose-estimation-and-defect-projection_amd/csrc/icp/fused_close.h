@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "solve.h"
+#include "solve_lanes.h"
 
 namespace {
 
@@ -139,8 +140,12 @@ __device__ bool solve6_ldlt_reg(const double *__restrict__ Ain, const double *__
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         x[i] = y[i];
-        if (!(y[i] == y[i]) || isinf(y[i])) ok = false;
+        if (not_finite64(y[i])) ok = false;  // (NaN or infinite)
     }
+    // (a solution that is not finite comes back as zeros: what a NaN's sign and payload are depends on the instructions the
+    // compiler picked, and no caller uses such a solution)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = ok ? x[i] : 0.0;
     return ok;
 }
 
@@ -215,6 +220,8 @@ struct PassArgs {
     // executor's page-locked block: no copy follows the last pass (single registration; null: the host copies)
     unsigned long long *down;
     int serial_close;           // PEDP_ICP_SERIAL_CLOSE=1: the close as it was, everything after the sums on one lane
+    int lane_solve;             // the wide close's 6x6 solve with a row per lane (solve_lanes.h; PEDP_ICP_LANE_SOLVE=0: on lane 0 alone).
+                                // The HOST reads it: it launches the kernels' LANES instantiations, which hold that form alone.
     // Head close (single registration, fused, wide close, final state written by the device; PEDP_ICP_HEAD_CLOSE=0: off).
     // A steady pass ends with its partial sums; the NEXT launch closes it, in every workgroup, before it transforms its
     // chunk.  The state has two slots by pass parity (slot p & 1 holds the state pass p starts from); `launch` is the
@@ -268,6 +275,9 @@ struct FinishArgs {
     // solve the three sincos run on three lanes, the sixteen entries of the new pose on sixteen; 1: all of it on lane 0,
     // one step after the other, as it was.  Every output is computed by the same sequence of float64 operations.
     int serial = 0;
+    // the wide close's point-to-plane solve: 0 -- solve6_ldlt_reg on lane 0; else solve6_ldlt_lanes on wave 0, a row per lane.
+    // The same float64 operations per output either way.
+    int lane = 0;
     // the mask the rebuild pass before this close read "was live" from (today: the copy the closer makes aside when it
     // asks for a rebuild; gen_masks: the other of two masks used in turn, rebuild g ORs into mask g & 1 -- its closer
     // zeroes the other one, nothing is copied aside when a rebuild is asked for)
@@ -530,6 +540,8 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
     if (wide ? tid < 64 : tid == 0) {
         const bool l0 = tid == 0;
         int stop_i = 0, angles_i = 0;  // angles: the update is made from x (point-to-plane, the solve succeeded)
+        int solve_i = 0;               // lane 0 found the pass in need of the point-to-plane solve and left it to the wave
+        const bool lane_form = wide && f.lane != 0;
         double upd[16], x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         ident4(upd);
         if (l0) {
@@ -576,7 +588,9 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 PEDP_STAMP_CLOSE(2, 0);
                 if (pass == 5) PEDP_STAMP_CLOSE(3, 4);
                 if (K > 0.0) {
-                    if (f.estimator == PEDP_POINT_TO_PLANE) {
+                    if (f.estimator == PEDP_POINT_TO_PLANE && lane_form) {
+                        solve_i = 1;  // (wave 0 solves below, a row per lane)
+                    } else if (f.estimator == PEDP_POINT_TO_PLANE) {
                         double A[36], nb[6];
                         int k = 0;
 #pragma unroll
@@ -618,11 +632,32 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
             stop_i = __builtin_amdgcn_readfirstlane(stop_i);
             angles_i = __builtin_amdgcn_readfirstlane(angles_i);
         }
+        if (lane_form) {
+            // "point-to-plane, K > 0, not stopping" is lane 0's finding, made wave-uniform.  The lanes read their entries of
+            // the symmetric matrix out of the packet's upper triangle, and -b.
+            solve_i = __builtin_amdgcn_readfirstlane(solve_i);
+            if (solve_i) {
+                const double *pk = L.pk;
+                const bool ok = solve6_ldlt_lanes(
+                    [pk](int a, int b) {
+                        const int u = a < b ? a : b, v = a < b ? b : a;  // entry (u, v), u <= v, of the packed triangle
+                        return pk[6 * u - u * (u - 1) / 2 + (v - u)];
+                    },
+                    [pk](int u) { return -pk[21 + u]; }, x, tid & 63);
+                if (l0) {
+                    PEDP_STAMP_CLOSE(2, 1);
+                    st->n_lane = st->n_lane + 1;
+                }
+                if (ok) angles_i = 1;
+            }
+        }
         if (!stop_i) {
             if (wide) {
                 if (angles_i) {  // wave-uniform
+                    if (!lane_form) {  // (the lane solve's x is the same in every lane as it comes)
 #pragma unroll
-                    for (int k = 0; k < 6; ++k) x[k] = bcast0(x[k]);
+                        for (int k = 0; k < 6; ++k) x[k] = bcast0(x[k]);
+                    }
                     double s, c;
                     sincos(tid == 0 ? x[0] : (tid == 1 ? x[1] : x[2]), &s, &c);  // one angle per lane
                     const double sa = __shfl(s, 0, 64), ca = __shfl(c, 0, 64), sb = __shfl(s, 1, 64), cb = __shfl(c, 1, 64),
@@ -703,7 +738,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
 __global__ __launch_bounds__(FIN_THREADS) void icp_finish_kernel(IcpState *st, unsigned long long *live, int32_t *live_list,
                                                          int n_lw, const double *partials, double *packet, int phase, int estimator,
                                                          double *__restrict__ trace, double *__restrict__ hist,
-                                                         double bcx, double bcy, double bcz, size_t pose_stride, int serial) {
+                                                         double bcx, double bcy, double bcz, size_t pose_stride, int serial, int lane) {
     {   // pose b = blockIdx.x of a batch: its state and buffers are b * pose_stride bytes behind pose 0's
         const size_t off = (size_t)blockIdx.x * pose_stride;
         st = pose_ptr(st, off); live = pose_ptr(live, off); live_list = pose_ptr(live_list, off);
@@ -714,8 +749,36 @@ __global__ __launch_bounds__(FIN_THREADS) void icp_finish_kernel(IcpState *st, u
     FinishArgs f;
     f.live = live; f.live_list = live_list; f.n_lw = n_lw; f.partials = partials; f.packet = packet; f.phase = phase;
     f.estimator = estimator; f.trace = trace; f.hist = hist; f.bcx = bcx; f.bcy = bcy; f.bcz = bcz;
-    f.serial = serial; f.live_old = live + n_lw;
+    f.serial = serial; f.lane = lane; f.live_old = live + n_lw;
     icp_finish_body<FIN_THREADS, LIVE_CAP, false>(st, f, L, threadIdx.x);
+}
+
+// Both forms of the close's solve on systems of the caller's (pedp_debug_solve6): the row-per-lane form, a wave per
+// system, and the one-lane form, a thread per system.
+__global__ __launch_bounds__(256) void solve6_lanes_debug_kernel(const double *__restrict__ A, const double *__restrict__ b, int64_t n,
+                                                                 double *__restrict__ x_out, int32_t *__restrict__ ok_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= n) return;  // (wave-uniform)
+    double x[6];
+    const double *As = A + 36 * s, *bs = b + 6 * s;
+    const bool ok = solve6_ldlt_lanes([As](int u, int v) { return As[6 * u + v]; }, [bs](int u) { return bs[u]; }, x, lane);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x_out[6 * s + k] = x[k];
+        ok_out[s] = ok ? 1 : 0;
+    }
+}
+// (one thread per system and per WAVE: solve6_ldlt_reg counts on being its wave's only active lane)
+__global__ __launch_bounds__(256) void solve6_one_debug_kernel(const double *__restrict__ A, const double *__restrict__ b, int64_t n,
+                                                               double *__restrict__ x_out, int32_t *__restrict__ ok_out) {
+    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= n || (threadIdx.x & 63) != 0) return;
+    double x[6];
+    const bool ok = solve6_ldlt_reg(A + 36 * s, b + 6 * s, x);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) x_out[6 * s + k] = x[k];
+    ok_out[s] = ok ? 1 : 0;
 }
 
 }  // namespace

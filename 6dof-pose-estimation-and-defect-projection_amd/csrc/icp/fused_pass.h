@@ -98,7 +98,10 @@ __device__ __forceinline__ void sweep_sub_block(const unsigned *__restrict__ lis
 
 // BATCH: the launch carries several poses (grid.y); a separate instantiation, so that a kernel
 // trace tells the single registration's launches from a batch's
-template <int W, bool BATCH>
+// LANES: the close solves its 6x6 system a row per lane (solve_lanes.h) and is the wide close -- the host launches this
+// instantiation only where neither PEDP_ICP_LANE_SOLVE=0 nor PEDP_ICP_SERIAL_CLOSE=1 is set, so the one-lane solve and its
+// 72 registers of matrix are not in the kernel at all; the other instantiation is the kernel as it was.
+template <int W, bool BATCH, bool LANES>
 __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, const PassArgs a0) {
     static_assert(W == 8 && CH == 128, "a chunk is two halves of four 16-slot sub-blocks");
     const size_t pose_off = BATCH ? (size_t)blockIdx.y * a0.pose_stride : 0;
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
         FinishArgs f;
         f.live = nullptr; f.live_list = nullptr; f.n_lw = 0; f.partials = a0.partials + (size_t)((a0.launch - 1) & 1) * a0.part_stride; f.packet = nullptr; f.phase = 0;
         f.estimator = a0.estimator; f.trace = nullptr; f.hist = nullptr; f.bcx = a0.bc[0]; f.bcy = a0.bc[1]; f.bcz = a0.bc[2];
-        f.serial = 0;
+        f.serial = 0; f.lane = LANES ? 1 : 0;
         f.known = 1; f.k_pass = a0.launch - 1; f.k_rebuild = 0; f.k_n_live = cur.n_live;
         icp_finish_body<W * 64, 2048, false, 2>(&cur, f, fin, threadIdx.x);  // (ends behind a barrier: U and the new state are published)
         PEDP_RT(a0.launch, 7);
@@ -958,7 +961,7 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     f.n_idle = (int)gridDim.x - n_wg;
     f.n_busy = n_wg;
     if (!BATCH && !head && planned && threadIdx.x == 0) cur.n_planned += 1;  // (head close: counted where the pass's state was made)
-    f.down = BATCH ? nullptr : a.down; f.serial = a.serial_close;
+    f.down = BATCH ? nullptr : a.down; f.serial = LANES ? 0 : a.serial_close; f.lane = LANES ? 1 : 0;
     f.known = 1; f.k_pass = pass; f.k_rebuild = rebuild ? 1 : 0; f.k_n_live = n_live;
     if constexpr (BATCH) {
         icp_finish_body<W * 64, 2048, true>(st, f, fin, threadIdx.x);

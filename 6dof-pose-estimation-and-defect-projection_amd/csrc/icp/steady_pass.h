@@ -129,7 +129,8 @@ __device__ __forceinline__ bool steady_follow(IcpState *cur, double *word, int *
 // a0.launch: the first pass this launch may run (what a generic launch of that index would run)
 // follow: the closers' records, [2][follow_cap] slots (null: every rank closes); closers: see above (< 1: every rank)
 // GROUPS: wave groups of eight waves per workgroup, each with a rank of its own (1: a workgroup is a rank)
-template <int GROUPS>
+// LANES: the close's 6x6 solve a row per lane, and no one-lane solve in the kernel (as icp_pass_kernel's LANES)
+template <int GROUPS, bool LANES>
 __global__ __launch_bounds__(GROUPS * BK_W * 64, 4) void icp_steady_kernel(IcpState *st0, const PassArgs a0, double *follow, int follow_cap, int closers) {
     constexpr int W = BK_W, GW = GROUPS * W;
     static_assert(W == 8 && CH == 128, "a chunk is two halves of four 16-slot sub-blocks");
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(GROUPS * BK_W * 64, 4) void icp_steady_kernel(IcpSt
                 FinishArgs f;
                 f.live = nullptr; f.live_list = nullptr; f.n_lw = 0; f.partials = a0.partials + (size_t)(q & 1) * a0.part_stride; f.packet = nullptr; f.phase = 0;
                 f.estimator = a0.estimator; f.trace = nullptr; f.hist = nullptr; f.bcx = a0.bc[0]; f.bcy = a0.bc[1]; f.bcz = a0.bc[2];
-                f.serial = 0;
+                f.serial = 0; f.lane = LANES ? 1 : 0;
                 f.known = 1; f.k_pass = q; f.k_rebuild = 0; f.k_n_live = n_live;
                 icp_finish_body<GW * 64, 1, true, 3>(&cur, f, fin, threadIdx.x);  // (ends behind a barrier)
             } else if (!steady_follow(&cur, &fin.pk[PACKET + 2], &misc[0], role_rec[q & 1], (unsigned)(uni(cur.nonce) + q + 1))) {

@@ -50,8 +50,9 @@
 //   icp/segmented_select.h   nn_select_kernel, nn_fallback_kernel, icp_accumulate_kernel, icp_reduce_kernel
 //   icp/solve.h              solve6_ldlt, svd3_dev, icp_solve_kernel
 //   icp/ransac.h             ransac_hypothesis_kernel
+//   icp/solve_lanes.h        solve6_ldlt_lanes: the close's 6x6 solve with a row per lane
 //   icp/fused_close.h        the fused pass's overview and constants, solve6_ldlt_reg, PassArgs, FinishArgs,
-//                            icp_finish_body, icp_finish_kernel
+//                            icp_finish_body, icp_finish_kernel, solve6_lanes_debug_kernel, solve6_one_debug_kernel
 //   icp/fused_pass.h         sweep_sub_block, icp_pass_kernel, batch_state_scatter_kernel, batch_state_gather_kernel,
 //                            icp_state_start_kernel
 //   icp/steady_pass.h        icp_steady_kernel: fully certified passes of a single registration in one resident launch
@@ -297,6 +298,7 @@ inline const IcpSwitches &icp_switches() {
         s.cert = flag("PEDP_ICP_CERT", 1); s.steady = flag("PEDP_ICP_STEADY", 1);
         s.steady_from = num("PEDP_ICP_STEADY_FROM", 5); s.steady_grid = num("PEDP_ICP_STEADY_GRID", 0);
         s.steady_closers = num("PEDP_ICP_STEADY_CLOSERS", 0); s.steady_groups = num("PEDP_ICP_STEADY_GROUPS", 0);
+        s.lane_solve = num("PEDP_ICP_LANE_SOLVE", 1);
         s.target_order = order && !strcmp(order, "hilbert") ? PEDP_TARGET_ORDER_HILBERT
                          : order && !strcmp(order, "compact") ? PEDP_TARGET_ORDER_COMPACT : PEDP_TARGET_ORDER_AUTO;
         return s;
@@ -322,6 +324,7 @@ inline IcpPath icp_decide_path(const IcpSwitches &sw, const IcpPathInputs &in) {
     const bool single = in.poses <= 1;
     const bool closes_itself = !in.exchange && !sw.unfused_finish;  // the workgroup that finishes last closes the pass
     p.serial_close = sw.serial_close; p.unfused_finish = sw.unfused_finish;
+    p.lane_solve = !sw.serial_close && sw.lane_solve > 0;  // (the wide close's solve; the one-lane close keeps its own)
     p.plan = single && !sw.no_visit_plan;  // (a batch fills every CU several times over anyway)
     p.certify = single && closes_itself && sw.cert;
     p.dev_result = single && !in.batch && closes_itself && !sw.copy_bracket;
@@ -347,8 +350,12 @@ inline int steady_per_cu(pedp_ctx_t c, int groups) {
     int n = per_cu[groups - 1][dev].load(std::memory_order_relaxed);
     if (n == 0) {
         int nb = 0;
-        const hipError_t e = groups == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<2>, 2 * BK_W * 64, 0)
-                                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<1>, BK_W * 64, 0);
+        // (a steady launch closes wide: its instantiation follows the process's PEDP_ICP_LANE_SOLVE alone)
+        const bool lanes = icp_switches().lane_solve > 0;
+        const hipError_t e = groups == 2 ? (lanes ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<2, true>, 2 * BK_W * 64, 0)
+                                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<2, false>, 2 * BK_W * 64, 0))
+                                         : (lanes ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<1, true>, BK_W * 64, 0)
+                                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, icp_steady_kernel<1, false>, BK_W * 64, 0));
         if (e != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = -1; }
         per_cu[groups - 1][dev].store(n = nb, std::memory_order_relaxed);
     }
@@ -472,7 +479,7 @@ void stage_pass_args(pedp_ctx_t x, IcpJob &job) {
     pa.fuse = !path.exchange && !path.unfused_finish ? 1 : 0;
     pa.n_lw = w.n_lw; pa.packet = w.packet; pa.trace = job.want_trace ? w.trace : nullptr; pa.ticket = w.ticket;
     pa.down = path.dev_result ? (unsigned long long *)((char *)x->pinned + RESULT_OFF) : nullptr;
-    pa.serial_close = path.serial_close; pa.head = path.head; pa.launch = 0;  // (the launch index is the launch's own)
+    pa.serial_close = path.serial_close; pa.lane_solve = path.lane_solve; pa.head = path.head; pa.launch = 0;  // (the launch index is the launch's own)
     pa.part_stride = (size_t)PSTRIDE * (size_t)w.blocks_cap;
     pa.cert = path.certify ? w.cert : nullptr; pa.cert_stride = (size_t)w.Ns_pad;
     pa.visit = path.plan ? w.visit : nullptr; pa.dur = path.plan ? w.dur : nullptr; pa.visit_cap = w.visit_cap; pa.n_cu = x->num_cus;
@@ -500,17 +507,21 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpJob &job, const PassLaunch &l) {
         const int asked = icp_switches().steady_closers;
         const SteadyShape sh = steady_shape(c, job.w.n_chunks);
         double *const follow = job.w.follow_cap > 0 ? job.w.follow : nullptr;
-        if (sh.groups == 2)
-            hipLaunchKernelGGL(icp_steady_kernel<2>, dim3((unsigned)sh.grid), dim3(2 * BK_W * 64), 0, c->stream, job.w.st, pa, follow,
-                               job.w.follow_cap, asked > 0 ? asked : c->num_cus);
-        else
-            hipLaunchKernelGGL(icp_steady_kernel<1>, dim3((unsigned)sh.grid), dim3(BK_W * 64), 0, c->stream, job.w.st, pa, follow,
-                               job.w.follow_cap, asked > 0 ? asked : c->num_cus);
+        const int n_closers = asked > 0 ? asked : c->num_cus;
+        auto steady = [&](auto kernel, int groups) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)sh.grid), dim3(groups * BK_W * 64), 0, c->stream, job.w.st, pa, follow, job.w.follow_cap, n_closers);
+        };
+        if (sh.groups == 2) { if (pa.lane_solve) steady(icp_steady_kernel<2, true>, 2); else steady(icp_steady_kernel<2, false>, 2); }
+        else { if (pa.lane_solve) steady(icp_steady_kernel<1, true>, 1); else steady(icp_steady_kernel<1, false>, 1); }
+    } else {
+        // the instantiation: a batch's or a single registration's, with the close's solve a row per lane or on one lane
+        const bool batch = job.in.poses > 1;
+        auto pass = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)g, batch ? (unsigned)job.in.poses : 1u), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
+        };
+        if (batch) { if (pa.lane_solve) pass(icp_pass_kernel<BK_W, true, true>); else pass(icp_pass_kernel<BK_W, true, false>); }
+        else { if (pa.lane_solve) pass(icp_pass_kernel<BK_W, false, true>); else pass(icp_pass_kernel<BK_W, false, false>); }
     }
-    else if (job.in.poses > 1)
-        hipLaunchKernelGGL((icp_pass_kernel<BK_W, true>), dim3((unsigned)g, (unsigned)job.in.poses), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
-    else
-        hipLaunchKernelGGL((icp_pass_kernel<BK_W, false>), dim3((unsigned)g), dim3(BK_W * 64), 0, c->stream, job.w.st, pa);
     if (l.ev1) { PEDP_HIP_CHECK(hipEventRecord(l.ev1, c->stream)); c->nn_timed = true; }
     PEDP_HIP_CHECK(hipGetLastError());
     return PEDP_OK;
@@ -523,7 +534,7 @@ void launch_finish(pedp_ctx_t x, const IcpJob &job, int stage) {
     const IcpWorkspace &w = job.w;
     hipLaunchKernelGGL(icp_finish_kernel, dim3((unsigned)job.in.poses), dim3(FIN_THREADS), 0, x->stream, w.st, w.live, w.live_list, w.n_lw,
                        w.cpart, w.packet, stage, job.estimator, job.pa.trace, w.hist, job.tp.bc[0], job.tp.bc[1], job.tp.bc[2],
-                       job.pa.pose_stride, job.pa.serial_close);
+                       job.pa.pose_stride, job.pa.serial_close, job.pa.lane_solve);
 }
 
 // Spatial order of a cloud, cached in the handle: a function of the cloud alone (cells over its own
@@ -1012,6 +1023,7 @@ int icp_collect(pedp_ctx_t x, const IcpJob &job, double T_out[16], double *fitne
     x->icp_last_passes = hp->iters + 1;
     x->icp_last_planned = hp->n_planned;
     x->icp_last_wide = hp->n_wide;
+    x->icp_last_lane = hp->n_lane;
     x->icp_last_head = hp->n_head;
     x->icp_last_cert = hp->sum_cert;
     x->icp_last_searched = hp->sum_searched;
@@ -1151,7 +1163,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
         c->icp_bgraph_key[slot] = key;
     }
     IcpState *up = pedp_pinned_at<IcpState>(c, pedp_pinned::ICP_BATCH_UP), *down = pedp_pinned_at<IcpState>(c, pedp_pinned::ICP_BATCH_DOWN);
-    c->icp_last_cand = c->icp_last_fb = c->icp_last_passes = 0;  // statistics: totals over the batch
+    c->icp_last_cand = c->icp_last_fb = c->icp_last_passes = c->icp_last_lane = 0;  // statistics: totals over the batch
     c->icp_last_nt = target->N;
     for (int b0 = 0; b0 < B; b0 += G) {
         const int n = B - b0 < G ? B - b0 : G;
@@ -1196,6 +1208,7 @@ int icp_batch_fused(pedp_ctx_t c, pedp_cloud_t source, pedp_cloud_t target, cons
             c->icp_last_cand += h.sum_tiles * 256;
             c->icp_last_fb += h.sum_fb;
             c->icp_last_passes += h.iters + 1;
+            c->icp_last_lane += h.n_lane;
         }
     }
     return PEDP_OK;
@@ -1510,6 +1523,35 @@ int pedp_debug_nn_bf16(pedp_ctx_t c, const float *src4, int64_t n_src, const flo
     return PEDP_OK;
 }
 
+int pedp_debug_solve6(pedp_ctx_t c, int64_t n, const double *A, const double *b, double *x_lanes, int32_t *ok_lanes, double *x_one, int32_t *ok_one) {
+    PEDP_REQUIRE(c && A && b && x_lanes && ok_lanes && x_one && ok_one && n > 0 && n <= ((int64_t)1 << 20),
+                 "pedp_debug_solve6: null argument, or a count outside 1 .. 2^20");
+    PEDP_HIP_CHECK(hipSetDevice(c->device));
+    double *d_A = nullptr, *d_b = nullptr, *d_x = nullptr;
+    int32_t *d_ok = nullptr;
+    hipError_t e = hipMalloc((void **)&d_A, sizeof(double) * 36 * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_b, sizeof(double) * 6 * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_x, sizeof(double) * 12 * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_ok, sizeof(int32_t) * 2 * (size_t)n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_A, A, sizeof(double) * 36 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_b, b, sizeof(double) * 6 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        // the lane form: a wave per system, four to a workgroup; the one-lane form: a thread per system, the only one of its wave
+        hipLaunchKernelGGL(solve6_lanes_debug_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const double *)d_A, (const double *)d_b, n, d_x, d_ok);
+        hipLaunchKernelGGL(solve6_one_debug_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const double *)d_A, (const double *)d_b, n,
+                           d_x + 6 * (size_t)n, d_ok + (size_t)n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(x_lanes, d_x, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(x_one, d_x + 6 * (size_t)n, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ok_lanes, d_ok, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ok_one, d_ok + (size_t)n, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_A); (void)hipFree(d_b); (void)hipFree(d_x); (void)hipFree(d_ok);
+    PEDP_HIP_CHECK(e);
+    return PEDP_OK;
+}
+
 int pedp_debug_icp_path(const pedp_icp_switches *switches, const pedp_icp_path_inputs *inputs, pedp_icp_path *path) {
     PEDP_REQUIRE(inputs && path, "pedp_debug_icp_path: null argument");
     *path = icp_decide_path(switches ? *switches : icp_switches(), *inputs);
@@ -1535,6 +1577,12 @@ int pedp_icp_last_serial_path(pedp_ctx_t c, int64_t *wide_closes, int64_t *brack
     PEDP_REQUIRE(c && wide_closes && bracket, "pedp_icp_last_serial_path: null argument");
     *wide_closes = c->icp_last_wide;
     *bracket = c->icp_last_bracket;
+    return PEDP_OK;
+}
+
+int pedp_icp_last_lane_solves(pedp_ctx_t c, int64_t *lane_solves) {
+    PEDP_REQUIRE(c && lane_solves, "pedp_icp_last_lane_solves: null argument");
+    *lane_solves = c->icp_last_lane;
     return PEDP_OK;
 }
 

@@ -159,7 +159,7 @@ struct pedp_ctx_s {
     int render_chunk = 0;    // pedp_render_configure: poses per chunk (0 = by a key budget)
     bool icp_exhaustive = false;  // pedp_icp_configure: no culling (all-pairs sweep every pass)
     int icp_timed_pass = -1;      // pedp_icp_configure: HIP events around the sweep kernel of this pass
-    long long icp_last_cand = 0, icp_last_fb = 0, icp_last_passes = 0, icp_last_nt = 0, icp_last_planned = 0, icp_last_wide = 0, icp_last_bracket = 0, icp_last_head = 0, icp_last_rebuilds = 0, icp_last_launches = 0, icp_last_cert = 0, icp_last_searched = 0, icp_last_steady = 0, icp_last_handbacks = 0, icp_last_followed = 0;
+    long long icp_last_cand = 0, icp_last_fb = 0, icp_last_passes = 0, icp_last_nt = 0, icp_last_planned = 0, icp_last_wide = 0, icp_last_lane = 0, icp_last_bracket = 0, icp_last_head = 0, icp_last_rebuilds = 0, icp_last_launches = 0, icp_last_cert = 0, icp_last_searched = 0, icp_last_steady = 0, icp_last_handbacks = 0, icp_last_followed = 0;
     void *icp_pending = nullptr;   // pedp_icp_begin's job until pedp_icp_end collects it (an IcpJob of pedp_icp.hip)  // last pedp_icp
     pedp_ctx_s *sub[PEDP_MAX_SUB] = {};  // sub-contexts (own stream + workspace) for batched registrations
     hipGraphExec_t icp_graph = nullptr;  // sub-contexts: one whole registration, replayed per start pose

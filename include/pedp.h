@@ -603,6 +603,23 @@ int pedp_icp_last_steady(pedp_ctx_t ctx, int64_t *passes, int64_t *handbacks);
  * bit (tests/test_icp_steady_groups_gpu.py compares). */
 int pedp_icp_last_steady_followers(pedp_ctx_t ctx, int64_t *followers);
 
+/* Closes of the last single registration collected on `ctx` whose 6x6 point-to-plane system was solved with a row per
+ * lane of the closing wave (csrc/icp/solve_lanes.h): the pivot exchanges -- they follow from the six input diagonals
+ * alone -- are played through first, lane i < 6 then holds the row that ends up at position i, b and y of that row, and
+ * a step of the LDLT is at most five multiply-add pairs and one division on all rows at once.  Each output is computed
+ * by the sequence of float64 operations the one-lane solve uses.  A pass counts when it is point-to-plane, has correspondences and does not stop: passes - 1 for
+ * a registration that runs all its passes (a fused batch: the total over its poses); 0 for point-to-point, with PEDP_ICP_LANE_SOLVE=0 (read once per process:
+ * the solve on one lane, as before) and with PEDP_ICP_SERIAL_CLOSE=1.  Results do not change in any bit
+ * (tests/test_icp_lane_solve_gpu.py compares). */
+int pedp_icp_last_lane_solves(pedp_ctx_t ctx, int64_t *lane_solves);
+
+/* Both device forms of the close's 6x6 solve on n systems (tests compare them with each other and with the oracle):
+ * A (float64 x 36 per system, row-major, both triangles) and b (float64 x 6) on the host; x_lanes / ok_lanes from the
+ * row-per-lane form, a wave per system, x_one / ok_one from the one-lane form, a thread per system (float64 x 6 and
+ * one int32 per system each; ok = 0: a NaN or infinite solution, and x = 0). */
+int pedp_debug_solve6(pedp_ctx_t ctx, int64_t n, const double *A, const double *b, double *x_lanes, int32_t *ok_lanes,
+                      double *x_one, int32_t *ok_one);
+
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
  * g[i * n_tgt + j] = |t'_j|^2 - 2 s'_i . t'_j exactly as the sweep's v_mfma_f32_16x16x32_bf16 produces it (same operand packing). */
@@ -625,6 +642,7 @@ typedef struct pedp_icp_switches {  /* the environment switches, read once per p
     int target_order; /* PEDP_TARGET_ORDER_*: hilbert | compact decide for every cloud in automatic mode */
     int steady_closers; /* workgroups of a steady launch that close a pass themselves; 0: the device's CU count */
     int steady_groups;  /* wave groups (ranks) per workgroup of a steady launch, 1 or 2; 0: by the scene's size (below) */
+    int lane_solve;     /* PEDP_ICP_LANE_SOLVE: 0 the close's 6x6 solve on one lane, 1 (default) a row per lane of the closing wave */
 } pedp_icp_switches;
 typedef struct pedp_icp_path_inputs {
     int64_t n_source, n_target; /* source points, finite target rows */
@@ -650,6 +668,7 @@ typedef struct pedp_icp_path {  /* DESIGN 4.2 has the table */
     int exchange;       /* the packet is summed over ranks between the sums and the solve */
     int steady;         /* the passes from steady_from on run in one resident launch, if the device's is free */
     int steady_from;
+    int lane_solve;     /* the wide close solves its 6x6 system a row per lane (never with serial_close) */
 } pedp_icp_path;
 /* switches null: those this process read from its environment. */
 int pedp_debug_icp_path(const pedp_icp_switches *switches, const pedp_icp_path_inputs *inputs, pedp_icp_path *path);
