@@ -127,6 +127,7 @@ PROTOTYPES = {
     "pedp_icp_last_steady_followers": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_icp_last_lane_solves": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "pedp_debug_nn_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pedp_debug_live_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, _P(C.c_int32)]),
     "pedp_debug_solve6": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_debug_icp_path": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_icp_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(IcpParams), C.c_void_p, C.c_int]),
@@ -964,7 +965,7 @@ ICP_PATH_FIELDS = ("fused", "dev_result", "copy_bracket", "head", "certify", "pl
 
 
 class IcpSwitches(C.Structure):     # pedp_icp_switches
-    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order", "steady_closers", "steady_groups", "lane_solve")]
+    _fields_ = [(n, C.c_int) for n in ICP_SWITCHES + ("steady_from", "steady_grid", "target_order", "steady_closers", "steady_groups", "lane_solve", "pass_grid")]
 
 
 class IcpPathInputs(C.Structure):   # pedp_icp_path_inputs
@@ -1107,6 +1108,17 @@ def debug_solve6(ctx, A, b):
     check(load().pedp_debug_solve6(ctx._h, n, _ptr(A), _ptr(b), _ptr(out["x_lanes"]), _ptr(out["ok_lanes"]), _ptr(out["x_one"]),
                                    _ptr(out["ok_one"])), "pedp_debug_solve6")
     return out
+
+
+def debug_live_list(ctx, mask_words, threads=512):
+    """The live list of a rebuild pass's close (pedp_debug_live_list) on the caller's mask words (uint64; bit b of word w:
+    chunk 64 w + b): (n_live, list) with list an int32 array of 64 x words entries -- the set bits' positions, ascending,
+    in its first n_live entries and -1 behind them.  threads: 512 (the close inside a pass launch) or 1024 (the finish kernel)."""
+    words = np.ascontiguousarray(mask_words, np.uint64).reshape(-1)
+    lst = np.full(64 * len(words), -1, np.int32)
+    n = C.c_int32(0)
+    check(load().pedp_debug_live_list(ctx._h, _ptr(words), len(words), int(threads), _ptr(lst), C.byref(n)), "pedp_debug_live_list")
+    return int(n.value), lst
 
 
 def icp_begin(ctx, source, target, max_correspondence_distance, init, estimator=POINT_TO_PLANE, max_iteration=30,

@@ -2,6 +2,7 @@
 // update, live list) as the body the pass kernel runs in-launch and as icp_finish_kernel.
 #pragma once
 #include "common.h"
+#include "live_list.h"
 #include "solve.h"
 #include "solve_lanes.h"
 
@@ -295,13 +296,7 @@ struct FinishLds {
 __device__ __forceinline__ double bcast0(double v) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
-// COHERENT: the partial sums and the live mask were written earlier in THIS launch by other
-// workgroups (sc1 stores / atomics): read them past this CU's L1 -- global_load ... sc1, never a
-// flat_ load (the pointers come out of the LDS-parked argument block, so the address space is
-// stated here).
-typedef __attribute__((address_space(1))) unsigned long long g_u64;
-typedef __attribute__((address_space(1))) int g_i32;
-typedef __attribute__((address_space(1))) unsigned g_u32;
+// (COHERENT loads, the g_u64 / g_i32 / g_u32 pointer types and load_live: live_list.h)
 __device__ __forceinline__ double load_sc1(const double *p) {
     return __longlong_as_double((long long)__hip_atomic_load((g_u64 *)(uintptr_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
@@ -315,11 +310,6 @@ template <bool COHERENT>
 __device__ __forceinline__ double load_partial(const double *p) {
     return COHERENT ? load_sc1(p) : *p;
 }
-template <bool COHERENT>
-__device__ __forceinline__ unsigned long long load_live(unsigned long long *p) {
-    if (COHERENT) return __hip_atomic_fetch_or((g_u64 *)(uintptr_t)p, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
 
 // MODE 0: `st` is the state in memory.  MODE 1: `st` is the workgroup's copy of the state in LDS; the caller writes it
 // out (and the final state to f.down's block) behind the body.  MODE 2: the head close -- as 1, and every workgroup of
@@ -327,6 +317,9 @@ __device__ __forceinline__ unsigned long long load_live(unsigned long long *p) {
 // sign-off poll, no live-mask upkeep.  MODE 3: the head close inside a launch that goes on (steady_pass.h) -- as 2, but the
 // partial sums were stored in THIS launch: they are read coherently, entry by entry.
 // the close's stamps (diagnostic build): of a head close, which every workgroup runs, workgroup 0's only
+#ifndef PEDP_ICP_STAMP_CLOSE_PASS
+#define PEDP_ICP_STAMP_CLOSE_PASS 5  // the pass whose close is stamped phase by phase (diagnostic build; 0 or 1: a rebuild pass's, with its listing)
+#endif
 #define PEDP_STAMP_CLOSE(unit, slot) do { if (!HEAD || blockIdx.x == 0) PEDP_STAMP(2, unit, slot); } while (0)
 template <int NT, int LCAP, bool COHERENT, int MODE = 0>
 __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &f, FinishLds<NT, LCAP> &L, const int tid) {
@@ -343,7 +336,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
     const bool wide = f.serial == 0;
     if (tid == 0) { L.do_rebuild = 0; L.stopped = 0; }
     if (tid == 0) PEDP_STAMP_CLOSE(0, 0);
-    if (tid == 0 && pass == 5) PEDP_STAMP_CLOSE(3, 0);
+    if (tid == 0 && pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 0);
     // The first look at the sign-off counters is requested here, with the partial sums' loads, and evaluated where
     // the poll stands: the counters only grow, so a look that is complete now is complete then, and only a look that
     // comes back short enters the spin.  (With fewer live chunks than workgroups there are idle workgroups in every
@@ -354,6 +347,11 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         if (tid < 16) look0 = __hip_atomic_load((g_u32 *)(uintptr_t)(f.idle + 32 * tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         idle_base0 = st->idle_base;  // (rewritten only by this workgroup, further down)
     }
+    // a rebuild pass's close lists the live chunks anew: its mask words are requested here as well (every workgroup with a
+    // chunk has taken its ticket: the mask is final)
+    const bool listing = f.phase != 2 && !HEAD && (f.known ? f.k_rebuild != 0 : st->rebuild != 0);
+    LiveWords lw = {0, 0, 0, 0ull};
+    if (listing) lw = live_words_load<NT, COHERENT>(f.live, f.n_lw, tid);
     // what the solving thread needs of the state is requested now, ahead of the sums; the pose is parked in LDS, an
     // entry per lane (the barriers of the sums lie between this store and its readers): held in lane 0's registers
     // through the sums and the solve it was thirty-two registers of a kernel at its cap, spilled and fetched back
@@ -370,42 +368,13 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
     if (f.phase != 2) {
         // Partial sums are indexed by chunk id in a rebuild pass and by live rank otherwise; either
         // way they are summed in ascending chunk order.
-        const bool listing = !HEAD && (f.known ? f.k_rebuild != 0 : st->rebuild != 0);
         int n_live = f.known ? f.k_n_live : st->n_live;
         bool listed = true;
         if (listing) {
-            // the new live list, ascending: thread t owns a contiguous range of mask words
-            const int per = (f.n_lw + NT - 1) / NT;
-            const int w_lo = tid * per < f.n_lw ? tid * per : f.n_lw, w_hi = w_lo + per < f.n_lw ? w_lo + per : f.n_lw;
-            int mine = 0;
-            unsigned long long first = 0ull;  // (per == 1 for scenes up to 64 NT chunks: the word is read once)
-            for (int wi = w_lo; wi < w_hi; ++wi) {
-                const unsigned long long word = load_live<COHERENT>(&f.live[wi]);
-                if (wi == w_lo) first = word;
-                mine += __builtin_popcountll(word);
-            }
-            L.scan[tid] = mine;
-            __syncthreads();
-            for (int off = 1; off < NT; off <<= 1) {
-                const int t = tid >= off ? L.scan[tid - off] : 0;
-                __syncthreads();
-                L.scan[tid] += t;
-                __syncthreads();
-            }
-            n_live = L.scan[NT - 1];
+            // the new live list, ascending (live_list.h; the waves' totals go through the head of L.scan)
+            n_live = live_list_build<NT, LCAP, COHERENT>(lw, f.live, f.live_list, L.lst, L.scan, tid);
             listed = n_live <= LCAP;
-            int at = L.scan[tid] - mine;
-            for (int wi = w_lo; wi < w_hi; ++wi) {
-                unsigned long long word = wi == w_lo ? first : load_live<COHERENT>(&f.live[wi]);
-                while (word != 0ull) {
-                    const int chunk = wi * 64 + __builtin_ctzll(word);
-                    word &= word - 1ull;
-                    if (listed) L.lst[at] = chunk;
-                    as_global(f.live_list)[at] = chunk;
-                    ++at;
-                }
-            }
-            __syncthreads();
+            if (tid == 0 && pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 7);  // the list stands
         }
         // PARTS contiguous ranges of the live chunks, ascending inside a range, then the ranges in
         // order.  Sixteen loads in flight per thread and range; branch-free (an entry beyond the range
@@ -479,11 +448,11 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         if (!listing) sum_ranges([&](int q) { return q; });
         else if (listed) sum_ranges([&](int q) { return L.lst[q]; });
         else sum_ranges([&](int q) { return load_sc1(&f.live_list[q]); });
-        if (tid == 0 && pass == 5) PEDP_STAMP_CLOSE(3, 1);
+        if (tid == 0 && pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 1);
         if (HEAD) PEDP_RT(pass + 1, 5);  // head close: this workgroup's loads of the partial sums are back
         if (tid == 0) L.n_live_s = n_live;
         __syncthreads();
-        if (tid == 0 && pass == 5) PEDP_STAMP_CLOSE(3, 2);
+        if (tid == 0 && pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 2);
         if (tid < 32) {
             double t = 0.0;
             for (int q = 0; q < PARTS; ++q) t += L.slice[q][tid];
@@ -546,7 +515,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
         ident4(upd);
         if (l0) {
             PEDP_STAMP_CLOSE(0, 1);
-            if (pass == 5) PEDP_STAMP_CLOSE(3, 3);
+            if (pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 3);
             if (COHERENT) { st->ticket_base += (unsigned)f.n_busy; st->idle_base += (unsigned)f.n_idle; }
             if (f.phase == 0) {
                 st->sum_tiles += (long long)L.pk[PACKET];
@@ -586,7 +555,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 stop_i = 1;
             } else {
                 PEDP_STAMP_CLOSE(2, 0);
-                if (pass == 5) PEDP_STAMP_CLOSE(3, 4);
+                if (pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 4);
                 if (K > 0.0) {
                     if (f.estimator == PEDP_POINT_TO_PLANE && lane_form) {
                         solve_i = 1;  // (wave 0 solves below, a row per lane)
@@ -669,7 +638,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                     for (int k = 0; k < 16; ++k) upd[k] = bcast0(upd[k]);
                 }
                 if (l0) PEDP_STAMP_CLOSE(0, 2);
-                if (l0 && pass == 5) PEDP_STAMP_CLOSE(3, 5);
+                if (l0 && pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 5);
                 // lane k = 4 i + j holds entry (i, j) of the update and of upd x T0 (mat4_mul_dev's sum) and stores both
                 const int i = (tid >> 2) & 3, j = tid & 3;
                 double tn = 0.0, u_ij = 0.0;
@@ -687,7 +656,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 }
             } else {
                 PEDP_STAMP_CLOSE(0, 2);
-                if (pass == 5) PEDP_STAMP_CLOSE(3, 5);
+                if (pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 5);
                 for (int k = 0; k < 16; ++k) { st->upd[k] = upd[k]; if (!HEAD) as_global(f.hist)[16 * (pass + 1) + k] = upd[k]; }
                 double Tn[16];
                 mat4_mul_dev(upd, L.t0, Tn);
@@ -719,7 +688,7 @@ __device__ __forceinline__ void icp_finish_body(IcpState *st, const FinishArgs &
                 st->rebuild = L.do_rebuild;
                 st->pass = pass + 1;
                 PEDP_STAMP_CLOSE(2, 3);
-                if (pass == 5) PEDP_STAMP_CLOSE(3, 6);
+                if (pass == PEDP_ICP_STAMP_CLOSE_PASS) PEDP_STAMP_CLOSE(3, 6);
             }
         }
         if (l0) PEDP_STAMP_CLOSE(0, 3);

@@ -304,12 +304,15 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
     const double ccx_b = BATCH ? st->centroid[0] : 0.0, ccy_b = BATCH ? st->centroid[1] : 0.0, ccz_b = BATCH ? st->centroid[2] : 0.0;
     const float r_search_b = BATCH ? st->r_search : 0.f;
 #define PEDP_CC(k, b) (BATCH ? (b) : bcast0(cur.centroid[k]))
-    // A rebuild pass asks the chunks' bounding spheres first (64 of this workgroup's chunks per round, one
-    // per lane, every wave for itself): a sphere moved by the pose so far that stays farther than r + margin
+    // A rebuild pass asks the chunks' bounding spheres first (8 of this workgroup's chunks per round, a lane per
+    // run sphere, every wave for itself): a sphere moved by the pose so far that stays farther than r + margin
     // from the target's box holds no live point -- the chunk is not touched (only, if it was live before,
     // its points' correspondences are withdrawn).  The others are decided point by point as before.
     unsigned long long todo = 0ull;  // wave-uniform: chunks of the current round still to visit
-    int todo_base = -64, it = 0;
+    int todo_base = -8, it = 0;
+#if PEDP_ICP_STAMPS
+    bool rt_first = true;
+#endif
     if (rebuild && threadIdx.x == 0) {
         double Rs[12];
 #pragma unroll
@@ -346,41 +349,63 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
         if (rebuild) {
             bool more = true;
             while (todo == 0ull) {  // wave-uniform
-                todo_base += 64;
+                // A round decides eight chunks: lane 8 c + s takes run sphere s of the round's c-th chunk, and its 32 bytes
+                // and the old mask's word are requested before anything is looked at -- one round trip per round.  (A lane
+                // per chunk that walked the eight spheres, each behind a branch on its radius, was sixteen.)
+                todo_base += 8;
                 if ((long long)blockIdx.x + (long long)todo_base * (long long)gdim >= (long long)a.n_chunks) { more = false; break; }
-                const long long u = (long long)blockIdx.x + (long long)(todo_base + lane) * (long long)gdim;
-                bool visit = false, withdraw = false;
-                if (u < (long long)a.n_chunks) {
+                const long long u = (long long)blockIdx.x + (long long)(todo_base + (lane >> 3)) * (long long)gdim;
+                const bool inside = u < (long long)a.n_chunks;
+                const long long uc = inside ? u : 0;  // (a lane without a chunk reads chunk 0's sphere and uses nothing of it)
+                typedef double v2d __attribute__((ext_vector_type(2)));
+                const PEDP_GLOBAL v2d *sp8 = (const PEDP_GLOBAL v2d *)(uintptr_t)(a.chunk_sph + (size_t)(8 * uc + (lane & 7)) * 4);
+                const v2d sxy = sp8[0], szr = sp8[1];
+                const unsigned long long old_word = as_global(PEDP_MASK_OLD)[uc >> 6];
+                bool near_box;
+                {
                     double Rs[12];
 #pragma unroll
                     for (int k = 0; k < 12; ++k) Rs[k] = rbs[k];
                     const double rscale = rbs[12], reach = rbs[13];
-                    const bool was_live = (as_global(PEDP_MASK_OLD)[u >> 6] >> (u & 63)) & 1ull;
-#pragma unroll 2
-                    for (int sb = 0; sb < 8; ++sb) {
-                        const PEDP_GLOBAL double *sp8 = as_global(a.chunk_sph) + (size_t)(8 * u + sb) * 4;
-                        const double cx = sp8[0], cy = sp8[1], cz = sp8[2], cr = sp8[3];
-                        const double tx = Rs[0] * cx + Rs[1] * cy + Rs[2] * cz + Rs[3], ty = Rs[4] * cx + Rs[5] * cy + Rs[6] * cz + Rs[7],
-                                     tz = Rs[8] * cx + Rs[9] * cy + Rs[10] * cz + Rs[11];
-                        // (box_dist2 of slot_math.h, written out: the call moved instructions of this kernel)
-                        const double ex = fmax(fmax(a.lo[0] - tx, tx - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - ty, ty - a.hi[1]), 0.0),
-                                     ez = fmax(fmax(a.lo[2] - tz, tz - a.hi[2]), 0.0);
-                        const double lim = cr * rscale + reach + 1e-9 * (fabs(tx) + fabs(ty) + fabs(tz) + 1.0);
-                        visit |= !(cr < 0.0) && !(ex * ex + ey * ey + ez * ez > lim * lim);  // (also when anything is NaN)
-                    }
-                    withdraw = !visit && (was_live || pass == 0);   // pass 0: every chunk's correspondences start at "none"
+                    const double cx = sxy[0], cy = sxy[1], cz = szr[0], cr = szr[1];
+                    const double tx = Rs[0] * cx + Rs[1] * cy + Rs[2] * cz + Rs[3], ty = Rs[4] * cx + Rs[5] * cy + Rs[6] * cz + Rs[7],
+                                 tz = Rs[8] * cx + Rs[9] * cy + Rs[10] * cz + Rs[11];
+                    // (box_dist2 of slot_math.h, written out: the call moved instructions of this kernel)
+                    const double ex = fmax(fmax(a.lo[0] - tx, tx - a.hi[0]), 0.0), ey = fmax(fmax(a.lo[1] - ty, ty - a.hi[1]), 0.0),
+                                 ez = fmax(fmax(a.lo[2] - tz, tz - a.hi[2]), 0.0);
+                    const double lim = cr * rscale + reach + 1e-9 * (fabs(tx) + fabs(ty) + fabs(tz) + 1.0);
+                    // (the sentinel is looked at LAST: with it in front the compiler requests the centre only behind its test, a second
+                    // round trip.  Also when anything is NaN.)
+                    near_box = inside && !(ex * ex + ey * ey + ez * ez > lim * lim) && !(cr < 0.0);
                 }
-                todo = __builtin_amdgcn_ballot_w64(visit);
-                unsigned long long wd = __builtin_amdgcn_ballot_w64(withdraw);
-                while (wd != 0ull) {  // rare: a chunk that was live and no longer is
-                    const int i = __builtin_ctzll(wd);
-                    wd &= wd - 1ull;
-                    const int64_t k = ((int64_t)blockIdx.x + (int64_t)(todo_base + i) * gdim) * CH + tid;
-                    if (tid < CH && k < a.N) as_global(a.idx_out)[as_global(a.perm)[k]] = -1;
+                // a chunk is visited where any of its eight spheres says so; chunk c's bit of `todo` and `wd` is bit 8 c
+                const unsigned long long nb = __builtin_amdgcn_ballot_w64(near_box);
+                const bool visit = ((nb >> (lane & 56)) & 0xFFull) != 0ull;
+                const bool was_live = (old_word >> (uc & 63)) & 1ull;
+                const bool withdraw = inside && !visit && (was_live || pass == 0);  // pass 0: every chunk's correspondences start at "none"
+                todo = __builtin_amdgcn_ballot_w64(visit && (lane & 7) == 0);
+                const unsigned long long wd = __builtin_amdgcn_ballot_w64(withdraw && (lane & 7) == 0);
+                if (wd != 0ull) {  // pass 0: most chunks; later: a chunk that was live and no longer is
+                    // Withdrawals, four chunks at a time over the workgroup's eight waves (every wave runs the rounds for itself
+                    // and finds the same `wd`): wave w takes half w & 1 of the (w >> 1)-th and the (4 + (w >> 1))-th chunk to
+                    // withdraw, and both entries of the order are requested before the first store.
+                    int64_t kq[2];
+                    int pq[2];
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        unsigned long long rest = wd;
+                        for (int s = 0; s < 4 * q + (wv >> 1); ++s) rest &= rest - 1ull;  // (wave-uniform)
+                        kq[q] = rest != 0ull ? ((int64_t)blockIdx.x + (int64_t)(todo_base + (__builtin_ctzll(rest) >> 3)) * gdim) * CH + (tid & (CH - 1))
+                                             : a.N;
+                        pq[q] = kq[q] < a.N ? as_global(a.perm)[kq[q]] : 0;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+                        if (kq[q] < a.N) as_global(a.idx_out)[pq[q]] = -1;
                 }
             }
             if (!more) break;
-            const int i = __builtin_ctzll(todo);
+            const int i = __builtin_ctzll(todo) >> 3;
             todo &= todo - 1ull;
             unit = (int)(blockIdx.x + (unsigned)(todo_base + i) * (unsigned)gdim);
             chunk = unit;
@@ -394,6 +419,11 @@ __global__ __launch_bounds__(W * 64, 4) void icp_pass_kernel(IcpState *st0, cons
         long long t_chunk0 = 0;
         if (!BATCH && !rebuild) t_chunk0 = (long long)__builtin_amdgcn_s_memtime();
         if (tid == 0) PEDP_STAMP(1, blockIdx.x, 0);
+#if PEDP_ICP_STAMPS
+        // the workgroup's FIRST chunk on the device-wide clock (slot 5 is the head close's otherwise: a launch has one or the other)
+        if (!close_here && rt_first) PEDP_RT(pass, 5);
+        rt_first = false;
+#endif
         PEDP_WV(0, __builtin_amdgcn_s_memtime());
         PEDP_WV(9, pass);
         PEDP_WV(10, __builtin_amdgcn_s_memrealtime());

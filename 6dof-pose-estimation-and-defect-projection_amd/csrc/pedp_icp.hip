@@ -39,6 +39,7 @@
 //
 // Source map.  This file is one translation unit: the kernels live in headers under icp/, included below in
 // their order of definition, and the host orchestration follows them here.
+//   icp/live_list.h          the live list of a rebuild pass's close by a wave scan: live_words_load, live_list_build, live_list_debug_kernel
 //   icp/common.h             build switches (PEDP_NN_EXPERIMENT, PEDP_ICP_STAMPS), constants, IcpState, dmul/dadd/dsub, dist2
 //   icp/prep.h               hilbert3, cell_key_kernel, chunk_sphere_kernel, pack_target_kernel, sort_rows_kernel,
 //                            tile_sphere_kernel
@@ -298,7 +299,7 @@ inline const IcpSwitches &icp_switches() {
         s.cert = flag("PEDP_ICP_CERT", 1); s.steady = flag("PEDP_ICP_STEADY", 1);
         s.steady_from = num("PEDP_ICP_STEADY_FROM", 5); s.steady_grid = num("PEDP_ICP_STEADY_GRID", 0);
         s.steady_closers = num("PEDP_ICP_STEADY_CLOSERS", 0); s.steady_groups = num("PEDP_ICP_STEADY_GROUPS", 0);
-        s.lane_solve = num("PEDP_ICP_LANE_SOLVE", 1);
+        s.lane_solve = num("PEDP_ICP_LANE_SOLVE", 1); s.pass_grid = num("PEDP_ICP_PASS_GRID", 0);
         s.target_order = order && !strcmp(order, "hilbert") ? PEDP_TARGET_ORDER_HILBERT
                          : order && !strcmp(order, "compact") ? PEDP_TARGET_ORDER_COMPACT : PEDP_TARGET_ORDER_AUTO;
         return s;
@@ -499,6 +500,8 @@ int enqueue_fused_pass(pedp_ctx_t c, const IcpJob &job, const PassLaunch &l) {
     // grid-stride loop over the live chunks: any grid is correct; two workgroups per CU are resident
     int64_t g = job.w.n_chunks;
     if (g > 2 * c->num_cus) g = 2 * c->num_cus;
+    // PEDP_ICP_PASS_GRID=n caps the generic pass kernels' workgroups with chunks (tests: many chunks per workgroup at a few hundred points)
+    if (!l.steady_launch && icp_switches().pass_grid > 0 && g > icp_switches().pass_grid) g = icp_switches().pass_grid;
     if (g < 1) g = 1;
     if (pa.head) g += 1;  // head close: one workgroup more than the chunks can fill (the service workgroup)
     if (l.ev0) PEDP_HIP_CHECK(hipEventRecord(l.ev0, c->stream));
@@ -1548,6 +1551,30 @@ int pedp_debug_solve6(pedp_ctx_t c, int64_t n, const double *A, const double *b,
     if (e == hipSuccess) e = hipMemcpyAsync(ok_one, d_ok + (size_t)n, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d_A); (void)hipFree(d_b); (void)hipFree(d_x); (void)hipFree(d_ok);
+    PEDP_HIP_CHECK(e);
+    return PEDP_OK;
+}
+
+int pedp_debug_live_list(pedp_ctx_t c, const unsigned long long *mask_words, int n_lw, int threads, int32_t *list_out, int32_t *n_live_out) {
+    PEDP_REQUIRE(c && mask_words && list_out && n_live_out && n_lw > 0 && n_lw <= (1 << 20) && (threads == BK_W * 64 || threads == FIN_THREADS),
+                 "pedp_debug_live_list: null argument, a word count outside 1 .. 2^20, or a thread count other than 512 and 1024");
+    PEDP_HIP_CHECK(hipSetDevice(c->device));
+    unsigned long long *d_m = nullptr;
+    int32_t *d_l = nullptr;  // the list (64 n_lw entries), behind it the count
+    const size_t cap = 64 * (size_t)n_lw;
+    hipError_t e = hipMalloc((void **)&d_m, sizeof(unsigned long long) * (size_t)n_lw);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_l, sizeof(int32_t) * (cap + 1));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_m, mask_words, sizeof(unsigned long long) * (size_t)n_lw, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_l, list_out, sizeof(int32_t) * cap, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        if (threads == BK_W * 64) hipLaunchKernelGGL((live_list_debug_kernel<BK_W * 64, 2048, true>), dim3(1), dim3(BK_W * 64), 0, c->stream, d_m, n_lw, d_l, d_l + cap);
+        else hipLaunchKernelGGL((live_list_debug_kernel<FIN_THREADS, LIVE_CAP, false>), dim3(1), dim3(FIN_THREADS), 0, c->stream, d_m, n_lw, d_l, d_l + cap);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(list_out, d_l, sizeof(int32_t) * cap, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(n_live_out, d_l + cap, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_m); (void)hipFree(d_l);
     PEDP_HIP_CHECK(e);
     return PEDP_OK;
 }

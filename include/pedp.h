@@ -620,6 +620,12 @@ int pedp_icp_last_lane_solves(pedp_ctx_t ctx, int64_t *lane_solves);
 int pedp_debug_solve6(pedp_ctx_t ctx, int64_t n, const double *A, const double *b, double *x_lanes, int32_t *ok_lanes,
                       double *x_one, int32_t *ok_one);
 
+/* The live list of a rebuild pass's close (csrc/icp/live_list.h) on mask words of the caller's: n_lw words (uint64, bit b of
+ * word w: chunk 64 w + b is live) on the host, in one workgroup of `threads` = 512 (the close inside a pass launch: coherent
+ * loads, 2,048 entries of the list in LDS) or 1,024 (icp_finish_kernel: plain loads, 8,192 entries).  list_out (int32 x 64 n_lw)
+ * gets the set bits' positions, ascending, in its first *n_live_out entries; the rest is left as it was. */
+int pedp_debug_live_list(pedp_ctx_t ctx, const unsigned long long *mask_words, int n_lw, int threads, int32_t *list_out, int32_t *n_live_out);
+
 /* Diagnostics of the dense sweep's bf16 form (tests measure its error against float64): for n_src scene rows (b.x, b.y, b.z, .)
  * = (-2 s') and n_tgt model rows (t'.x, t'.y, t'.z, |t'|^2), float32 x 4 each on the host, counts multiples of 16,
  * g[i * n_tgt + j] = |t'_j|^2 - 2 s'_i . t'_j exactly as the sweep's v_mfma_f32_16x16x32_bf16 produces it (same operand packing). */
@@ -643,6 +649,7 @@ typedef struct pedp_icp_switches {  /* the environment switches, read once per p
     int steady_closers; /* workgroups of a steady launch that close a pass themselves; 0: the device's CU count */
     int steady_groups;  /* wave groups (ranks) per workgroup of a steady launch, 1 or 2; 0: by the scene's size (below) */
     int lane_solve;     /* PEDP_ICP_LANE_SOLVE: 0 the close's 6x6 solve on one lane, 1 (default) a row per lane of the closing wave */
+    int pass_grid;      /* PEDP_ICP_PASS_GRID: cap of a generic pass launch's workgroups with chunks (tests); 0: none.  The path does not depend on it */
 } pedp_icp_switches;
 typedef struct pedp_icp_path_inputs {
     int64_t n_source, n_target; /* source points, finite target rows */

@@ -67,7 +67,9 @@ print("finish, last solving pass: LDLT %.2f  sincos+T %.2f  T update, motion, st
 fin = buf[2][0]
 f5 = buf[2][3]
 if f5[6] > 0:
-    print("finish of pass 5 (us): state read + partial loads %.2f | barrier %.2f | 32-range sum + barrier %.2f | fitness, trace, criteria %.2f | solve + sincos %.2f | pose, bound, state %.2f" % tuple(np.diff(f5[:7]) * tick))
+    if f5[7] > f5[0]:  # a rebuild pass's close (a stamps library built with -DPEDP_ICP_STAMP_CLOSE_PASS=0 or 1): the listing's share of the first span
+        print("   of the first span below: close begun -> live list stands %.2f us" % ((f5[7] - f5[0]) * tick))
+    print("finish of pass %s (us): state read + partial loads %.2f | barrier %.2f | 32-range sum + barrier %.2f | fitness, trace, criteria %.2f | solve + sincos %.2f | pose, bound, state %.2f" % ((os.environ.get("PEDP_STAMP_CLOSE_PASS", "5"),) + tuple(np.diff(f5[:7]) * tick)))
 # device-wide timeline (s_memrealtime, 10-ns ticks) of every pass: first entry -> last chunk done -> pass closed -> next pass's first entry
 rt = np.zeros((32, 512, 8), np.int64)
 if hasattr(lib, "pedp_debug_icp_rt") and lib.pedp_debug_icp_rt(C.c_void_p(rt.ctypes.data)) == 0:
@@ -93,6 +95,12 @@ if hasattr(lib, "pedp_debug_icp_rt") and lib.pedp_debug_icp_rt(C.c_void_p(rt.cty
         if not in_launch:
             last = r[on, 2].max()
         hc = on & (r[:, 7] > 0)
+        fc = on & ~hc & (r[:, 5] >= e0) & (r[:, 5] <= r[:, 2])
+        if fc.any():  # no head close in this launch: slot 5 is the workgroup's first chunk begun (after entry, sphere tests, withdrawals)
+            line += (f"; first chunk begun median {np.median(us(r[fc,5])):5.2f} max {us(r[fc,5].max()):5.2f} ({fc.sum()} workgroups); "
+                     f"first chunk begun (median) -> last chunk done {us(r[on,2].max()) - np.median(us(r[fc,5])):6.2f}")
+        if in_launch:
+            line += f"; last ticket back -> closed {us(last) - us(r[on,3].max()):5.2f}"
         if hc.any():  # this launch began with the head close of the pass before
             line += (f"; head close: loads back median {np.median(us(r[hc,5])):5.2f} max {us(r[hc,5].max()):5.2f}, sums done median {np.median(us(r[hc,6])):5.2f}, "
                      f"U published median {np.median(us(r[hc,7])):5.2f} max {us(r[hc,7].max()):5.2f}")
