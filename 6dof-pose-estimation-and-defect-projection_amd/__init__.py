@@ -18,6 +18,7 @@ Layout
   view_plan.py     ViewPlanner: next-best-view planning, the gain of candidate camera poses over a CoverageMap; orbit_views
   deviation_map.py DeviationMap: per-face statistics of the signed deviation over frames, regions with their volume
   surface_fit.py   fit_to_surface: robust best fit of a scene cloud to the posed surface itself; refit_pose, fit_frame_to_surface
+  raycasting_scene.py RaycastingScene: cast_rays, count / list_intersections, test_occlusions and the distance queries on one mesh
   compat.py        `from pedp_hip.compat import *` in place of `from src import *` (run.py:3)
   dist.py          one-process-per-GPU sharding over torch.distributed (RCCL)
   synth.py         deterministic synthetic inputs of the benchmark configurations

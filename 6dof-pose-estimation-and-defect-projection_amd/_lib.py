@@ -67,6 +67,15 @@ PROTOTYPES = {
     "pedp_rayset_destroy": (None, [C.c_void_p]),
     "pedp_raycast_rayset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_rayset_last_variant": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
+    "pedp_count_intersections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "pedp_count_intersections_rayset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pedp_test_occlusions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "pedp_test_occlusions_rayset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "pedp_list_intersections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int64)]),
+    "pedp_list_intersections_rayset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int64)]),
+    "pedp_intersections_last_path": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
     "pedp_debug_mfma_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "pedp_mesh_posed_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pedp_project_heatmap_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int,
@@ -502,6 +511,7 @@ class Mesh:
         self.V, self.F = len(v), len(t)
         self.posable = bool(posable)
         self._hit_cap = 0        # project_heatmap: room kept for the hits (last call's count and a margin)
+        self._list_cap = 0       # list_intersections: room kept for the entries, likewise
         self._h = C.c_void_p()
         if posable:
             check(load().pedp_mesh_create_posable(ctx._h, _ptr(v), self.V, _ptr(t), self.F, C.byref(self._h)),
@@ -621,6 +631,82 @@ class Mesh:
         """Device-pointer variant (torch tensors' data_ptr()); asynchronous on the stream."""
         check(load().pedp_raycast(self.ctx._h, self._h, C.c_void_p(rays_ptr), int(n), DEVICE, C.c_void_p(t_ptr),
                                   C.c_void_p(id_ptr), C.c_void_p(uv_ptr) if uv_ptr else None), "pedp_raycast")
+
+    # ---- the all-hits queries (pedp_count_intersections, pedp_test_occlusions, pedp_list_intersections; DESIGN.md s4.24)
+    # `rays`: an N x 6 float32 host array, or a RaySet.
+
+    def _hits_call(self, name, rays, *rest):
+        """pedp_<name>(ctx, mesh, rays6, N, HOST, ...) or its _rayset twin; returns (N, status)."""
+        if isinstance(rays, RaySet):
+            return rays.N, getattr(load(), f"pedp_{name}_rayset")(self.ctx._h, self._h, rays._h, HOST, *rest)
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        return len(r), getattr(load(), f"pedp_{name}")(self.ctx._h, self._h, _ptr(r), len(r), HOST, *rest)
+
+    @staticmethod
+    def _n_rays(rays):
+        return rays.N if isinstance(rays, RaySet) else np.asarray(rays).size // 6
+
+    def count_intersections(self, rays):
+        """RaycastingScene.count_intersections: int32 per ray, the number of triangles it intersects."""
+        out = np.empty(self._n_rays(rays), np.int32)
+        check(self._hits_call("count_intersections", rays, _ptr(out))[1], "pedp_count_intersections")
+        return out
+
+    def test_occlusions(self, rays, tnear=0.0, tfar=np.inf):
+        """RaycastingScene.test_occlusions: bool per ray, whether a triangle it intersects has tnear <= t <= tfar."""
+        out = np.empty(self._n_rays(rays), np.uint8)
+        check(self._hits_call("test_occlusions", rays, C.c_float(tnear), C.c_float(tfar), _ptr(out))[1], "pedp_test_occlusions")
+        return out.view(np.bool_)
+
+    def list_intersections(self, rays):
+        """RaycastingScene.list_intersections: dict(ray_splits int64 N + 1, ray_ids int64 M, t_hit f32 M, geometry_ids u32
+        zeros M, primitive_ids u32 M, primitive_uvs f32 M x 2); a ray's entries by ascending t, then triangle index.
+        Room for the entries is kept from the last call (its count and a margin); a call that needs more runs once more."""
+        n = self._n_rays(rays)
+        cap = self._list_cap or max(4 * n, 1024)
+        while True:
+            splits = np.empty(n + 1, np.int64)
+            ids, t = np.empty(cap, np.int64), np.empty(cap, np.float32)
+            prim, uv = np.empty(cap, np.uint32), np.empty((cap, 2), np.float32)
+            total = C.c_int64()
+            _, rc = self._hits_call("list_intersections", rays, cap, _ptr(splits), _ptr(ids), _ptr(t), _ptr(prim), _ptr(uv),
+                                    C.byref(total))
+            if rc != 0 and total.value > cap:     # more entries than room (the count is reported): once more with room for them
+                cap = total.value
+                continue
+            check(rc, "pedp_list_intersections")
+            break
+        m = total.value
+        self._list_cap = m + m // 4 + 1024
+        return {"ray_splits": splits, "ray_ids": ids[:m], "t_hit": t[:m], "geometry_ids": np.zeros(m, np.uint32),
+                "primitive_ids": prim[:m], "primitive_uvs": uv[:m]}
+
+    def count_intersections_rayset(self, rayset):
+        return self.count_intersections(rayset)
+
+    def test_occlusions_rayset(self, rayset, tnear=0.0, tfar=np.inf):
+        return self.test_occlusions(rayset, tnear, tfar)
+
+    def list_intersections_rayset(self, rayset):
+        return self.list_intersections(rayset)
+
+    def count_intersections_device(self, rays_ptr, n, counts_ptr):
+        """Device-pointer form (torch tensors' data_ptr(); counts int32); asynchronous on the stream."""
+        check(load().pedp_count_intersections(self.ctx._h, self._h, C.c_void_p(rays_ptr), int(n), DEVICE, C.c_void_p(counts_ptr)),
+              "pedp_count_intersections")
+
+    def count_intersections_rayset_device(self, rayset, counts_ptr):
+        check(load().pedp_count_intersections_rayset(self.ctx._h, self._h, rayset._h, DEVICE, C.c_void_p(counts_ptr)),
+              "pedp_count_intersections_rayset")
+
+    def test_occlusions_device(self, rays_ptr, n, occluded_ptr, tnear=0.0, tfar=np.inf):
+        """Device-pointer form (occluded: one byte per ray); asynchronous on the stream."""
+        check(load().pedp_test_occlusions(self.ctx._h, self._h, C.c_void_p(rays_ptr), int(n), DEVICE, C.c_float(tnear), C.c_float(tfar),
+                                          C.c_void_p(occluded_ptr)), "pedp_test_occlusions")
+
+    def test_occlusions_rayset_device(self, rayset, occluded_ptr, tnear=0.0, tfar=np.inf):
+        check(load().pedp_test_occlusions_rayset(self.ctx._h, self._h, rayset._h, DEVICE, C.c_float(tnear), C.c_float(tfar),
+                                                 C.c_void_p(occluded_ptr)), "pedp_test_occlusions_rayset")
 
     CLOSEST_OUTPUTS = {"points": (3, np.float64), "distances": (None, np.float64), "primitive_ids": (None, np.uint32),
                        "primitive_uvs": (2, np.float64), "sides": (None, np.int8)}
@@ -831,6 +917,13 @@ def ransac_hypotheses(ctx, src, tgt, corr, seed, itr0, count, edge_similarity, m
                                         float(edge_similarity), float(max_distance), float(normal_angle), _ptr(ok), _ptr(T)),
           "pedp_ransac_hypotheses")
     return ok.astype(bool), T
+
+
+def intersections_last_path(ctx):
+    """(path, grid_status) of the context's last all-hits query (pedp_intersections_last_path): path 4 the grid, 1 exhaustive."""
+    p, g = C.c_int(), C.c_int()
+    check(load().pedp_intersections_last_path(ctx._h, C.byref(p), C.byref(g)), "pedp_intersections_last_path")
+    return p.value, g.value
 
 
 def raycast_last_variant(ctx):

@@ -68,6 +68,7 @@ from .defect_map import DefectMap  # noqa: E402,F401  (run.py:61, :119, :196-201
 from .coverage import CoverageMap  # noqa: E402,F401  (no counterpart: run.py never says what was not inspected)
 from .view_plan import ViewPlanner, orbit_views  # noqa: E402,F401  (no counterpart: where to point the camera next)
 from .deviation_map import DeviationMap  # noqa: E402,F401  (no counterpart: how far off each face is, over all frames)
+from .raycasting_scene import RaycastingScene  # noqa: E402,F401  (defect_projection.py:245-256 builds one; here with all its queries)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
 
@@ -104,5 +105,5 @@ __all__ = [
     "closest_points", "compute_distance", "align_to_mesh", "deviation_heatmap",
     "Solid", "compute_signed_distance", "compute_occupancy", "signed_closest_points", "signed_deviation", "split_deviation",
     "fit_to_surface", "refit_pose", "fit_frame_to_surface",
-    "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap",
+    "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap", "RaycastingScene",
 ]

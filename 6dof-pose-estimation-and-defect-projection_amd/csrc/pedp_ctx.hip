@@ -274,6 +274,10 @@ void pedp_ctx_destroy(pedp_ctx_t c) {
     c->cloud_pool.clear();
     c->sort_ws.release();
     if (c->rast_status) (void)hipHostFree(c->rast_status);
+    if (c->hits_status) (void)hipHostFree(c->hits_status);
+    c->hits_ws.release();
+    c->hits_keys.release();
+    c->hits_io.release();
     c->icp_ws.release();
     c->proj.release();
     c->ops.release();

@@ -127,6 +127,14 @@ struct pedp_ctx_s {
     int ray_last_variant = 0;        // variant the last cast on this context ran
     int ray_tri_chunks = 0;  // 0 = auto
     int ray_variant = 0;     // 0 = auto; written by pedp_raycast_configure only
+    // all-hits queries (pedp_count_intersections, pedp_test_occlusions, pedp_list_intersections)
+    pedp_scratch hits_ws;    // per ray: counts, cursors, splits; the scan's scratch
+    pedp_scratch hits_keys;  // a list's keys as they arrive and sorted; the sort's scratch
+    pedp_scratch hits_io;    // outputs of host-memory calls
+    int *hits_status = nullptr;  // pinned, the queries' own words (the casts' rast_status stays theirs): [0] why the grid gave up (0: it did not), [1] ray count
+    const int *hits_last_status = nullptr;  // the words the last query's grid pass reports to (the context's or a ray set's)
+    int hits_avoid_n = -2;   // ray count whose last per-call query the grid gave up on: the exhaustive path instead (auto only)
+    int hits_last_path = 0;  // 4: the grid, 1: every ray against every triangle; 0: no query yet
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // sweep timing
     hipEvent_t ev_copy = nullptr;             // pedp_cloud_create_device: behind its copies (the host waits on it)
     bool ray_timed = false;

@@ -24,10 +24,15 @@
 // Variants 1, 3 and 5 hand rays of differing origins to the general-origin sweep of ray/sweep_packed.h on the
 // device; variant 4 completes what its grid cannot answer in ray_finalize_kernel.  ray/mesh_records.h builds what
 // a mesh handle holds.
+//
+// The all-hits queries (count / occlusion / list of intersections, at the end of this file) hand the same accepted
+// pairs to other sinks than the atomicMin: ray/all_hits.h, over the grid's traversal or an exhaustive sweep.
 #include "pedp_internal.h"
 #include <algorithm>
 #include <cstdlib>
 #include <new>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
 #include "ray/mt.h"
 #include "ray/mesh_records.h"
 #include "ray/sweep_packed.h"
@@ -36,6 +41,7 @@
 #include "ray/grid.h"
 #include "ray/sweep_tri_lane.h"
 #include "ray/finalize.h"
+#include "ray/all_hits.h"
 
 namespace {
 
@@ -113,6 +119,15 @@ void grid_enqueue_build(pedp_ctx_t c, const float *d_rays, int64_t N, const Grid
     launch(c, rast_insert_kernel, (N + 255) / 256, 256, d_rays, N, h, g.head, g.nodes, g.part);
 }
 
+// The triangles against the grid built under header h: every accepted pair goes to `sink` (HitMin: a cast).
+template <class Sink>
+void grid_enqueue_walk(pedp_ctx_t c, pedp_mesh_t mesh, const float *d_rays, int64_t N, const GridScratch &g, RastHdr *h, Sink sink) {
+    if (mesh->F > 0)
+        launch(c, rast_tri_kernel<Sink>, (mesh->F + 255) / 256, 256, mesh->tri, mesh->F, h, g.head, g.nodes, g.items, sink, g.full_list);
+    launch(c, rast_item_kernel<Sink>, RAST_ITEM_WAVES / 4, 256, mesh->tri, h, g.head, g.nodes, g.items, sink);
+    launch(c, rast_full_kernel<Sink>, (N + 255) / 256, 256, mesh->tri, d_rays, N, h, g.full_list, sink);
+}
+
 // The triangles against the built grid, the end of the timed stretch, the results.  seq picks the header; status:
 // the pinned status words, which the last kernel writes through the device's address of them.
 int grid_enqueue_cast(pedp_ctx_t c, pedp_mesh_t mesh, const float *d_rays, int64_t N, const GridScratch &g, unsigned seq,
@@ -120,10 +135,7 @@ int grid_enqueue_cast(pedp_ctx_t c, pedp_mesh_t mesh, const float *d_rays, int64
     int *d_status = nullptr;
     PEDP_HIP_CHECK(hipHostGetDevicePointer((void **)&d_status, status, 0));
     RastHdr *h = g.hdr[seq & 1], *h_next = g.hdr[(seq + 1) & 1];
-    if (mesh->F > 0)
-        launch(c, rast_tri_kernel, (mesh->F + 255) / 256, 256, mesh->tri, mesh->F, h, g.head, g.nodes, g.items, keys, g.full_list);
-    launch(c, rast_item_kernel, RAST_ITEM_WAVES / 4, 256, mesh->tri, h, g.head, g.nodes, g.items, keys);
-    launch(c, rast_full_kernel, (N + 255) / 256, 256, mesh->tri, d_rays, N, h, g.full_list, keys);
+    grid_enqueue_walk(c, mesh, d_rays, N, g, h, HitMin{keys});
     PEDP_HIP_CHECK(hipGetLastError());
     PEDP_HIP_CHECK(hipEventRecord(c->ev1, c->stream));
     c->ray_timed = true;
@@ -490,6 +502,8 @@ struct pedp_rayset_s {
     unsigned seq = 0;           // casts enqueued: picks one of the two headers
     bool grid_ok = false;       // the build found the rays servable; cleared for good by a cast that was not answered by the grid
     int last_variant = 0, last_status = 0;
+    uint64_t id = 0;            // process-wide, never reused: names the set in the all-hits queries' status words
+    bool hits_avoid = false;    // an all-hits query's grid pass gave up on these rays: the exhaustive path from now on (auto only)
 };
 
 // the set's one allocation; base == nullptr: its size only
@@ -510,7 +524,7 @@ int pedp_rayset_create(pedp_ctx_t c, const float *rays6, int64_t N, int mem, ped
     PEDP_HIP_CHECK(hipSetDevice(c->device));
     pedp_rayset_s *r = new (std::nothrow) pedp_rayset_s();
     if (!r) { pedp_set_error("pedp_rayset_create: out of host memory"); return PEDP_ERR_ALLOC; }
-    r->ctx = c; r->device = c->device; r->N = N;
+    r->ctx = c; r->device = c->device; r->N = N; r->id = pedp_next_generation();
     hipError_t e = hipMalloc((void **)&r->buf, rayset_carve(r, nullptr));
     if (e == hipSuccess) e = hipHostMalloc((void **)&r->status, 64, hipHostMallocMapped);
     if (e != hipSuccess) { pedp_set_error("pedp_rayset_create: %s", hipGetErrorString(e)); pedp_rayset_destroy(r); return PEDP_ERR_ALLOC; }
@@ -601,6 +615,267 @@ int pedp_raycast_last_variant(pedp_ctx_t c, int *variant, int *grid_status) {
     PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
     *variant = c->ray_last_variant;
     *grid_status = (c->ray_last_variant == 4 && c->rast_status) ? ((volatile int *)c->rast_status)[0] : 0;
+    return PEDP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- all-hits queries (ray/all_hits.h, DESIGN s4.24)
+namespace {
+
+constexpr int HITS_PATH_GRID = 4, HITS_PATH_EXHAUSTIVE = 1;   // pedp_intersections_last_path
+
+// The rays of a query, checked: device rows (a call's own, uploaded in host mode, or a ray set's resident copy).
+struct HitsRays { const float *d; int64_t N; pedp_rayset_s *set; };
+int hits_rays(pedp_ctx_t c, pedp_mesh_t mesh, const float *rays6, int64_t N, pedp_rayset_t set, bool by_set, int mem, const char *who,
+              HitsRays *out) {
+    PEDP_REQUIRE(c && mesh && (!by_set || set), "%s: null context / mesh / ray set", who);
+    PEDP_REQUIRE(mesh->ctx == c && (!by_set || set->ctx == c), "%s: mesh or ray set belongs to another context", who);
+    PEDP_REQUIRE(mem == PEDP_HOST || mem == PEDP_DEVICE, "%s: bad mem flag %d", who, mem);
+    if (by_set) N = set->N;
+    PEDP_REQUIRE(N >= 0 && N < (int64_t)0x7FFFFFF0, "%s: N out of range", who);
+    PEDP_REQUIRE(mesh->F > 0 && mesh->F < (int64_t)0x7FFFFFF0, "%s: the mesh has no triangles (or 2^31 and more)", who);
+    PEDP_REQUIRE(by_set || rays6 || N == 0, "%s: null rays", who);
+    PEDP_HIP_CHECK(hipSetDevice(c->device));
+    *out = HitsRays{by_set ? set->rays : rays6, N, by_set ? set : nullptr};
+    if (!by_set && mem == PEDP_HOST && N > 0) {
+        PEDP_TRY(c->ray_in.reserve(sizeof(float) * 6 * (size_t)N));
+        PEDP_TRY(pedp_upload(c, c->ray_in.ptr, rays6, sizeof(float) * 6 * (size_t)N));
+        out->d = (const float *)c->ray_in.ptr;
+    }
+    return PEDP_OK;
+}
+
+// Path choice: pedp_raycast_configure's variant.  0: the grid from 16,384 rays on and for a ray set, unless an earlier
+// query's grid pass gave up on these rays (read from the status words without waiting: at worst the news comes a call
+// late); 4: the grid; others: every ray against every triangle.  A ray set whose grid cannot serve it has no grid to use.
+bool hits_use_grid(pedp_ctx_t c, const HitsRays &r) {
+    const int variant = c->ray_variant;
+    volatile int *st = c->hits_status;
+    if (st && st[0] != 0) {
+        const uint64_t owner = (uint64_t)(unsigned)st[2] | ((uint64_t)(unsigned)st[3] << 32);
+        if (owner == 0) c->hits_avoid_n = st[1];
+        else if (r.set && r.set->id == owner) r.set->hits_avoid = true;
+    }
+    if (r.set) {
+        volatile int *cs = r.set->status;   // (a cast the grid did not answer: pedp_raycast_rayset retires the grid at its next call)
+        const bool cast_gave_up = cs[1] == (int)(r.N & 0x7FFFFFFF) && cs[0] != 0;
+        if (!r.set->grid_ok || cast_gave_up) return false;
+        return variant == 4 || (variant == 0 && !r.set->hits_avoid);
+    }
+    return variant == 4 || (variant == 0 && r.N >= 16384 && c->hits_avoid_n != (int)(r.N & 0x7FFFFFFF));
+}
+
+// One pass over the rays: every pair that mt_accept accepts reaches `sink` exactly once.  The sink's words are zero
+// before it.  With the grid: the casts' three kernels, then ah_close_kernel (status; the next header; where the grid
+// gave up, the words back to zero), then ah_sweep_kernel, which returns at once unless the grid gave up -- the
+// decision stays on the device.  Without: ah_sweep_kernel alone.  The grid's scratch is the context's (built here, as
+// cast_grid does, the casts' header protocol kept) or the ray set's (built at creation; its keys are not touched).
+template <class Sink>
+int hits_pass(pedp_ctx_t c, pedp_mesh_t mesh, const HitsRays &r, bool use_grid, Sink sink) {
+    const int64_t N = r.N;
+    const RastHdr *h_walked = nullptr;
+    if (use_grid) {
+        if (!c->hits_status) {
+            PEDP_HIP_CHECK(hipHostMalloc((void **)&c->hits_status, 64, hipHostMallocMapped));
+            memset(c->hits_status, 0, 64);
+            c->hits_status[1] = -1;
+        }
+        int *d_status = nullptr;
+        PEDP_HIP_CHECK(hipHostGetDevicePointer((void **)&d_status, c->hits_status, 0));
+        GridScratch g;
+        unsigned seq;
+        if (r.set) {
+            g = r.set->grid;
+            seq = r.set->seq;
+        } else {
+            PEDP_TRY(c->ray_keys.reserve(sizeof(unsigned long long) * (size_t)N));
+            PEDP_TRY(c->ray_rast.reserve(GridScratch::bytes(N)));
+            char *base = (char *)c->ray_rast.ptr;
+            g = GridScratch(base, N);
+            seq = c->rast_seq;
+            if (c->rast_hdr_ready != (void *)base) {  // new buffer, or a pass that did not reach its last kernel
+                PEDP_HIP_CHECK(hipMemcpyAsync(g.hdr[seq & 1], &RAST_HDR_START, sizeof(RastHdr), hipMemcpyHostToDevice, c->stream));
+                PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
+            }
+            c->rast_hdr_ready = nullptr;
+            grid_enqueue_build(c, r.d, N, g, g.hdr[seq & 1], (unsigned long long *)c->ray_keys.ptr);
+        }
+        RastHdr *h = g.hdr[seq & 1], *h_next = g.hdr[(seq + 1) & 1];
+        grid_enqueue_walk(c, mesh, r.d, N, g, h, sink);
+        launch(c, ah_close_kernel<Sink>, (N + 255) / 256, 256, N, (const RastHdr *)h, h_next, d_status,
+               (unsigned long long)(r.set ? r.set->id : 0), sink);
+        PEDP_HIP_CHECK(hipGetLastError());
+        if (r.set) r.set->seq += 1;
+        else { c->rast_hdr_ready = c->ray_rast.ptr; c->rast_seq += 1; }
+        h_walked = h;
+    }
+    // triangle chunks: enough workgroups for four rounds over the chip, no chunk below 256 triangles
+    const int64_t ray_blocks = (N + 255) / 256;
+    int64_t n_chunks = 1;
+    while (ray_blocks * n_chunks < 4 * (int64_t)c->num_cus && mesh->F / (n_chunks * 2) >= 256 && n_chunks < 32768) n_chunks *= 2;
+    const int64_t per_chunk = (mesh->F + n_chunks - 1) / n_chunks;
+    hipLaunchKernelGGL(ah_sweep_kernel<Sink>, dim3((unsigned)ray_blocks, (unsigned)n_chunks), dim3(256), 0, c->stream, (const float *)mesh->tri,
+                       mesh->F, per_chunk, r.d, N, h_walked, sink);
+    PEDP_HIP_CHECK(hipGetLastError());
+    return PEDP_OK;
+}
+
+// count_intersections / test_occlusions: one word per ray, zeroed, one pass, delivered.  T: int32_t with HitCount,
+// uint8_t with HitInRange (make: the sink over the device words).
+template <class T, class Make>
+int hits_per_ray(pedp_ctx_t c, pedp_mesh_t mesh, const HitsRays &r, int mem, T *out, const char *who, Make make) {
+    if (r.N == 0) return PEDP_OK;
+    PEDP_REQUIRE(out, "%s: null output", who);
+    T *d_out = out;
+    if (mem == PEDP_HOST) {
+        PEDP_TRY(c->hits_io.reserve(sizeof(T) * (size_t)r.N));
+        d_out = (T *)c->hits_io.ptr;
+    }
+    PEDP_HIP_CHECK(hipMemsetAsync(d_out, 0, sizeof(T) * (size_t)r.N, c->stream));
+    const bool use_grid = hits_use_grid(c, r);
+    c->hits_last_path = use_grid ? HITS_PATH_GRID : HITS_PATH_EXHAUSTIVE;
+    PEDP_TRY(hits_pass(c, mesh, r, use_grid, make(d_out)));
+    return mem == PEDP_HOST ? pedp_download(c, out, d_out, sizeof(T) * (size_t)r.N) : PEDP_OK;
+}
+
+// What a list works in besides its keys (member order is layout, as in GridScratch).
+struct HitsListScratch {
+    Carver cv; int64_t N; size_t scan_bytes;
+    int *counts = cv.take<int>((size_t)N + 1);            // (the last one stays zero: the scan runs over N + 1)
+    int *cursor = cv.take<int>((size_t)N);
+    long long *splits = cv.take<long long>((size_t)N + 1);
+    char *scan_tmp = cv.take<char>(scan_bytes);
+    HitsListScratch(char *base, int64_t N, size_t scan_bytes) : cv{base}, N(N), scan_bytes(scan_bytes) {}
+};
+struct HitsKeys {   // a list's M keys as the fill pass leaves them and sorted, and the sort's scratch
+    Carver cv; int64_t M; size_t sort_bytes;
+    unsigned long long *arrived = cv.take<unsigned long long>((size_t)M);
+    unsigned long long *sorted = cv.take<unsigned long long>((size_t)M);
+    char *sort_tmp = cv.take<char>(sort_bytes);
+    HitsKeys(char *base, int64_t M, size_t sort_bytes) : cv{base}, M(M), sort_bytes(sort_bytes) {}
+};
+struct HitsOut {    // a host-memory list's outputs on the device
+    Carver cv; int64_t M;
+    long long *ray_ids = cv.take<long long>((size_t)M);
+    float *t = cv.take<float>((size_t)M);
+    uint32_t *prim = cv.take<uint32_t>((size_t)M);
+    float *uv = cv.take<float>(2 * (size_t)M);
+    HitsOut(char *base, int64_t M) : cv{base}, M(M) {}
+};
+
+// list_intersections: count pass, exclusive scan (ray_splits and M), fill pass, a segmented radix sort of the keys
+// over ray_splits (rocPRIM: linear in a segment's length), the outputs from the sorted keys.  One host wait, which M
+// needs; the count pass's grid status comes with it and picks the fill pass's path.  Both passes hand the sink the
+// pairs mt_accept accepts, each once, whatever the path: the same set (DESIGN s4.24).
+int hits_list(pedp_ctx_t c, pedp_mesh_t mesh, const HitsRays &r, int mem, int64_t capacity, int64_t *ray_splits, int64_t *ray_ids,
+              float *t_hit, uint32_t *prim_id, float *uv, int64_t *total, const char *who) {
+    PEDP_REQUIRE(total && ray_splits && capacity >= 0, "%s: null ray_splits / total, or a negative capacity", who);
+    PEDP_REQUIRE(capacity == 0 || (ray_ids && t_hit && prim_id && uv), "%s: null output arrays", who);
+    const int64_t N = r.N;
+    *total = 0;
+    size_t scan_bytes = 0;
+    PEDP_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, (int *)nullptr, (long long *)nullptr, 0ll, (size_t)N + 1,
+                                           rocprim::plus<long long>(), c->stream));
+    PEDP_TRY(c->hits_ws.reserve(HitsListScratch(nullptr, N, scan_bytes).cv.at));
+    const HitsListScratch w((char *)c->hits_ws.ptr, N, scan_bytes);
+    long long *splits = mem == PEDP_DEVICE ? (long long *)ray_splits : w.splits;
+    PEDP_HIP_CHECK(hipMemsetAsync(w.counts, 0, sizeof(int) * ((size_t)N + 1), c->stream));
+    if (N > 0) PEDP_HIP_CHECK(hipMemsetAsync(w.cursor, 0, sizeof(int) * (size_t)N, c->stream));
+    bool use_grid = N > 0 && hits_use_grid(c, r);
+    if (N > 0) {
+        c->hits_last_path = use_grid ? HITS_PATH_GRID : HITS_PATH_EXHAUSTIVE;
+        PEDP_TRY(hits_pass(c, mesh, r, use_grid, HitCount{w.counts}));
+    }
+    size_t tmp = scan_bytes;   // rocprim takes it by reference
+    PEDP_HIP_CHECK(rocprim::exclusive_scan(w.scan_tmp, tmp, w.counts, splits, 0ll, (size_t)N + 1, rocprim::plus<long long>(), c->stream));
+    long long *h_total = pedp_pinned_at<long long>(c, pedp_pinned::COUNTERS);
+    PEDP_HIP_CHECK(hipMemcpyAsync(h_total, splits + N, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const int64_t M = *h_total;
+    if (use_grid && ((volatile int *)c->hits_status)[0] != 0) use_grid = false;   // the grid gave up: the fill pass need not ask it again
+    *total = M;
+    if (mem == PEDP_HOST) PEDP_TRY(pedp_download(c, ray_splits, splits, sizeof(long long) * ((size_t)N + 1)));
+    PEDP_REQUIRE(M <= capacity, "%s: %lld intersections, room for %lld", who, (long long)M, (long long)capacity);
+    if (M == 0) return PEDP_OK;
+    PEDP_REQUIRE(M < (int64_t)0x7FFFFFF0, "%s: 2^31 intersections and more", who);
+    size_t sort_bytes = 0;
+    PEDP_HIP_CHECK(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                      (unsigned)M, (unsigned)N, (const long long *)nullptr, (const long long *)nullptr, 0, 64,
+                                                      c->stream));
+    PEDP_TRY(c->hits_keys.reserve(HitsKeys(nullptr, M, sort_bytes).cv.at));
+    const HitsKeys k((char *)c->hits_keys.ptr, M, sort_bytes);
+    PEDP_TRY(hits_pass(c, mesh, r, use_grid, HitFill{splits, w.cursor, k.arrived}));
+    PEDP_HIP_CHECK(rocprim::segmented_radix_sort_keys(k.sort_tmp, sort_bytes, k.arrived, k.sorted, (unsigned)M, (unsigned)N,
+                                                      (const long long *)splits, (const long long *)splits + 1, 0, 64, c->stream));
+    HitsOut o(nullptr, M);
+    if (mem == PEDP_HOST) {
+        PEDP_TRY(c->hits_io.reserve(o.cv.at));
+        o = HitsOut((char *)c->hits_io.ptr, M);
+    } else {
+        o.ray_ids = (long long *)ray_ids; o.t = t_hit; o.prim = prim_id; o.uv = uv;
+    }
+    launch(c, ah_emit_kernel, (M + 255) / 256, 256, (const float *)mesh->tri, mesh->F, r.d, N, (const long long *)splits,
+           (const unsigned long long *)k.sorted, M, o.ray_ids, o.t, o.prim, o.uv);
+    PEDP_HIP_CHECK(hipGetLastError());
+    if (mem == PEDP_HOST) {
+        PEDP_TRY(pedp_download(c, ray_ids, o.ray_ids, sizeof(long long) * (size_t)M));
+        PEDP_TRY(pedp_download(c, t_hit, o.t, sizeof(float) * (size_t)M));
+        PEDP_TRY(pedp_download(c, prim_id, o.prim, sizeof(uint32_t) * (size_t)M));
+        PEDP_TRY(pedp_download(c, uv, o.uv, sizeof(float) * 2 * (size_t)M));
+    }
+    return PEDP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pedp_count_intersections(pedp_ctx_t c, pedp_mesh_t mesh, const float *rays6, int64_t N, int mem, int32_t *counts) {
+    HitsRays r;
+    PEDP_TRY(hits_rays(c, mesh, rays6, N, nullptr, false, mem, "pedp_count_intersections", &r));
+    return hits_per_ray(c, mesh, r, mem, counts, "pedp_count_intersections", [](int32_t *d) { return HitCount{d}; });
+}
+
+int pedp_count_intersections_rayset(pedp_ctx_t c, pedp_mesh_t mesh, pedp_rayset_t rays, int mem, int32_t *counts) {
+    HitsRays r;
+    PEDP_TRY(hits_rays(c, mesh, nullptr, 0, rays, true, mem, "pedp_count_intersections_rayset", &r));
+    return hits_per_ray(c, mesh, r, mem, counts, "pedp_count_intersections_rayset", [](int32_t *d) { return HitCount{d}; });
+}
+
+int pedp_test_occlusions(pedp_ctx_t c, pedp_mesh_t mesh, const float *rays6, int64_t N, int mem, float tnear, float tfar, uint8_t *occluded) {
+    HitsRays r;
+    PEDP_TRY(hits_rays(c, mesh, rays6, N, nullptr, false, mem, "pedp_test_occlusions", &r));
+    return hits_per_ray(c, mesh, r, mem, occluded, "pedp_test_occlusions", [=](uint8_t *d) { return HitInRange{d, tnear, tfar}; });
+}
+
+int pedp_test_occlusions_rayset(pedp_ctx_t c, pedp_mesh_t mesh, pedp_rayset_t rays, int mem, float tnear, float tfar, uint8_t *occluded) {
+    HitsRays r;
+    PEDP_TRY(hits_rays(c, mesh, nullptr, 0, rays, true, mem, "pedp_test_occlusions_rayset", &r));
+    return hits_per_ray(c, mesh, r, mem, occluded, "pedp_test_occlusions_rayset", [=](uint8_t *d) { return HitInRange{d, tnear, tfar}; });
+}
+
+int pedp_list_intersections(pedp_ctx_t c, pedp_mesh_t mesh, const float *rays6, int64_t N, int mem, int64_t capacity, int64_t *ray_splits,
+                            int64_t *ray_ids, float *t_hit, uint32_t *prim_ids, float *uvs, int64_t *total) {
+    HitsRays r;
+    PEDP_TRY(hits_rays(c, mesh, rays6, N, nullptr, false, mem, "pedp_list_intersections", &r));
+    return hits_list(c, mesh, r, mem, capacity, ray_splits, ray_ids, t_hit, prim_ids, uvs, total, "pedp_list_intersections");
+}
+
+int pedp_list_intersections_rayset(pedp_ctx_t c, pedp_mesh_t mesh, pedp_rayset_t rays, int mem, int64_t capacity, int64_t *ray_splits,
+                                   int64_t *ray_ids, float *t_hit, uint32_t *prim_ids, float *uvs, int64_t *total) {
+    HitsRays r;
+    PEDP_TRY(hits_rays(c, mesh, nullptr, 0, rays, true, mem, "pedp_list_intersections_rayset", &r));
+    return hits_list(c, mesh, r, mem, capacity, ray_splits, ray_ids, t_hit, prim_ids, uvs, total, "pedp_list_intersections_rayset");
+}
+
+int pedp_intersections_last_path(pedp_ctx_t c, int *path, int *grid_status) {
+    PEDP_REQUIRE(c && path && grid_status, "pedp_intersections_last_path: null argument");
+    PEDP_REQUIRE(c->hits_last_path > 0, "pedp_intersections_last_path: no all-hits query has run on this context");
+    PEDP_HIP_CHECK(hipSetDevice(c->device));
+    PEDP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    *path = c->hits_last_path;
+    *grid_status = (c->hits_last_path == HITS_PATH_GRID && c->hits_status) ? ((volatile int *)c->hits_status)[0] : 0;
     return PEDP_OK;
 }
 

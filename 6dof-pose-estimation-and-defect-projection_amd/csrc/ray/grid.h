@@ -249,13 +249,14 @@ __device__ __forceinline__ void rast_fail(RastHdr *h, int why) {
     atomicOr(&h->reason, why);
 }
 
+template <class Sink>
 __device__ __forceinline__ void rast_test(const float4 nd, unsigned ray, const float *O, const TriRec &q, unsigned f,
-                                          unsigned long long *__restrict__ keys) {
+                                          const Sink &sink) {
     Ray r;
     r.ox = O[0]; r.oy = O[1]; r.oz = O[2];
     r.dx = nd.x; r.dy = nd.y; r.dz = nd.z;
     const MT m = mt_eval(r, q);
-    if (mt_accept(m)) atomicMin(&keys[ray], mt_key(m, f));
+    if (mt_accept(m)) sink.one(ray, m, f);
 }
 
 // The cells of the rays that can meet triangle q (origin O, frame A/E1/E2, grid u0/v0/su/sv, GX x GY): the
@@ -356,9 +357,12 @@ __global__ void rast_debug_ray_kernel(const float *__restrict__ rays6, int64_t N
     out[3 * i] = (float)kind; out[3 * i + 1] = (u - h->u0) * h->su; out[3 * i + 2] = (v - h->v0) * h->sv;
 }
 
+// (Sink, here and in the two kernels below: what an accepted pair is handed to -- HitMin for a cast, ray/all_hits.h's
+// for the all-hits queries, which need every pair met ONCE: DESIGN s4.24 names the lines that see to it)
+template <class Sink>
 __global__ __launch_bounds__(256) void rast_tri_kernel(const float *__restrict__ aos, int64_t F, RastHdr *__restrict__ h,
                                                       const unsigned *__restrict__ head, const float4 *__restrict__ nodes,
-                                                      RastItem *__restrict__ items, unsigned long long *__restrict__ keys,
+                                                      RastItem *__restrict__ items, Sink sink,
                                                       unsigned *__restrict__ full_list) {
     if (h->ok == 0) return;
     const int lane = threadIdx.x & 63;
@@ -445,7 +449,7 @@ __global__ __launch_bounds__(256) void rast_tri_kernel(const float *__restrict__
 #pragma unroll
             for (int j = 0; j < U; ++j)
                 if (idx[j] != RAST_NONE) {
-                    rast_test(nd[j], idx[j], O, q, (unsigned)f, keys);
+                    rast_test(nd[j], idx[j], O, q, (unsigned)f, sink);
                     idx[j] = __float_as_uint(nd[j].w);
                 }
             if (++steps > RAST_CHAIN_MAX) { rast_fail(h, 4); break; }
@@ -454,9 +458,10 @@ __global__ __launch_bounds__(256) void rast_tri_kernel(const float *__restrict__
 }
 
 // The listed triangles (no bounded image) against EVERY ray: a thread per ray, the records through scalar loads.
+template <class Sink>
 __global__ __launch_bounds__(256) void rast_full_kernel(const float *__restrict__ aos, const float *__restrict__ rays6, int64_t N,
                                                        const RastHdr *__restrict__ h, const unsigned *__restrict__ full_list,
-                                                       unsigned long long *__restrict__ keys) {
+                                                       Sink sink) {
     if (h->ok == 0) return;
     const int n = h->n_full < RAST_FULL_CAP ? h->n_full : RAST_FULL_CAP;
     if (n == 0) return;
@@ -465,21 +470,19 @@ __global__ __launch_bounds__(256) void rast_full_kernel(const float *__restrict_
     Ray r;
     r.ox = rays6[6 * i]; r.oy = rays6[6 * i + 1]; r.oz = rays6[6 * i + 2];
     r.dx = rays6[6 * i + 3]; r.dy = rays6[6 * i + 4]; r.dz = rays6[6 * i + 5];
-    unsigned long long best = KEY_MISS;
+    typename Sink::Acc acc = sink.start();
     for (int k = 0; k < n; ++k) {
         const unsigned f = full_list[k];  // wave-uniform
         const MT m = mt_eval(r, aos + (size_t)f * PEDP_TRI_STRIDE);
-        if (mt_accept(m)) {
-            const unsigned long long key = mt_key(m, f);
-            best = key < best ? key : best;
-        }
+        if (mt_accept(m)) sink.gather(acc, i, m, f);
     }
-    if (best != KEY_MISS) atomicMin(&keys[i], best);
+    sink.finish(acc, i);
 }
 
+template <class Sink>
 __global__ __launch_bounds__(256) void rast_item_kernel(const float *__restrict__ aos, RastHdr *__restrict__ h,
                                                        const unsigned *__restrict__ head, const float4 *__restrict__ nodes,
-                                                       const RastItem *__restrict__ items, unsigned long long *__restrict__ keys) {
+                                                       const RastItem *__restrict__ items, Sink sink) {
     if (h->ok == 0) return;
     const int n_items = h->n_items < RAST_ITEM_CAP ? h->n_items : RAST_ITEM_CAP;
     const int lane = threadIdx.x & 63;
@@ -509,7 +512,7 @@ __global__ __launch_bounds__(256) void rast_item_kernel(const float *__restrict_
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (idx[j] != RAST_NONE) {
-                    rast_test(nd[j], idx[j], O, q, (unsigned)I.tri, keys);
+                    rast_test(nd[j], idx[j], O, q, (unsigned)I.tri, sink);
                     idx[j] = __float_as_uint(nd[j].w);
                 }
             if (++steps > RAST_CHAIN_MAX) { rast_fail(h, 4); break; }

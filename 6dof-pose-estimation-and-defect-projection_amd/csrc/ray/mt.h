@@ -78,6 +78,21 @@ __device__ __forceinline__ unsigned long long mt_key(const MT &m, unsigned id) {
     return ((unsigned long long)tb << 32) | (unsigned long long)id;
 }
 
+// What a selector hands an accepted pair to.  The casts' sink: the closest hit, the packed atomicMin.  `one` takes a
+// pair as it is met; gather / finish let a thread that owns a ray fold its pairs before it touches memory.  (The
+// all-hits queries' sinks, ray/all_hits.h, have the same members.)
+struct HitMin {
+    unsigned long long *__restrict__ keys;
+    typedef unsigned long long Acc;
+    __device__ __forceinline__ Acc start() const { return KEY_MISS; }
+    __device__ __forceinline__ void one(unsigned ray, const MT &m, unsigned f) const { atomicMin(&keys[ray], mt_key(m, f)); }
+    __device__ __forceinline__ void gather(Acc &best, int64_t, const MT &m, unsigned f) const {
+        const unsigned long long key = mt_key(m, f);
+        best = key < best ? key : best;
+    }
+    __device__ __forceinline__ void finish(Acc best, int64_t ray) const { if (best != KEY_MISS) atomicMin(&keys[ray], best); }
+};
+
 // (for the atomic min / max of direction bounds in variants 3 and 4)
 __device__ __forceinline__ unsigned enc_f(float f) {  // order-preserving float -> uint
     unsigned b = __float_as_uint(f);

@@ -125,6 +125,42 @@ int pedp_debug_rast_rects(pedp_ctx_t ctx, pedp_mesh_t mesh, const float *rays6, 
  * synchronises on the second event. */
 int pedp_raycast_last_sweep_ms(pedp_ctx_t ctx, float *ms);
 
+/* ---------------------------------------------------------------- all-hits queries
+ * RaycastingScene.count_intersections / test_occlusions / list_intersections on the mesh handle.  A ray intersects a
+ * triangle exactly when the cast's own test accepts the pair (edges inclusive: a ray through a shared edge intersects
+ * both triangles); its t is the float32 quotient the cast forms, its (u, v) the cast's.  Rays with a zero, NaN or
+ * infinite direction intersect nothing.  rays6, N, mem as in pedp_raycast; N = 0 does nothing (a list: ray_splits[0] =
+ * 0, total 0); a mesh without triangles, or N >= 2^31 - 16, is PEDP_ERR_BAD_ARG.  The _rayset forms take a resident ray
+ * set in the place of rays6, N.  Path: pedp_raycast_configure's variant -- 0: the grid of variant 4 from 16,384 rays on
+ * and for a ray set (the exhaustive path once a query's grid pass has given up on those rays), 4: the grid, 1, 2, 3,
+ * 5: every ray against every triangle.  Rays the grid cannot hold are completed exhaustively on the device in the same
+ * call.  Every path gives identical bits.  The casts' state (a ray set's keys, the grid's headers, the casts' status
+ * words and automatic variant choice) is left as a cast expects it.
+ *
+ * counts: int32 per ray, the number of intersecting triangles. */
+int pedp_count_intersections(pedp_ctx_t ctx, pedp_mesh_t mesh, const float *rays6, int64_t N, int mem, int32_t *counts);
+int pedp_count_intersections_rayset(pedp_ctx_t ctx, pedp_mesh_t mesh, pedp_rayset_t rays, int mem, int32_t *counts);
+/* occluded: one byte per ray, 1 when an intersecting triangle has tnear <= t <= tfar (float32 compare, both ends
+ * inclusive; a NaN bound gives 0), else 0. */
+int pedp_test_occlusions(pedp_ctx_t ctx, pedp_mesh_t mesh, const float *rays6, int64_t N, int mem, float tnear, float tfar,
+                         uint8_t *occluded);
+int pedp_test_occlusions_rayset(pedp_ctx_t ctx, pedp_mesh_t mesh, pedp_rayset_t rays, int mem, float tnear, float tfar,
+                                uint8_t *occluded);
+/* Every intersection: ray_splits (N + 1; ray i owns entries ray_splits[i] .. ray_splits[i + 1] - 1), and per entry ray_ids,
+ * t_hit, prim_ids, uvs (x 2).  Within a ray the entries are ordered by t, then by triangle index -- the order of the
+ * cast's key, so a ray's first entry is its pedp_raycast result bit for bit.  The outputs hold `capacity` entries;
+ * *total (host) is always reported and ray_splits always complete; if total > capacity nothing else is written and the
+ * call returns PEDP_ERR_BAD_ARG, like pedp_project_heatmap.  The call waits for the stream once (total sizes the rest). */
+int pedp_list_intersections(pedp_ctx_t ctx, pedp_mesh_t mesh, const float *rays6, int64_t N, int mem, int64_t capacity,
+                            int64_t *ray_splits, int64_t *ray_ids, float *t_hit, uint32_t *prim_ids, float *uvs, int64_t *total);
+int pedp_list_intersections_rayset(pedp_ctx_t ctx, pedp_mesh_t mesh, pedp_rayset_t rays, int mem, int64_t capacity,
+                                   int64_t *ray_splits, int64_t *ray_ids, float *t_hit, uint32_t *prim_ids, float *uvs,
+                                   int64_t *total);
+/* How the last all-hits query of this context was answered: *path 4 (the grid; *grid_status 0, or why the exhaustive
+ * completion had to answer instead, bits as in pedp_raycast_last_variant) or 1 (every ray against every triangle).
+ * Synchronises the stream. */
+int pedp_intersections_last_path(pedp_ctx_t ctx, int *path, int *grid_status);
+
 /* ---------------------------------------------------------------- fused defect projection
  * the per-frame work around cast_rays moved onto the device.
  *
