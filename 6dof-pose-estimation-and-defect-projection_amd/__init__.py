@@ -17,6 +17,7 @@ Layout
   coverage.py      CoverageMap: which faces of the model the camera has seen, and how well, over a DefectMap's faces
   view_plan.py     ViewPlanner: next-best-view planning, the gain of candidate camera poses over a CoverageMap; orbit_views
   deviation_map.py DeviationMap: per-face statistics of the signed deviation over frames, regions with their volume
+  mesh_refine.py   refine_mesh: the model's faces split to a maximum edge length, each with its CAD face; edge_for_camera
   surface_fit.py   fit_to_surface: robust best fit of a scene cloud to the posed surface itself; refit_pose, fit_frame_to_surface
   raycasting_scene.py RaycastingScene: cast_rays, count / list_intersections, test_occlusions and the distance queries on one mesh
   compat.py        `from pedp_hip.compat import *` in place of `from src import *` (run.py:3)
@@ -29,5 +30,7 @@ from .defect_map import DefectMap
 from .coverage import CoverageMap
 from .view_plan import ViewPlanner, orbit_views
 from .deviation_map import DeviationMap
+from .mesh_refine import RefinedMesh, edge_for_camera, refine_mesh
 
-__all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap"]
+__all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap", "refine_mesh",
+           "RefinedMesh", "edge_for_camera"]

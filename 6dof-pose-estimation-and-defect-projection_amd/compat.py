@@ -14,7 +14,9 @@ exact cloud-to-mesh distance with the deviation heat map (`closest_points`, `com
 is measured in (`fit_to_surface`, `refit_pose`, `fit_frame_to_surface`, surface_fit.py), and the defect map on the model in the place of run.py:196-201's list of
 hit clouds (`DefectMap`, defect_map.py), and the inspection coverage over its faces, which the reference has no
 counterpart of (`CoverageMap`, coverage.py), and the next camera poses that coverage asks for (`ViewPlanner`,
-`orbit_views`, view_plan.py); the Dash app, sensor
+`orbit_views`, view_plan.py), and the refinement that gives a coarse CAD model the resolution those per-face maps need
+(`refine_mesh`, `RefinedMesh`, `edge_for_camera`, mesh_refine.py; the reference loads a separately prepared model file,
+datareader.py:720-724); the Dash app, sensor
 code and the networks' weights stay the reference's own.
 """
 import numpy as np
@@ -68,6 +70,7 @@ from .defect_map import DefectMap  # noqa: E402,F401  (run.py:61, :119, :196-201
 from .coverage import CoverageMap  # noqa: E402,F401  (no counterpart: run.py never says what was not inspected)
 from .view_plan import ViewPlanner, orbit_views  # noqa: E402,F401  (no counterpart: where to point the camera next)
 from .deviation_map import DeviationMap  # noqa: E402,F401  (no counterpart: how far off each face is, over all frames)
+from .mesh_refine import RefinedMesh, edge_for_camera, refine_mesh  # noqa: E402,F401  (datareader.py:720-724 loads an offline-refined model.ply)
 from .raycasting_scene import RaycastingScene  # noqa: E402,F401  (defect_projection.py:245-256 builds one; here with all its queries)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
@@ -106,4 +109,5 @@ __all__ = [
     "Solid", "compute_signed_distance", "compute_occupancy", "signed_closest_points", "signed_deviation", "split_deviation",
     "fit_to_surface", "refit_pose", "fit_frame_to_surface",
     "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap", "RaycastingScene",
+    "refine_mesh", "RefinedMesh", "edge_for_camera",
 ]

@@ -1,5 +1,6 @@
 // The topology of an indexed triangle mesh, shared by the defect map (pedp_defectmap.hip) and the solid
-// (pedp_solid.hip): the weld of its vertices and its edge slots sorted by their welded end points.
+// (pedp_solid.hip): the weld of its vertices and its edge slots sorted by their welded end points.  The refinement
+// (pedp_refine.hip) takes the weld and the slots' numbering from here and keys only the slots of its long edges.
 //   weld        w[v] = the lowest index of a vertex at v's position; positions compare with ==, so -0 equals +0, and a
 //               vertex with a NaN is welded to nothing (w[v] = v)
 //   edge slots  slot e = 3 f + k joins corners k and (k + 1) % 3 of face f; its key is (min w, max w), or all ones where

@@ -1355,6 +1355,65 @@ int pedp_deviation_map_summary(pedp_deviation_map_t dev, const pedp_deviation_cr
 int pedp_deviation_map_regions(pedp_deviation_map_t dev, const pedp_deviation_criteria *c, int32_t grow, int mem, int32_t *labels,
                                int64_t capacity, pedp_deviation_region *table, int64_t *n_regions);
 
+/* ---------------------------------------------------------------- mesh refinement: faces split to a maximum edge length
+ * The defect, coverage and deviation maps and the view planner speak per FACE of the model, so a face is the smallest
+ * thing they can say anything about -- and a CAD export makes a flat side two triangles.  pedp_mesh_refine gives a model
+ * a resolution: every edge longer than max_edge is bisected, round after round, until none is left, and every refined
+ * face carries the face of the input it came from, so that each map can be laid over the refined model and read back
+ * per CAD face.  The reference prepares a second model file offline for the same need (datareader.py:720-724).  The
+ * contract is DESIGN.md s4.25.  Everything is float64, no contraction, every expression in the order written.
+ *
+ * pedp_mesh_refine: verts V x 3 float64, tris F x 3, host or device memory by `mem`; max_edge > 0; max_faces caps the
+ * number of faces of the result (and of the input).  PEDP_ERR_BAD_ARG: an index >= V, a vertex with a non-finite
+ * coordinate, max_edge that is not a positive finite number, F > 2^28, V > 2^32 - 2.
+ *   weld         w[v] = the lowest index of a vertex at v's position, compared with == (the defect map's weld, one
+ *                implementation); a vertex made by a round is unique: w[v] = v
+ *   one round    over the current vertices and faces:
+ *     long edge    edge (a, b) of a face is LONG iff (dx dx + dy dy) + dz dz > max_edge max_edge with d = b - a.  The
+ *                  test is bit-symmetric in a and b, so the faces at an edge always agree, also where the input
+ *                  duplicates vertices along the edge (OBJ exports with split normals do)
+ *     vertices     every distinct long edge, told apart by its key (min(w_a, w_b), max(w_a, w_b)), gets ONE new vertex
+ *                  at 0.5 (a + b) per component (symmetric too); the new vertices follow all existing ones in ascending
+ *                  key order
+ *     children     every face is replaced, in place in the face order, by 1 ... 4 children that keep its winding;
+ *                  corners keep their own indices, not the welded ones.  With edge k = (c_k, c_(k+1)%3):
+ *                    none long    the face itself
+ *                    one long     rotated so that it is edge 0, m its midpoint: (c0, m, c2), (m, c1, c2)
+ *                    two long     rotated so that the short edge is edge 2, m0 = mid(c0, c1), m1 = mid(c1, c2):
+ *                                 (m0, c1, m1), then (c0, m0, c2), (m0, m1, c2) if |m0 - c2|^2 <= |m1 - c0|^2 (the same
+ *                                 squared-length expression), else (c0, m0, m1), (c0, m1, c2)
+ *                    three long   (c0, m0, m2), (m0, c1, m1), (m2, m1, c2), (m0, m1, m2)
+ *     parents      parent_face of a child is its parent's; initially parent_face[f] = f
+ *   rounds       repeat until a round finds no long edge; a mesh without one is returned unchanged after 0 rounds.  They
+ *                end: a 1- or 3-split makes no inner edge longer than max_edge or half an edge of the parent, and a
+ *                2-split's diagonal is a median, at most sqrt(3) / 2 of the parent's longest edge.  More faces than
+ *                max_faces after a round, more than 64 rounds or more than 2^32 - 2 vertices: PEDP_ERR_BAD_ARG, *out
+ *                stays null and *faces_reached (nullable) reports that round's face count; on success it is F_out
+ * What follows: the input's V vertices are kept, in order; parent_face is non-decreasing, so the children of an input
+ * face are a contiguous run; the surface is unchanged (a new vertex is the midpoint of two vertices of one face); a closed,
+ * consistently oriented input stays so, both sides of every edge hold bit-identical points, and they still do after
+ * rounding to the mesh handle's float32 records, which is what pedp_solid_create needs.  The result is a pure function of
+ * the arrays and max_edge: the same bits on every call and on any context, whatever the context did before (new
+ * vertices are numbered by the stable pooled sort, children are placed by a scan; the only atomics are integer minima).
+ * Per round the host reads two counts to size the round's outputs, so the call waits on the context's stream:
+ * PEDP_ERR_BAD_ARG while a registration is pending on ctx (pedp_icp_begin).  The handle keeps the result on the device.
+ *
+ * pedp_refined_size: the result's vertex and face counts and the number of rounds that split something.
+ * pedp_refined_read: verts V_out x 3, tris F_out x 3, parent_face F_out, each nullable, host or device memory by `mem`;
+ * PEDP_DEVICE only enqueues copies on the context's stream; PEDP_HOST is PEDP_ERR_BAD_ARG while a registration is pending.
+ * pedp_refined_reduce: folds child_values (F_out) to parent_values (F) over each input face's run, in ascending child
+ * index, starting from the run's first value y_0 (every input face has a child): PEDP_REDUCE_SUM acc = acc + y;
+ * PEDP_REDUCE_MAX acc = y where y > acc or y is a NaN; PEDP_REDUCE_MIN likewise with <.  A lane per input face; mem as
+ * for pedp_refined_read. */
+typedef struct pedp_refined_s *pedp_refined_t;
+enum { PEDP_REDUCE_MAX = 0, PEDP_REDUCE_MIN = 1, PEDP_REDUCE_SUM = 2 };
+int pedp_mesh_refine(pedp_ctx_t ctx, const double *verts, int64_t V, const uint32_t *tris, int64_t F, int mem, double max_edge,
+                     int64_t max_faces, pedp_refined_t *out, int64_t *faces_reached);
+int pedp_refined_size(pedp_refined_t refined, int64_t *V_out, int64_t *F_out, int32_t *rounds);
+int pedp_refined_read(pedp_refined_t refined, int mem, double *verts, uint32_t *tris, int32_t *parent_face);
+int pedp_refined_reduce(pedp_refined_t refined, int op, int mem, const double *child_values, double *parent_values);
+int pedp_refined_destroy(pedp_refined_t refined);
+
 /* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
  * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
  * The contract is DESIGN.md s4.11.  With pos = mask > 0, truthy = mask.astype(bool) (for a float32 mask they differ on
