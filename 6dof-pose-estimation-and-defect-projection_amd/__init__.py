@@ -18,6 +18,7 @@ Layout
   view_plan.py     ViewPlanner: next-best-view planning, the gain of candidate camera poses over a CoverageMap; orbit_views
   deviation_map.py DeviationMap: per-face statistics of the signed deviation over frames, regions with their volume
   mesh_refine.py   refine_mesh: the model's faces split to a maximum edge length, each with its CAD face; edge_for_camera
+  mesh_sample.py   sample_points_uniformly / sample_points_poisson_disk: the model's cloud from its mesh; thin_to_spacing, mesh_to_pcd
   surface_fit.py   fit_to_surface: robust best fit of a scene cloud to the posed surface itself; refit_pose, fit_frame_to_surface
   raycasting_scene.py RaycastingScene: cast_rays, count / list_intersections, test_occlusions and the distance queries on one mesh
   compat.py        `from pedp_hip.compat import *` in place of `from src import *` (run.py:3)
@@ -31,6 +32,8 @@ from .coverage import CoverageMap
 from .view_plan import ViewPlanner, orbit_views
 from .deviation_map import DeviationMap
 from .mesh_refine import RefinedMesh, edge_for_camera, refine_mesh
+from .mesh_sample import MeshSampler, mesh_to_pcd, sample_points_poisson_disk, sample_points_uniformly, thin_to_spacing
 
 __all__ = ["_lib", "PedpError", "LIB_PATH", "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap", "refine_mesh",
-           "RefinedMesh", "edge_for_camera"]
+           "RefinedMesh", "edge_for_camera", "sample_points_uniformly", "sample_points_poisson_disk", "thin_to_spacing", "mesh_to_pcd",
+           "MeshSampler"]

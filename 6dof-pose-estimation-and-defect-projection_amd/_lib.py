@@ -231,6 +231,18 @@ PROTOTYPES = {
     "pedp_refined_read": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_refined_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pedp_refined_destroy": (C.c_int, [C.c_void_p]),
+    "pedp_mesh_sampler_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, _P(C.c_void_p)]),
+    "pedp_mesh_sampler_destroy": (C.c_int, [C.c_void_p]),
+    "pedp_mesh_sampler_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pedp_mesh_sample": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "pedp_points_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_int, C.c_int64, C.c_void_p, _P(C.c_int64),
+                                   _P(C.c_int32)]),
+    "pedp_points_thin_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_uint64, C.c_int, C.c_void_p,
+                                         _P(C.c_double), _P(C.c_int32), _P(C.c_int32)]),
+    "pedp_mesh_sample_disk": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_double, C.c_int64, C.c_int, _P(C.c_int64), _P(C.c_int64),
+                                        _P(C.c_double), _P(C.c_int32), _P(C.c_int32)]),
+    "pedp_mesh_sample_disk_read": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pedp_mask_depth_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "pedp_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),

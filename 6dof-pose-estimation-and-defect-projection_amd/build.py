@@ -38,6 +38,7 @@ SOURCES = {
     "pedp_deviationmap.hip": [],
     "pedp_solid.hip": [],
     "pedp_refine.hip": [],
+    "pedp_sample.hip": [],
     "pedp_surface_fit.hip": [],
     "pedp_conv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "pedp_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

@@ -16,7 +16,8 @@ hit clouds (`DefectMap`, defect_map.py), and the inspection coverage over its fa
 counterpart of (`CoverageMap`, coverage.py), and the next camera poses that coverage asks for (`ViewPlanner`,
 `orbit_views`, view_plan.py), and the refinement that gives a coarse CAD model the resolution those per-face maps need
 (`refine_mesh`, `RefinedMesh`, `edge_for_camera`, mesh_refine.py; the reference loads a separately prepared model file,
-datareader.py:720-724); the Dash app, sensor
+datareader.py:720-724), and the sampling that makes the model's cloud from the model's mesh (`mesh_to_pcd`,
+`sample_points_uniformly`, `sample_points_poisson_disk`, `thin_to_spacing`, mesh_sample.py; pose_estimation.py:453-464); the Dash app, sensor
 code and the networks' weights stay the reference's own.
 """
 import numpy as np
@@ -71,6 +72,7 @@ from .coverage import CoverageMap  # noqa: E402,F401  (no counterpart: run.py ne
 from .view_plan import ViewPlanner, orbit_views  # noqa: E402,F401  (no counterpart: where to point the camera next)
 from .deviation_map import DeviationMap  # noqa: E402,F401  (no counterpart: how far off each face is, over all frames)
 from .mesh_refine import RefinedMesh, edge_for_camera, refine_mesh  # noqa: E402,F401  (datareader.py:720-724 loads an offline-refined model.ply)
+from .mesh_sample import mesh_to_pcd, sample_points_poisson_disk, sample_points_uniformly, thin_to_spacing  # noqa: E402,F401  (pose_estimation.py:453-464)
 from .raycasting_scene import RaycastingScene  # noqa: E402,F401  (defect_projection.py:245-256 builds one; here with all its queries)
 from .networks import RefineNet, ScoreNetMultiPair, load_refiner, load_scorer  # noqa: E402,F401  (learning/models/*.py)
 
@@ -110,4 +112,5 @@ __all__ = [
     "fit_to_surface", "refit_pose", "fit_frame_to_surface",
     "DefectMap", "CoverageMap", "ViewPlanner", "orbit_views", "DeviationMap", "RaycastingScene",
     "refine_mesh", "RefinedMesh", "edge_for_camera",
+    "mesh_to_pcd", "sample_points_uniformly", "sample_points_poisson_disk", "thin_to_spacing",
 ]

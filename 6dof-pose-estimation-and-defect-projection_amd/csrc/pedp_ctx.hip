@@ -294,6 +294,8 @@ void pedp_ctx_destroy(pedp_ctx_t c) {
     c->closest_io.release();
     c->fit_ws.release();
     c->fit_io.release();
+    c->sample_ws.release();
+    c->sample_io.release();
     c->stats_ws.release();
     c->stats_io.release();
     if (c->pinned) (void)hipHostFree(c->pinned);

@@ -188,6 +188,8 @@ struct pedp_ctx_s {
     pedp_scratch closest_io; // closest points: inputs and outputs of host-memory calls
     pedp_scratch fit_ws;     // surface fit: the state, the search's outputs, the blocks' partial sums, the trace (pedp_surface_fit.hip)
     pedp_scratch fit_io;     // surface fit: the points of a host-memory call
+    pedp_scratch sample_ws;  // thinning to a spacing: the grid index, the states, the scans' and the sort's scratch (pedp_sample.hip)
+    pedp_scratch sample_io;  // thinning a given cloud: its points, keys and the kept indices of a host-memory call
     int closest_mode = 0;    // pedp_closest_configure: 0 culled (the kernel by N), 1 exhaustive, 2 / 3 one culled kernel
 };
 

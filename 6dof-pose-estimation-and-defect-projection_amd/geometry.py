@@ -313,6 +313,19 @@ class TriangleMesh:
         self.vertex_normals = acc / np.where(ln > 0, ln, 1.0)
         return self
 
+    def sample_points_uniformly(self, number_of_points=100, use_triangle_normal=False, **extra):
+        """Open3D's method; extra: seed, first, ctx (pedp_hip.mesh_sample.sample_points_uniformly)."""
+        from . import mesh_sample
+
+        return mesh_sample.sample_points_uniformly(self, number_of_points, use_triangle_normal, **extra)
+
+    def sample_points_poisson_disk(self, number_of_points=None, init_factor=5, pcl=None, use_triangle_normal=False, **extra):
+        """Open3D's method; extra: spacing (in the place of number_of_points), seed, ctx
+        (pedp_hip.mesh_sample.sample_points_poisson_disk)."""
+        from . import mesh_sample
+
+        return mesh_sample.sample_points_poisson_disk(self, number_of_points, init_factor, pcl, use_triangle_normal, **extra)
+
     def __deepcopy__(self, memo):
         m = TriangleMesh(np.array(self.vertices), np.array(self.triangles))
         m.vertex_normals = np.array(self.vertex_normals)

@@ -39,14 +39,15 @@ def edge_for_camera(K, distance, pixels=2.0):
     return pixels * distance / f
 
 
-def _mesh_arrays(mesh):
-    """(vertices V x 3 float64, triangles F x 3 as 32-bit indices, device) on the side the mesh came from."""
+def _mesh_arrays(mesh, who="refine_mesh"):
+    """(vertices V x 3 float64, triangles F x 3 as 32-bit indices, device) on the side the mesh came from; `who` names the
+    caller in the errors."""
     if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
         v, t = mesh
     elif hasattr(mesh, "vertices") and hasattr(mesh, "triangles"):
         v, t = mesh.vertices, mesh.triangles
     else:
-        raise _lib.PedpError(f"refine_mesh: mesh must hold .vertices and .triangles or be a (vertices, triangles) pair, "
+        raise _lib.PedpError(f"{who}: mesh must hold .vertices and .triangles or be a (vertices, triangles) pair, "
                              f"got {type(mesh).__name__}")
     dev = device_of(v, t)
     if dev is None:
@@ -54,14 +55,14 @@ def _mesh_arrays(mesh):
         t = t.detach().numpy() if is_torch(t) else np.asarray(t)
     for name, a in (("vertices", v), ("triangles", t)):
         if not hasattr(a, "shape") or not hasattr(a, "dtype"):
-            raise _lib.PedpError(f"refine_mesh: {name} must be an array or a tensor, got {type(a).__name__}")
+            raise _lib.PedpError(f"{who}: {name} must be an array or a tensor, got {type(a).__name__}")
     kind_v, kind_t = str(v.dtype).replace("torch.", ""), str(t.dtype).replace("torch.", "")
     if len(v.shape) != 2 or v.shape[1] != 3 or kind_v not in ("float32", "float64"):
-        raise _lib.PedpError(f"refine_mesh: vertices must be a V x 3 float array, got {kind_v} of shape {tuple(v.shape)}")
+        raise _lib.PedpError(f"{who}: vertices must be a V x 3 float array, got {kind_v} of shape {tuple(v.shape)}")
     if int(np.prod(tuple(t.shape))) == 0:
         t = t.reshape(0, 3)
     if len(t.shape) != 2 or t.shape[1] != 3 or kind_t not in (("int32", "uint32", "int64") + (("uint64",) if dev is None else ())):
-        raise _lib.PedpError(f"refine_mesh: triangles must be an F x 3 integer array, got {kind_t} of shape {tuple(t.shape)}")
+        raise _lib.PedpError(f"{who}: triangles must be an F x 3 integer array, got {kind_t} of shape {tuple(t.shape)}")
     if dev is not None:
         import torch
 
@@ -69,13 +70,13 @@ def _mesh_arrays(mesh):
         t = t.to(dev)
         if t.dtype == torch.int64:
             if t.numel() and (int(t.min()) < 0 or int(t.max()) > MISS):
-                raise _lib.PedpError("refine_mesh: triangle indices must lie in [0, 2^32)")
+                raise _lib.PedpError(f"{who}: triangle indices must lie in [0, 2^32)")
             t = torch.where(t > 0x7FFFFFFF, t - (1 << 32), t).to(torch.int32)      # the same 32 bits
         elif t.dtype != torch.int32:
             t = t.contiguous().view(torch.int32)
         return v, t.contiguous(), dev
     if len(t) and (t.min() < 0 or t.max() > MISS):
-        raise _lib.PedpError("refine_mesh: triangle indices must lie in [0, 2^32)")
+        raise _lib.PedpError(f"{who}: triangle indices must lie in [0, 2^32)")
     return np.ascontiguousarray(v, dtype=np.float64), np.ascontiguousarray(t, dtype=np.uint32), None
 
 

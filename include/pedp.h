@@ -1414,6 +1414,75 @@ int pedp_refined_read(pedp_refined_t refined, int mem, double *verts, uint32_t *
 int pedp_refined_reduce(pedp_refined_t refined, int op, int mem, const double *child_values, double *parent_values);
 int pedp_refined_destroy(pedp_refined_t refined);
 
+/* ---------------------------------------------------------------- surface sampling: uniform and Poisson-disk model clouds
+ * The cloud of the model's surface (model.ply, the ICP target and the pose errors' points) made from the model's mesh,
+ * in the place of Open3D's sample_points_uniformly / sample_points_poisson_disk (src/pose_estimation.py:453-464).
+ * Everything is a pure function of (mesh, seed, spacing): the same bits on every call and context.  float64, no fused
+ * multiply-add, every sum and product in the order written.  The contract is DESIGN.md s4.26:
+ *   generator   Philox4x32-10.  Sample k (a uint64, global: a call for [first, first + n) returns that slice of one
+ *               endless sequence, k wrapping at 2^64) draws x = philox(counter (k_lo, k_hi, 0, 0), key (seed_lo, seed_hi))
+ *               and y = philox(counter (k_lo, k_hi, 1, 0), the same key).
+ *   face        area_f = 0.5 * sqrt((cx^2 + cy^2) + cz^2) of c = e1 x e2, e1 = v1 - v0, e2 = v2 - v0; amax the largest
+ *               finite area; w_f = (uint64) floor((area_f / amax) * 2^32), 0 for an area that is 0 or not finite; C the
+ *               inclusive integer prefix sum of w, W its total; t = mulhi64((x0 << 32) | x1, W); the face is the first f
+ *               with C[f] > t.  A face of weight 0 is never chosen (info: unsampled_faces).
+ *   point       u1 = (((x2 << 32) | x3) >> 11) * 2^-53, u2 = (((y0 << 32) | y1) >> 11) * 2^-53, s = sqrt(u1), a = 1 - s,
+ *               b = s * (1 - u2), c = s * u2, p = (a * v0 + b * v1) + c * v2 per component.  barycentric = (a, b, c).
+ *   normal      PEDP_SAMPLE_NORMALS_VERTEX: (a * n0 + b * n1) + c * n2 of the vertex normals, not renormalised;
+ *               PEDP_SAMPLE_NORMALS_TRIANGLE: c / sqrt((cx^2 + cy^2) + cz^2) of the face's e1 x e2.
+ *   thinning    S(r) of points p_i, i < M: point i has the key (z_i << 32) | (i mod 2^32), the lower key wins; z_i = y2 of
+ *               a mesh sample's own draw, and word 0 of philox(counter (i_lo, i_hi, 2, 0), key seed) for a given cloud.
+ *               i and j conflict iff ((dx^2 + dy^2) + dz^2) < r * r (strict).  S(r) is what a visit in ascending key
+ *               order keeps that keeps a point iff it conflicts with no kept point.  The device finds it in rounds
+ *               of final decisions (REMOVED once a conflicting lower key is KEPT, KEPT once all conflicting lower keys
+ *               are REMOVED), so it depends on no schedule; the rounds it took are reported, not part of the contract.
+ *               No two points of S(r) are closer than r, and every point is closer than r to one of S(r).
+ *   count       M = init_factor * N samples k = 0 .. M - 1; r bisected on [0, 2 * sqrt(area / N)] for 24 halvings,
+ *               mid = 0.5 * (lo + hi), |S(mid)| >= N ? lo = mid : hi = mid; r* = the final lo; of S(r*) the N lowest
+ *               keys.  area = the faces' areas summed in face order.  Always exactly N points, none closer than r*.
+ *   spacing     S(r) of M = ceil((init_factor * area) / (r * r)) samples k = 0 .. M - 1 (at least 1).
+ *
+ * pedp_mesh_sampler_create: verts V x 3 float64, tris F x 3 (1 <= F <= 2^24), vertex_normals V x 3 or null, all in host
+ * or device memory by `mem`; the handle keeps copies and the prefix sum on the device.  PEDP_ERR_BAD_ARG for an index
+ * outside the vertices, a non-finite coordinate, or W = 0 (no face has an area).  The call waits on the context's stream.
+ * pedp_mesh_sample: samples [first, first + n) to points n x 3, face_ids n, barycentric n x 3, normals_out n x 3 (each
+ * but points nullable; normals_out needed unless normals is PEDP_SAMPLE_NORMALS_NONE).  PEDP_DEVICE only enqueues.
+ * pedp_points_thin: S(spacing) of a given cloud (n x 3, finite), spacing >= 0: the kept indices in ascending order to
+ * kept (capacity entries), their number to *count -- larger than capacity: come back with that many.
+ * pedp_points_thin_count: the count form on a given cloud, bisected on [0, spacing_max]: exactly number_of_points (<= n)
+ * indices in ascending order to kept, r* to *spacing, the last thinning's rounds, and the thinnings run to *probes.
+ * pedp_mesh_sample_disk: the count form (number_of_points >= 1, spacing < 0) or the spacing form (number_of_points 0,
+ * spacing > 0) on the mesh; the draw and the kept set stay on the device in the handle until the next call.  *count kept
+ * samples of *drawn, *spacing_out = r* or the spacing given.  pedp_mesh_sample_disk_read: the kept samples in ascending
+ * sample index: points, face_ids, barycentric, normals_out (only after a draw with normals), sample_index, each nullable.
+ * The thinning calls read a few counters per group of rounds: they wait on the context's stream and are
+ * PEDP_ERR_BAD_ARG while a registration is pending on it. */
+typedef struct pedp_mesh_sampler_s *pedp_mesh_sampler_t;
+enum { PEDP_SAMPLE_NORMALS_NONE = 0, PEDP_SAMPLE_NORMALS_VERTEX = 1, PEDP_SAMPLE_NORMALS_TRIANGLE = 2 };
+typedef struct {
+    int64_t vertices, faces;
+    int64_t unsampled_faces;   /* faces of weight 0: no area, or below 2^-32 of the largest */
+    uint64_t total_weight;     /* W */
+    double area;               /* the faces' areas summed in face order */
+    double largest_area;       /* amax */
+    int32_t has_vertex_normals;
+    int32_t reserved;
+} pedp_mesh_sampler_info_t;
+int pedp_mesh_sampler_create(pedp_ctx_t ctx, const double *verts, int64_t V, const uint32_t *tris, int64_t F, const double *vertex_normals,
+                             int mem, pedp_mesh_sampler_t *out);
+int pedp_mesh_sampler_destroy(pedp_mesh_sampler_t sampler);
+int pedp_mesh_sampler_info(pedp_mesh_sampler_t sampler, pedp_mesh_sampler_info_t *info);
+int pedp_mesh_sample(pedp_mesh_sampler_t sampler, uint64_t seed, uint64_t first, int64_t n, int normals, int mem, double *points,
+                     int32_t *face_ids, double *barycentric, double *normals_out);
+int pedp_points_thin(pedp_ctx_t ctx, const double *points, int64_t n, double spacing, uint64_t seed, int mem, int64_t capacity, int32_t *kept,
+                     int64_t *count, int32_t *rounds);
+int pedp_points_thin_count(pedp_ctx_t ctx, const double *points, int64_t n, int64_t number_of_points, double spacing_max, uint64_t seed,
+                           int mem, int32_t *kept, double *spacing, int32_t *rounds, int32_t *probes);
+int pedp_mesh_sample_disk(pedp_mesh_sampler_t sampler, uint64_t seed, int64_t number_of_points, double spacing, int64_t init_factor,
+                          int normals, int64_t *count, int64_t *drawn, double *spacing_out, int32_t *rounds, int32_t *probes);
+int pedp_mesh_sample_disk_read(pedp_mesh_sampler_t sampler, int mem, double *points, int32_t *face_ids, double *barycentric,
+                               double *normals_out, int32_t *sample_index);
+
 /* ---------------------------------------------------------------- mask / depth statistics (guess_translation, register's gate)
  * What estimater.py:135-147 and :182-183 take from a frame with np.where, np.median and a sum, in one call on the device.
  * The contract is DESIGN.md s4.11.  With pos = mask > 0, truthy = mask.astype(bool) (for a float32 mask they differ on
